@@ -14,6 +14,13 @@ W untimed warm-up steps, then exactly K timed steps bracketed by barrier + devic
 sides; the time is the MAX over ranks; rank 0 prints one JSON line. ``value`` is the whole-job
 aggregate (images/s over all ranks).
 
+A plain run does only that: set up, warm up, time the K steps, print the line. ``--dump-outputs DIR``
+also writes what the last timed step computed (loss, logits, updated parameters, gradients) as
+``DIR/<name>.npy``; the inputs and initial weights are seeded, so two builds can be compared array
+for array. Everything else the benchmark measures -- the reference batch (bs 4), the transposed
+decoder, ``train_model`` on an on-disk dataset, serving FPS / latency -- runs only with ``--full``
+(``--extras 0`` / ``--serve 0`` then switch the two groups off again).
+
 The step is the full reference training step (``scripts/train_segmenter.py:156-165``): forward,
 BCEWithLogits loss, backward, Adam(lr=1e-4) -- on random-init weights of the reference
 architecture (``UNet(3, 1)``, bilinear decoder) and synthetic 256x256 RGB images / binary masks.
@@ -63,13 +70,24 @@ def parse():
                    help="gradient all-reduce dtype (bf16: half the xGMI bytes, fp32 accumulate in Adam)")
     p.add_argument("--ddp-force", type=int, default=0,
                    help="1: run the DDP path (RCCL process group, bucketed all-reduce hooks) even at world 1")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline measurement also run the secondary ones (--extras, --serve); "
+                        "a run without it times the headline step only")
     p.add_argument("--extras", type=int, default=-1,
-                   help="also report ref_batch_imgs_per_s (bs 4 step) and train_model_imgs_per_s (train_model on an "
-                        "on-disk synthetic PNG dataset, incl. data gather/H2D) and transposed_imgs_per_s (the "
-                        "transposed-conv decoder at the same batch); default: on for 1-GPU native runs")
+                   help="with --full: also report ref_batch_imgs_per_s (bs 4 step) and train_model_imgs_per_s "
+                        "(train_model on an on-disk synthetic PNG dataset, incl. data gather/H2D) and "
+                        "transposed_imgs_per_s (the transposed-conv decoder at the same batch); default: on for "
+                        "1-GPU native --full runs")
     p.add_argument("--serve", type=int, default=-1,
-                   help="also measure e2e serving FPS / p50 latency (default: on for single-GPU runs)")
-    return p.parse_args()
+                   help="with --full: also measure e2e serving FPS / p50 latency (default: on for single-GPU "
+                        "native --full runs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                        "(float32; arrays above 4 Mi elements as a fixed seeded sample; rank 0 only)")
+    args = p.parse_args()
+    if not args.full and (args.extras > 0 or args.serve > 0):
+        p.error("--extras 1 / --serve 1 need --full")
+    return args
 
 
 def self_launch(args) -> "int | None":
@@ -140,6 +158,7 @@ def barrier(world, dev):
 
 def make_eager_step(args, dev, world):
     from robotic_discovery_platform_amd.models.unet_ref import UNet
+    torch.manual_seed(0)  # same initial weights in every run, as build_bench_step does for the native step
     model = UNet(3, 1, bilinear=(args.decoder == "bilinear")).to(dev).to(memory_format=torch.channels_last)
     if world > 1:
         model = torch.nn.parallel.DistributedDataParallel(model, device_ids=[dev.index] if dev.type == "cuda" else None,
@@ -151,6 +170,8 @@ def make_eager_step(args, dev, world):
     y = (torch.rand(args.batch, 1, args.size, args.size, generator=g) > 0.5).float().to(dev)
     amp = dev.type == "cuda"
 
+    last = {}
+
     def step():
         opt.zero_grad(set_to_none=True)
         with torch.autocast(device_type=dev.type, dtype=torch.bfloat16, enabled=amp):
@@ -158,16 +179,57 @@ def make_eager_step(args, dev, world):
         loss = crit(out.float(), y)
         loss.backward()
         opt.step()
+        last["loss"], last["logits"] = loss, out
         return loss
 
+    def outputs():
+        params = [p for p in model.parameters()]
+        return {"loss": last["loss"].detach().reshape(1), "logits": last["logits"].detach(),
+                "params": torch.cat([p.detach().reshape(-1) for p in params]),
+                "grads": torch.cat([p.grad.reshape(-1) for p in params])}
+
+    step.outputs = outputs
     return step
 
 
 def make_native_step(args, dev, world):
     from robotic_discovery_platform_amd.train.engine import build_bench_step
-    return build_bench_step(batch=args.batch, size=args.size, decoder=args.decoder, device=dev,
+    step = build_bench_step(batch=args.batch, size=args.size, decoder=args.decoder, device=dev,
                             world=world, graph="auto" if args.graph < 0 else bool(args.graph), bucket_mb=args.bucket_mb, loss=args.loss,
                             sync_bn=bool(args.sync_bn), grad_comm=args.grad_comm, ddp_force=bool(args.ddp_force))
+    tr = step.trainer
+
+    def outputs():
+        # what a caller of NativeTrainer.step holds afterwards: the loss it returns, the logits of that
+        # forward, the gradients of that backward and the masters after the Adam update
+        return {"loss": tr.ex.loss, "logits": tr.ex.logits_nchw(), "params": tr.model.store.flat,
+                "grads": tr.model.store.grad}
+
+    step.outputs = outputs
+    return step
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32, four arrays stay under 64 MB
+
+
+def dump_outputs(step, out_dir: str, dev) -> dict:
+    """Write the arrays of ``step.outputs()`` (state after the last timed step) as float32 ``.npy`` files.
+    An array above ``DUMP_MAX_ELEMS`` elements is written as a sample at fixed positions (sorted, drawn
+    from a generator seeded by the array's size), so the same positions are compared in every run."""
+    import numpy as np
+    sync(dev)  # every stream of the step, the side-stream Adam update and weight re-layout included
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in step.outputs().items():
+        t = t.detach().to(torch.float32)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator(device="cpu").manual_seed(t.numel())
+            idx = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = np.ascontiguousarray(t.cpu().numpy())
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def quiesce_gc() -> None:
@@ -312,7 +374,12 @@ def main():
         rank_ms = [float(x.item()) for x in allt]
     imgs = args.batch * world * args.steps / dt
     extra = {}
-    extras = args.extras if args.extras >= 0 else int(world == 1 and args.impl == "native" and dev.type == "cuda")
+    if args.dump_outputs and rank == 0:
+        progress.phase = "writing outputs"
+        extra["dumped_outputs"] = dump_outputs(step, args.dump_outputs, dev)
+    # the secondary measurements run only with --full (default there: on for 1-GPU native runs)
+    full_auto = int(args.full and world == 1 and args.impl == "native" and dev.type == "cuda")
+    extras = args.extras if args.full and args.extras >= 0 else full_auto
     if extras and rank == 0:
         progress.phase = "extras (reference batch, transposed decoder, train_model)"
         for fn in (measure_ref_batch, measure_transposed, measure_train_model):
@@ -320,7 +387,7 @@ def main():
                 extra.update(fn(args, dev))
             except Exception as e:  # pragma: no cover - reported in the JSON
                 extra[fn.__name__ + "_error"] = f"{type(e).__name__}: {e}"
-    serve = args.serve if args.serve >= 0 else int(world == 1 and args.impl == "native" and dev.type == "cuda")
+    serve = args.serve if args.full and args.serve >= 0 else full_auto
     if serve and rank == 0:
         progress.phase = "serving"
         try:  # second half of the metric; never let it break the training result line
@@ -382,8 +449,8 @@ def main():
 if __name__ == "__main__":
     if main():
         # The result line is out and the serving measurement ran: skip interpreter teardown so the
-        # gRPC core's threads cannot turn a finished run into an abort at exit. (Not taken with
-        # --serve 0 -- profilers such as rocprofv3 write their output in exit handlers.)
+        # gRPC core's threads cannot turn a finished run into an abort at exit. (Taken only by --full
+        # runs that serve -- profilers such as rocprofv3 write their output in exit handlers.)
         sys.stdout.flush()
         sys.stderr.flush()
         os._exit(0)

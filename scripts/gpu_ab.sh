@@ -16,6 +16,7 @@ if [ -n "$AB" ]; then
   done; done; done
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 400 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || { tail -20 gpurun_out/bench.err; exit 1; }
-  tail -1 gpurun_out/bench.json | cut -c1-600
+  OUT=${RDP_OUT_DIR:-logs}; mkdir -p "$OUT"
+  timeout -k 10 600 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+  tail -1 "$OUT/bench.json" | cut -c1-600
 fi

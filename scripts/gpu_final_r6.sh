@@ -7,5 +7,6 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout
 rc=$?
 tail -4 gpurun_out/pytest_gpu_final.log
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 600 python bench.py > gpurun_out/bench_final.json 2> gpurun_out/bench_final.err || { tail -20 gpurun_out/bench_final.err; exit 1; }
-tail -1 gpurun_out/bench_final.json | cut -c1-400
+OUT=${RDP_OUT_DIR:-logs}; mkdir -p "$OUT"
+timeout -k 10 600 python bench.py --full > "$OUT/bench_final.json" 2> "$OUT/bench_final.err" || { tail -20 "$OUT/bench_final.err"; exit 1; }
+tail -1 "$OUT/bench_final.json" | cut -c1-400

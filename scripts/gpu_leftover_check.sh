@@ -9,6 +9,7 @@ tail -2 gpurun_out/lo_pytest.log
 [ $rc -ne 0 ] && exit $rc
 ps -eo pid,ppid,pcpu,etime,args --sort=-pcpu > gpurun_out/lo_ps.txt 2>&1 || true
 head -25 gpurun_out/lo_ps.txt
-timeout -k 10 300 python bench.py --serve 0 > gpurun_out/lo_bench.json 2> gpurun_out/lo_bench.err || exit 1
-python -c "import json; d=json.loads(open('gpurun_out/lo_bench.json').read().strip().splitlines()[-1]); print(d['value'], d['ref_batch_imgs_per_s'], d['ref_batch_ms_per_step'], d['train_model_imgs_per_s'])"
+OUT=${RDP_OUT_DIR:-logs}; mkdir -p "$OUT"
+timeout -k 10 300 python bench.py --full --serve 0 > "$OUT/lo_bench.json" 2> "$OUT/lo_bench.err" || exit 1
+python -c "import json; d=json.loads(open('$OUT/lo_bench.json').read().strip().splitlines()[-1]); print(d['value'], d['ref_batch_imgs_per_s'], d['ref_batch_ms_per_step'], d['train_model_imgs_per_s'])"
 ps -eo pid,ppid,pcpu,etime,args --sort=-pcpu | head -12

@@ -8,8 +8,9 @@ if [ -z "$SKIP_TESTS" ]; then
   rc=$?; tail -12 gpurun_out/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [ -n "$BENCH" ]; then
-  timeout -k 10 400 python bench.py ${BENCH_ARGS} > gpurun_out/bench.json 2> gpurun_out/bench.err || { tail -20 gpurun_out/bench.err; exit 1; }
-  cat gpurun_out/bench.json
+  OUT=${RDP_OUT_DIR:-logs}; mkdir -p "$OUT"
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+  cat "$OUT/bench.json"
 fi
 if [ -n "$EAGER" ]; then
   for b in 32 4; do

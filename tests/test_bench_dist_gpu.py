@@ -57,6 +57,39 @@ def test_plain_bench_gpus2_self_launches():
     assert d["config"]["impl"] == "native"
 
 
+def test_plain_native_run_is_lean_and_dumps_outputs(tmp_path):
+    """``python bench.py --gpus 1 --steps K --warmup W``: the headline step only (none of the ``--full``
+    measurements in the line), K timed steps, and with ``--dump-outputs`` the native step's loss, logits,
+    updated parameters and gradients as float32 arrays."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(RDP_NO_BUILD="1")
+    out = str(tmp_path / "dump")
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "2",
+           "--size", "64", "--dump-outputs", out]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=150)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 3 and d["config"]["impl"] == "native" and d["dtype"] == "bf16"
+    assert abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) / d["value"] < 0.02
+    assert not any(k.startswith(("ref_batch", "transposed", "train_model", "serve")) for k in d)
+    arrays = {f[:-4]: np.load(os.path.join(out, f)) for f in os.listdir(out)}
+    assert sorted(arrays) == ["grads", "logits", "loss", "params"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    assert arrays["logits"].shape == (2, 1, 64, 64) and arrays["logits"].std() > 0
+    assert arrays["params"].shape == arrays["grads"].shape and np.abs(arrays["grads"]).sum() > 0
+    assert 0 < arrays["loss"][0] < 10
+    # BCE of the dumped logits against the seeded targets of the step is the dumped loss
+    import torch
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    torch.rand(2, 3, 64, 64, generator=g)
+    y = (torch.rand(2, 1, 64, 64, generator=g) > 0.5).float()
+    bce = torch.nn.functional.binary_cross_entropy_with_logits(torch.from_numpy(arrays["logits"]), y)
+    # (fp32 sum of 8,192 terms of ~0.7: worst case 8192 x 2^-24 x 0.7 = 3.4e-4 on the mean)
+    assert abs(float(bce) - float(arrays["loss"][0])) < 5e-4
+
+
 @pytest.mark.parametrize("fail", [0, 1])
 def test_bench_ddp_force_world1_native_selfcheck(fail):
     """World 1 under nccl with the DDP path forced: the self-check runs the native ncclAllReduce probe

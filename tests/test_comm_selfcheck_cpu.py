@@ -105,6 +105,8 @@ def test_rank_count_mismatch_is_fatal(tmp_path):
 def test_bench_json_reports_selfcheck_and_rank_spread():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["RDP_NO_BUILD"] = "1"
+    # a CPU / gloo run on every machine: with a GPU visible the two ranks would want a device each
+    env.update(CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     cmd = [sys.executable, "bench.py", "--gpus", "2", "--impl", "eager", "--steps", "2", "--warmup", "1",
            "--batch", "1", "--size", "32"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)

@@ -29,6 +29,8 @@ def _run(fn, world, *args):
 
 
 def _entry(rank, world, port, fn, args):
+    # CPU / gloo workers on every machine: with one GPU visible, rank 1 would ask for a second device
+    os.environ.update(CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     torch.set_num_threads(2)

@@ -1,5 +1,6 @@
-"""Parity against the literal reference geometry module (``/root/reference/pkg/geometry_utils.py``),
-loaded by file path when present (numpy + scipy only); skipped otherwise.
+"""Parity against the literal reference geometry module (the reference's ``pkg/geometry_utils.py``):
+its recorded outputs on the synthetic scenes are the fixture ``tests/golden/reference_geometry.npz``
+(written by ``scripts/record_reference_geometry.py``, which loads that module by file path and runs it).
 
 What is pinned, on the synthetic RGB-D scenes:
   * deprojection (``_get_pcd_from_mask``): identical float64 points in identical order;
@@ -13,37 +14,34 @@ What is pinned, on the synthetic RGB-D scenes:
 The end-to-end result on scenes with y ties is therefore "parity unpinned" by construction: it
 depends on which tied pixels the reference's introselect happens to keep.
 """
-import importlib.util
 import os
 
 import numpy as np
 import pytest
 
-REF = "/root/reference/pkg/geometry_utils.py"
-pytestmark = pytest.mark.skipif(not os.path.exists(REF), reason="reference checkout not present")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_geometry.npz")
 
 
-def _ref():
-    spec = importlib.util.spec_from_file_location("rdp_reference_geometry_utils", REF)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+@pytest.fixture(scope="module")
+def ref():
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
 
 
 @pytest.mark.parametrize("seed", range(6))
-def test_reference_geometry_parity(seed):
+def test_reference_geometry_parity(seed, ref):
     from scipy.interpolate import splev, splprep
 
     from robotic_discovery_platform_amd.config import GeometryConfig
     from robotic_discovery_platform_amd.data.synthetic import DEFAULT_K, make_scene
     from robotic_discovery_platform_amd.geometry import reference as ours_ref
     from robotic_discovery_platform_amd.geometry.curvature import edges_numpy, fit_edges
-    ref = _ref()
     cfg = GeometryConfig()
     sc = make_scene(seed)
-    pcd = ref._get_pcd_from_mask(sc.mask, sc.depth, DEFAULT_K, 0.001)
+    pcd = ref[f"pcd_{seed}"]  # the reference's _get_pcd_from_mask(sc.mask, sc.depth, DEFAULT_K, 0.001)
+    assert pcd.dtype == np.float64
     assert np.array_equal(pcd, ours_ref.point_cloud(sc.mask, sc.depth, DEFAULT_K, 0.001))
-    e_ref = ref._find_point_cloud_edge(pcd)
+    e_ref = ref[f"edge_{seed}"]  # the reference's _find_point_cloud_edge(pcd)
     e_our, n = edges_numpy(sc.mask, sc.depth, DEFAULT_K, 0.001, cfg)
     assert n == pcd.shape[0] and e_ref.shape[0] == e_our.shape[0]
     # per bin: same count; points above the k-th y identical; the rest tied at the k-th y
@@ -61,7 +59,7 @@ def test_reference_geometry_parity(seed):
     # spline stage on the reference's own edge points and order
     pts = np.ascontiguousarray(e_ref[np.argsort(e_ref[:, 0])])
     tck, _ = splprep([pts[:, 0], pts[:, 1], pts[:, 2]], s=0.1, k=3)
-    rmean, rmax = ref._calculate_spline_curvature(tck)
+    rmean, rmax = ref[f"curv_{seed}"]  # the reference's _calculate_spline_curvature(tck)
     rpts = np.array(splev(np.linspace(0, 1, 100), tck)).T
     got = fit_edges(pts, cfg, n)
     assert got.status == "ok"
@@ -70,15 +68,14 @@ def test_reference_geometry_parity(seed):
     assert np.abs(gp - rpts).max() < 1e-9
 
 
-def test_reference_early_exit_parity():
+def test_reference_early_exit_parity(ref):
     from robotic_discovery_platform_amd.data.synthetic import DEFAULT_K
     from robotic_discovery_platform_amd.geometry.curvature import compute_curvature_profile
-    ref = _ref()
     depth = np.full((480, 640), 500, np.uint16)
-    for mask in (np.zeros((480, 640), np.uint8), _column_mask()):
-        r = ref.compute_curvature_profile(mask, depth, DEFAULT_K, 0.001)
+    for i, mask in enumerate((np.zeros((480, 640), np.uint8), _column_mask())):
+        # the reference's compute_curvature_profile(mask, depth, DEFAULT_K, 0.001): mean, max, points
+        assert tuple(ref["early"][i]) == (0.0, 0.0, 0)
         g = compute_curvature_profile(mask, depth, DEFAULT_K, 0.001, device="cpu")
-        assert (r.mean_curvature, r.max_curvature, len(r.spline_points)) == (0.0, 0.0, 0)
         assert (g.mean_curvature, g.max_curvature, len(g.spline_points)) == (0.0, 0.0, 0)
 
 

@@ -23,6 +23,8 @@ def _free_port():
 
 
 def _entry(rank, world, port, root, tag, resume, crash):
+    # CPU / gloo workers on every machine: with one GPU visible, rank 1 would ask for a second device
+    os.environ.update(CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
     if crash:
