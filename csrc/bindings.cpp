@@ -116,6 +116,13 @@ void rdp_jpeg_meta(const int*, int*);
 int rdp_jpeg_decode(const uint8_t*, long, int16_t*, long, uint16_t*, int);
 int rdp_jpeg_gpu(const void*, const int*, const int*, void*, int, int, int, void*, hipStream_t);
 long rdp_jpeg_plane_bytes(int, int);
+long rdp_jpeg_tables_bytes();
+long rdp_jpeg_entropy_work_words(long, int);
+long rdp_jpeg_scan_bound(const uint8_t*, long);
+int rdp_jpeg_scan(const uint8_t*, long, int*, uint8_t*, uint8_t*, long, int*);
+int rdp_jpeg_entropy_emulate(const uint8_t*, long, int, const uint8_t*, const int*, int16_t*, long, int, int*, int*);
+int rdp_jpeg_entropy_gpu(const void*, long, const int*, const void*, const int*, void*, long, int*, long, int*, int,
+                         long*, hipStream_t);
 long rdp_jpeg_max_coefs(int, int);
 int rdp_png_decode(const uint8_t*, long, uint8_t*, long, int);
 long rdp_png_encode_gray(const uint8_t*, int, int, int, int, int, uint8_t*, long);
@@ -1684,6 +1691,109 @@ void jpeg_to_rgb(torch::Tensor coefs, torch::Tensor geo, torch::Tensor qt, torch
                (int)(coefs.numel() / 64), rgb.data_ptr(), unplanned_stream());
 }
 
+// Front end of the GPU entropy decoder (csrc/jpeg.cpp rdp_jpeg_scan): a marker-less baseline JPEG ->
+// (meta int32[224] as jpeg_decode's, packed Huffman tables u8, the scan bytes with the 0xFF00 stuffing
+// removed and cut at the first marker, nbits), or None where the host decoder has to run (restart markers,
+// anything jpeg_decode declines, a scan above `capacity` bytes; 0: sized from the stream). No entropy work.
+py::object jpeg_scan(py::bytes data, bool pin, long capacity) {
+  char* buf = nullptr;
+  Py_ssize_t n = 0;
+  if (PyBytes_AsStringAndSize(data.ptr(), &buf, &n) != 0) throw py::error_already_set();
+  long cap = capacity;
+  if (cap <= 0) cap = rdp_jpeg_scan_bound((const uint8_t*)buf, n);
+  if (cap <= 0) return py::none();
+  cap = (cap + 3) / 4 * 4;
+  auto opt = torch::TensorOptions().pinned_memory(pin);
+  auto meta = torch::zeros({32 + 192}, opt.dtype(torch::kInt32));
+  auto tables = torch::empty({rdp_jpeg_tables_bytes()}, opt.dtype(torch::kUInt8));
+  auto scan = torch::empty({cap}, opt.dtype(torch::kUInt8));
+  int nbits = 0, r;
+  {
+    py::gil_scoped_release nogil;
+    r = rdp_jpeg_scan((const uint8_t*)buf, n, meta.data_ptr<int>(), tables.data_ptr<uint8_t>(),
+                      scan.data_ptr<uint8_t>(), cap, &nbits);
+  }
+  if (r != 0) return py::none();
+  const long used = std::max(4L, ((long)nbits / 8 + 3) / 4 * 4);
+  return py::make_tuple(meta, tables, scan.narrow(0, 0, std::min(used, cap)), nbits);
+}
+
+void check_entropy_args(const torch::Tensor& scan, const torch::Tensor& tables, const torch::Tensor& geo,
+                        const torch::Tensor& coefs, bool cuda) {
+  TORCH_CHECK(scan.is_cuda() == cuda && scan.scalar_type() == torch::kUInt8 && scan.is_contiguous() &&
+                  scan.numel() >= 4 && scan.numel() % 4 == 0, "scan: u8, a multiple of 4 bytes");
+  TORCH_CHECK(tables.is_cuda() == cuda && tables.scalar_type() == torch::kUInt8 && tables.is_contiguous() &&
+                  tables.numel() >= rdp_jpeg_tables_bytes(), "tables: jpeg_scan's u8 block");
+  TORCH_CHECK(geo.is_cuda() == cuda && geo.scalar_type() == torch::kInt32 && geo.is_contiguous() && geo.numel() >= 32,
+              "geo int32[32]");
+  TORCH_CHECK(coefs.is_cuda() == cuda && coefs.scalar_type() == torch::kInt16 && coefs.is_contiguous() &&
+                  coefs.numel() >= 64, "coefs int16");
+}
+
+// The entropy stage on the GPU (csrc/jpeg_entropy.hip): scan (u8, its numel is the capacity the grids are
+// sized from) of which `nbits` bits are the frame's -- an int, or an int32[1] device tensor (a captured
+// graph reads the frame's count from it) -- decoded into coefs_out (jpeg_decode's planes). work: int32
+// [jpeg_entropy_work_words(scan.numel(), subseq_bits)]; status: int32[1], 0 ok / 1 corrupt after the
+// launches (a device tensor, or host memory the device can write). Returns (subsequences, rounds) -- that waits for the stream -- or None while the stream is
+// being captured.
+py::object jpeg_entropy_gpu(torch::Tensor scan, py::object nbits, torch::Tensor tables, torch::Tensor geo,
+                            torch::Tensor coefs_out, torch::Tensor work, torch::Tensor status, int subseq_bits) {
+  check_entropy_args(scan, tables, geo, coefs_out, true);
+  TORCH_CHECK(work.is_cuda() && work.scalar_type() == torch::kInt32 && work.is_contiguous(), "work int32");
+  // status: on the device, or in host memory the device can write (the serving pipeline reads it at
+  // collect time without a copy)
+  TORCH_CHECK(status.scalar_type() == torch::kInt32 && status.numel() >= 1 && status.is_contiguous(), "status int32[1]");
+  int* status_dev = status.data_ptr<int>();
+  if (!status.is_cuda()) {
+    void* dp = nullptr;
+    TORCH_CHECK(hipHostGetDevicePointer(&dp, status.data_ptr(), 0) == hipSuccess && dp,
+                "status: a CPU tensor must live in device-mapped host memory");
+    status_dev = (int*)dp;
+  }
+  torch::Tensor nb;
+  if (THPVariable_Check(nbits.ptr())) {
+    nb = nbits.cast<torch::Tensor>();
+    TORCH_CHECK(nb.is_cuda() && nb.get_device() == scan.get_device() && nb.scalar_type() == torch::kInt32 &&
+                    nb.numel() >= 1, "nbits: int32[1] on the scan's device");
+  } else {
+    const long v = nbits.cast<long>();
+    TORCH_CHECK(v >= 0 && v <= scan.numel() * 8, "nbits beyond the scan buffer");
+    nb = torch::full({1}, v, torch::TensorOptions().dtype(torch::kInt32).device(scan.device()));
+  }
+  const hipStream_t st = unplanned_stream();
+  long stats_word = 0;
+  const int r = rdp_jpeg_entropy_gpu(scan.data_ptr(), scan.numel(), nb.data_ptr<int>(), tables.data_ptr(),
+                                     geo.data_ptr<int>(), coefs_out.data_ptr(), coefs_out.numel(), work.data_ptr<int>(),
+                                     work.numel(), status_dev, subseq_bits, &stats_word, st);
+  TORCH_CHECK(r == 0, "jpeg_entropy_gpu: bad arguments (subseq_bits a multiple of 32 >= 64, work of "
+                      "jpeg_entropy_work_words, 16-byte aligned tables / coefs) or a failed launch: ", r);
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return py::none();
+  int stats[2] = {0, 0};
+  TORCH_CHECK(hipMemcpyAsync(stats, work.data_ptr<int>() + stats_word, sizeof(stats), hipMemcpyDeviceToHost, st) ==
+                  hipSuccess && hipStreamSynchronize(st) == hipSuccess, "jpeg_entropy_gpu: statistics read-back");
+  return py::make_tuple(stats[0], stats[1]);
+}
+
+// The same stages as plain CPU loops over the shared per-lane code (csrc/jpeg.cpp
+// rdp_jpeg_entropy_emulate): CPU tensors, same arguments and results; `work` is not used.
+py::object jpeg_entropy_emulate(torch::Tensor scan, py::object nbits, torch::Tensor tables, torch::Tensor geo,
+                                torch::Tensor coefs_out, torch::Tensor work, torch::Tensor status, int subseq_bits) {
+  check_entropy_args(scan, tables, geo, coefs_out, false);
+  TORCH_CHECK(!status.is_cuda() && status.scalar_type() == torch::kInt32 && status.numel() >= 1, "status int32[1]");
+  const long v = THPVariable_Check(nbits.ptr()) ? nbits.cast<torch::Tensor>().item<long>() : nbits.cast<long>();
+  TORCH_CHECK(v >= 0 && v <= scan.numel() * 8, "nbits beyond the scan buffer");
+  int stats[2] = {0, 0}, r;
+  {
+    py::gil_scoped_release nogil;
+    r = rdp_jpeg_entropy_emulate(scan.data_ptr<uint8_t>(), scan.numel(), (int)v, tables.data_ptr<uint8_t>(),
+                                 geo.data_ptr<int>(), coefs_out.data_ptr<int16_t>(), coefs_out.numel(), subseq_bits,
+                                 status.data_ptr<int>(), stats);
+  }
+  TORCH_CHECK(r == 0, "jpeg_entropy_emulate: bad arguments (subseq_bits a multiple of 32 >= 64)");
+  return py::make_tuple(stats[0], stats[1]);
+}
+
 // u8 [H, W] CPU tensor -> 8-bit grayscale PNG bytes (deflate level), encoded without the GIL
 // u8 or int16 (u16 bits) [H, W] CPU tensor -> 8 / 16-bit grayscale PNG bytes, encoded without the GIL;
 // bands > 1: a banded stream with its rdPs index (codecs.cpp), bands deflated in parallel
@@ -1843,6 +1953,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jpeg_decode", &jpeg_decode, py::arg("data"), py::arg("parallel") = true, py::arg("pin") = false);
   m.def("jpeg_to_rgb", on_device(&jpeg_to_rgb));
   m.def("jpeg_plane_bytes", &rdp_jpeg_plane_bytes);
+  m.def("jpeg_scan", &jpeg_scan, py::arg("data"), py::arg("pin") = false, py::arg("capacity") = 0);
+  m.def("jpeg_entropy_gpu", on_device(&jpeg_entropy_gpu), py::arg("scan"), py::arg("nbits"), py::arg("tables"),
+        py::arg("geo"), py::arg("coefs_out"), py::arg("work"), py::arg("status"), py::arg("subseq_bits") = 0);
+  m.def("jpeg_entropy_emulate", &jpeg_entropy_emulate, py::arg("scan"), py::arg("nbits"), py::arg("tables"),
+        py::arg("geo"), py::arg("coefs_out"), py::arg("work"), py::arg("status"), py::arg("subseq_bits") = 0);
+  m.def("jpeg_entropy_work_words", &rdp_jpeg_entropy_work_words);
+  m.def("jpeg_tables_bytes", &rdp_jpeg_tables_bytes);
   m.def("jpeg_max_coefs", &rdp_jpeg_max_coefs);
   m.def("png_encode", &png_encode, py::arg("img"), py::arg("level") = 1, py::arg("bands") = 1);
   m.def("resize_area_u8", on_device(&resize_area_u8));

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "host_pool.h"
+#include "jpeg_sync.h"
 
 namespace {
 
@@ -436,6 +437,65 @@ int decode_segment(const Jpeg& j, const uint8_t* src, const uint8_t* end, long m
   return 0;
 }
 
+// rdp_jpeg_info's header summary of a parsed stream
+void fill_info(const Jpeg& j, int* info) {
+  const long mcus = (long)j.mcux * j.mcuy;
+  info[0] = j.width; info[1] = j.height; info[2] = j.ncomp; info[3] = j.hmax; info[4] = j.vmax;
+  info[5] = j.mcux; info[6] = j.mcuy; info[7] = j.restart;
+  info[8] = j.restart ? (int)((mcus + j.restart - 1) / j.restart) : 1;
+  for (int c = 0; c < 3; ++c) {
+    const Comp& cp = j.comp[c < j.ncomp ? c : 0];
+    info[9 + 5 * c] = cp.h; info[10 + 5 * c] = cp.v; info[11 + 5 * c] = cp.bw; info[12 + 5 * c] = cp.bh;
+    info[13 + 5 * c] = cp.tq;
+  }
+}
+
+// The GPU entropy decoder's table block (jpeg_sync.h) of a parsed stream; false when the scan uses more
+// than two DC or two AC tables (the host decoder takes those)
+bool fill_tables(const Jpeg& j, jsync::Tables& T) {
+  std::memset(&T, 0, sizeof(T));
+  int dcs[2] = {-1, -1}, acs[2] = {-1, -1};
+  auto slot = [](int* used, int id) {
+    for (int i = 0; i < 2; ++i) {
+      if (used[i] == id) return i;
+      if (used[i] < 0) { used[i] = id; return i; }
+    }
+    return -1;
+  };
+  int nb = 0;
+  for (int c = 0; c < j.ncomp; ++c) {
+    const Comp& cp = j.comp[c];
+    const int sd = slot(dcs, cp.td), sa = slot(acs, cp.ta);
+    if (sd < 0 || sa < 0) return false;
+    for (int by = 0; by < cp.v; ++by)
+      for (int bx = 0; bx < cp.h; ++bx) {
+        if (nb >= 12) return false;
+        T.sel[nb] = (uint8_t)(sd | (sa << 4));
+        T.comp[nb] = (uint8_t)c;
+        T.by[nb] = (uint8_t)by;
+        T.bx[nb] = (uint8_t)bx;
+        ++nb;
+      }
+  }
+  T.nb = nb;
+  for (int i = 0; i < 64; ++i) T.zz[i] = (uint8_t)kZigzag[i];
+  for (int i = 0; i < 4; ++i) {
+    const int id = i < 2 ? dcs[i] : acs[i - 2];
+    if (id < 0) continue;
+    const Huff& h = i < 2 ? j.dc[id] : j.ac[id];
+    jsync::HuffTab& t = T.t[i];
+    std::memcpy(t.look, h.look, sizeof(t.look));
+    std::memcpy(t.vals, h.vals, sizeof(t.vals));
+    for (int l = 0; l < 17; ++l) {
+      const bool has = l >= 1 && h.bits[l];
+      t.maxcode[l] = has ? h.maxcode[l] : -1;
+      t.mincode[l] = has ? h.mincode[l] : 0;
+      t.valptr[l] = has ? h.valptr[l] : 0;
+    }
+  }
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -447,15 +507,7 @@ long rdp_jpeg_info(const uint8_t* d, long n, int* info) {
   Jpeg j;
   const int r = parse(d, n, j);
   if (r) return r;
-  const long mcus = (long)j.mcux * j.mcuy;
-  info[0] = j.width; info[1] = j.height; info[2] = j.ncomp; info[3] = j.hmax; info[4] = j.vmax;
-  info[5] = j.mcux; info[6] = j.mcuy; info[7] = j.restart;
-  info[8] = j.restart ? (int)((mcus + j.restart - 1) / j.restart) : 1;
-  for (int c = 0; c < 3; ++c) {
-    const Comp& cp = j.comp[c < j.ncomp ? c : 0];
-    info[9 + 5 * c] = cp.h; info[10 + 5 * c] = cp.v; info[11 + 5 * c] = cp.bw; info[12 + 5 * c] = cp.bh;
-    info[13 + 5 * c] = cp.tq;
-  }
+  fill_info(j, info);
   return j.total_coefs;
 }
 
@@ -520,6 +572,146 @@ int rdp_jpeg_decode(const uint8_t* d, long n, int16_t* coefs, long ncoefs, uint1
     for (int s = 0; s < nseg; ++s) seg(s);
   }
   return bad.load() ? -1 : 0;
+}
+
+// ---- GPU entropy decode of marker-less scans: host front end + CPU emulation (jpeg_sync.h has the algorithm)
+
+long rdp_jpeg_tables_bytes() { return (long)sizeof(jsync::Tables); }
+
+long rdp_jpeg_entropy_work_words(long cap_bytes, int S) {
+  if (S == 0) S = jsync::kDefaultBits;
+  if (S < 64 || S % 32 || cap_bytes < 0) return -1;
+  return jsync::work_layout(cap_bytes, S).words;
+}
+
+// Upper bound of rdp_jpeg_scan's output for this stream (its entropy-coded bytes, rounded up to whole
+// 32-bit words), or parse()'s error.
+long rdp_jpeg_scan_bound(const uint8_t* d, long n) {
+  Jpeg j;
+  const int r = parse(d, n, j);
+  if (r) return r;
+  return ((j.scan_end - j.scan_begin) + 3) / 4 * 4 + 4;
+}
+
+// Front end of the GPU entropy decoder: what rdp_jpeg_decode accepts, without restart markers. meta
+// (int32[224]: rdp_jpeg_meta's geometry, then the three quantisation tables), the packed Huffman tables
+// (rdp_jpeg_tables_bytes()), and the scan bytes with the 0xFF00 stuffing removed, cut at the first marker,
+// into scan[cap] (cap a multiple of 4); *nbits = 8 x the bytes written. No entropy work. 0 ok, -1 corrupt,
+// -2 unsupported here (restart markers, more than two tables of a class, a scan above `cap`): the
+// host decoder runs.
+int rdp_jpeg_scan(const uint8_t* d, long n, int* meta, uint8_t* tables, uint8_t* scan, long cap, int* nbits) {
+  Jpeg j;
+  const int r = parse(d, n, j);
+  if (r) return r;
+  if (j.restart != 0 || cap < 0 || cap % 4 || cap >= (1L << 28)) return -2;
+  jsync::Tables T;
+  if (!fill_tables(j, T)) return -2;
+  std::memcpy(tables, &T, sizeof(T));
+  int hi[24];
+  fill_info(j, hi);
+  rdp_jpeg_meta(hi, meta);
+  for (int c = 0; c < 3; ++c) {
+    const uint16_t* q = j.qt[j.comp[c < j.ncomp ? c : 0].tq];
+    for (int i = 0; i < 64; ++i) meta[32 + 64 * c + i] = q[i];
+  }
+  // 0xFF to 0xFF (memchr), as the RST search of rdp_jpeg_decode: the bytes between go out in one copy
+  const uint8_t* p = d + j.scan_begin;
+  const uint8_t* end = d + j.scan_end;
+  long o = 0;
+  while (p < end) {
+    const uint8_t* f = (const uint8_t*)std::memchr(p, 0xFF, (size_t)(end - p));
+    const long run = (f ? f : end) - p;
+    const bool stuffed = f && f + 1 < end && f[1] == 0x00;
+    if (o + run + (stuffed ? 1 : 0) > cap) return -2;
+    std::memcpy(scan + o, p, (size_t)run);
+    o += run;
+    if (!stuffed) break;  // the end, or a marker: the decoder reads zeros from here on
+    scan[o++] = 0xFF;
+    p = f + 2;
+  }
+  *nbits = (int)(o * 8);
+  return 0;
+}
+
+// The GPU decoder's stages (jpeg_entropy.hip) as plain loops over the same per-lane code, workgroup by
+// workgroup and round by round, so results and statistics equal the kernels'. scan[cap_bytes] (a multiple
+// of 4, 4-byte aligned), S bits per subsequence (0: the default). *status: 0 ok, 1 corrupt (whenever
+// rdp_jpeg_decode returns -1); stats (optional): subsequences, rounds. Returns -1 on bad arguments.
+int rdp_jpeg_entropy_emulate(const uint8_t* scan, long cap_bytes, int nbits, const uint8_t* tables, const int* geo,
+                             int16_t* coefs, long cap_coefs, int S, int* status, int* stats) {
+  using namespace jsync;
+  if (S == 0) S = kDefaultBits;
+  if (S < 64 || S % 32 || cap_bytes < 0 || cap_bytes % 4 || cap_bytes >= (1L << 28) || nbits < 0 ||
+      (long)nbits > cap_bytes * 8 || ((uintptr_t)scan & 3) || cap_coefs < 0)
+    return -1;
+  Tables T;
+  std::memcpy(&T, tables, sizeof(T));
+  if (T.nb < 1 || T.nb > 12) return -1;
+  const uint32_t* w = (const uint32_t*)scan;
+  const uint32_t nb = (uint32_t)nbits, uS = (uint32_t)S;
+  const long n = sub_count(nb, uS);
+  std::vector<St> In(n), E(n), prev(kLanes);
+  std::vector<int> cnt(n);
+  // one workgroup's Jacobi iteration; stitch: lane 0 restarts from the previous workgroup's end state
+  auto sync_group = [&](long g, bool stitch) {
+    const long t0 = g * kLanes, nl = std::min<long>(kLanes, n - t0);
+    if (!stitch)
+      for (long i = 0; i < nl; ++i) {
+        const long t = t0 + i;
+        In[t] = St{(uint32_t)t * uS, 0};
+        E[t] = In[t];
+        cnt[t] = run_spec(T, w, nb, E[t], sub_end((uint32_t)t, (uint32_t)n, uS, nb));
+      }
+    int rounds = 0;
+    const long bound = stitch ? nl : nl - 1;
+    for (long r = 1; r <= bound; ++r) {
+      for (long i = 0; i < nl; ++i) prev[i] = i > 0 ? E[t0 + i - 1] : stitch ? E[t0 - 1] : In[t0];
+      bool any = false;
+      for (long i = 0; i < nl; ++i) {
+        const long t = t0 + i;
+        if (same(prev[i], In[t])) continue;
+        In[t] = prev[i];
+        St o = In[t];
+        cnt[t] = run_spec(T, w, nb, o, sub_end((uint32_t)t, (uint32_t)n, uS, nb));
+        any |= !same(o, E[t]);
+        E[t] = o;
+      }
+      ++rounds;  // rounds run, the one that finds nothing changed included
+      if (!any) break;
+    }
+    return rounds;
+  };
+  const long nwg = (n + kLanes - 1) / kLanes;
+  int rounds = 0;
+  for (long g = 0; g < nwg; ++g) rounds = std::max(rounds, sync_group(g, false));
+  for (long g = 1; g < nwg; ++g) rounds += sync_group(g, true);
+  const Geo G = make_geo(geo, T.nb, cap_coefs / 64);
+  const long live = std::max(0L, std::min(G.total, G.cap));
+  std::memset(coefs, 0, (size_t)live * 64 * sizeof(int16_t));
+  int bad = 0;
+  long ord = 0;
+  for (long t = 0; t < n; ++t) {
+    bad |= run_write(T, G, w, nb, In[t], sub_end((uint32_t)t, (uint32_t)n, uS, nb), t == n - 1, ord, coefs);
+    ord += cnt[t];
+  }
+  const int nc = std::min(std::max(geo[2], 0), 3);
+  for (int c = 0; c < nc; ++c) {
+    if (G.h[c] < 1 || G.v[c] < 1) continue;
+    const long nblk = (long)G.bw[c] * geo[11 + 8 * c];
+    uint32_t pred = 0;
+    for (long jx = 0; jx < nblk; ++jx) {
+      const long blk = dc_block_index(G, c, jx);
+      if (blk < 0 || blk >= live) continue;
+      pred += (uint32_t)(int32_t)coefs[blk * 64];
+      coefs[blk * 64] = (int16_t)pred;
+    }
+  }
+  *status = bad;
+  if (stats) {
+    stats[0] = (int)n;
+    stats[1] = rounds;
+  }
+  return 0;
 }
 
 }  // extern "C"

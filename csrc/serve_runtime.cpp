@@ -41,6 +41,8 @@ extern "C" long rdp_png_encode_bound(int, int, int, int);
 extern "C" long rdp_jpeg_info(const uint8_t*, long, int*);
 extern "C" void rdp_jpeg_meta(const int*, int*);
 extern "C" int rdp_jpeg_decode(const uint8_t*, long, int16_t*, long, uint16_t*, int);
+extern "C" int rdp_jpeg_scan(const uint8_t*, long, int*, uint8_t*, uint8_t*, long, int*);
+extern "C" long rdp_jpeg_tables_bytes();
 extern "C" int rdp_png_info(const uint8_t*, long, int*, int*, int*);
 extern "C" int rdp_png_decode(const uint8_t*, long, uint8_t*, long, int);
 
@@ -88,9 +90,10 @@ class FrameRunner {
     for (void* p : host_) (void)hipHostFree(p);
   }
   // graph execs, owned by the pipeline's torch CUDAGraphs (kept alive there): slots 0..2 = the network
-  // graph of colour source 0 BGR / 1 RGB / 2 JPEG coefficients, slot 3 = the geometry graph
+  // graph of colour source 0 BGR / 1 RGB / 2 JPEG coefficients, slot 3 = the geometry graph, slot 4 = the
+  // network graph of a marker-less JPEG scan (entropy decode on the GPU first)
   void set_graph(int slot, uintptr_t exec) {
-    if (slot < 0 || slot > 3) throw std::invalid_argument("slot");
+    if (slot < 0 || slot > 4) throw std::invalid_argument("slot");
     exec_[slot] = (hipGraphExec_t)exec;
   }
   // Measured (same box, 2 rounds): the copy stream vs the depth H2D in order on the frame stream --
@@ -136,6 +139,7 @@ class FrameRunner {
     hip_check(hipEventRecord(ev0_, s_), "hipEventRecord");
     upload(d_color_, h_color_, color_bytes_, "H2D colour");
     hip_check(hipGraphLaunch(exec_[src], s_), "hipGraphLaunch");
+    scan_inflight_ = false;
   }
 
   // colour half, from an entropy-decoded JPEG (data/jpeg.py JpegCoefs: pinned meta + coefficient
@@ -149,7 +153,44 @@ class FrameRunner {
     upload(d_meta_, P(meta), meta_bytes, "H2D meta", false);
     upload(d_coef_, P(coefs), coef_bytes, "H2D coefs", false);
     hip_check(hipGraphLaunch(exec_[2], s_), "hipGraphLaunch");
+    scan_inflight_ = false;
   }
+
+  // The scan source's device block: [meta int32[224] | nbits int32 | pad to kScanTables | Huffman tables |
+  // pad to scan_off | scan bytes (scan_cap)], uploaded as ONE copy of its used prefix from a pinned
+  // staging block of the same layout; `status`: the entropy stage's status word, in host memory the
+  // kernels write (alloc_host). gpu_entropy: submit_encoded sends marker-less JPEGs this way.
+  enum { kScanNbits = 224 * 4, kScanTables = 912 };
+  void set_scan_buffers(uintptr_t d_blk, size_t scan_off, size_t scan_cap, uintptr_t status, bool gpu_entropy) {
+    DeviceScope g(dev_);
+    if (scan_off < kScanTables + (size_t)rdp_jpeg_tables_bytes() || scan_off % 16 || scan_cap % 4)
+      throw std::invalid_argument("scan block layout");
+    d_blk_ = P(d_blk); scan_off_ = scan_off; scan_cap_ = scan_cap; h_status_ = (volatile int*)P(status);
+    if (!h_blk_) {
+      hip_check(hipHostMalloc(&h_blk_, scan_off + scan_cap, hipHostMallocDefault), "hipHostMalloc");
+      std::memset(h_blk_, 0, scan_off + scan_cap);
+      host_.push_back(h_blk_);
+    }
+    gpu_entropy_ = gpu_entropy;
+  }
+  void set_gpu_entropy(bool on) { gpu_entropy_ = on && h_blk_; }
+
+  // colour half, from a de-stuffed marker-less scan (data/jpeg.py JpegScan; copied into the staging block)
+  void submit_scan(uintptr_t meta, uintptr_t tables, uintptr_t scan, size_t scan_bytes, long nbits) {
+    if (!h_blk_ || scan_bytes > scan_cap_ || nbits < 0 || (size_t)nbits > scan_bytes * 8)
+      throw std::invalid_argument("JPEG scan exceeds the pipeline");
+    need(4);
+    py::gil_scoped_release nogil;
+    DeviceScope g(dev_);
+    uint8_t* b = (uint8_t*)h_blk_;
+    std::memcpy(b, P(meta), 224 * 4);
+    std::memcpy(b + kScanTables, P(tables), (size_t)rdp_jpeg_tables_bytes());
+    std::memcpy(b + scan_off_, P(scan), scan_bytes);
+    hip_check(hipEventRecord(ev0_, s_), "hipEventRecord");
+    launch_scan((int)nbits);
+  }
+  // the entropy stage's verdict on the frame just waited for (0 ok; valid after wait() / collect_encoded())
+  int scan_status() const { return scan_inflight_ && h_status_ ? *h_status_ : 0; }
 
   // depth half (HxW 16-bit): H2D, the geometry graph, the result read-back and the frame's end event
   void submit_depth(py::buffer depth) {
@@ -190,6 +231,14 @@ class FrameRunner {
       (void)hipGetLastError();
     }
     hip_check(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st), what);
+  }
+
+  void launch_scan(int nbits) {  // the staging block is filled; ev0_ recorded; the device is current
+    *(int*)((uint8_t*)h_blk_ + kScanNbits) = nbits;
+    const size_t used = scan_off_ + (((size_t)nbits / 8 + 15) & ~(size_t)15);
+    upload(d_blk_, h_blk_, std::min(used, scan_off_ + scan_cap_), "H2D scan");
+    hip_check(hipGraphLaunch(exec_[4], s_), "hipGraphLaunch");
+    scan_inflight_ = true;
   }
 
   void launch_depth_half() {  // h_depth_ staged; the device is current
@@ -290,7 +339,22 @@ class FrameRunner {
 
   void work_half(int k, const uint8_t* c, long cn, const uint8_t* d, long dn, const int* hi, long nco, int* rc) {
     {
+      if (k == 0 && gpu_entropy_ && exec_[4] && hi[7] == 0) {
+        // colour, marker-less scan: headers + de-stuffing only; the entropy decode runs in the network
+        // graph (a scan the front end declines -- over capacity, three tables of a class -- goes on below)
+        uint8_t* b = (uint8_t*)h_blk_;
+        int nbits = 0;
+        const int r = rdp_jpeg_scan(c, cn, (int*)b, b + kScanTables, b + scan_off_, (long)scan_cap_, &nbits);
+        if (r == -1) { rc[0] = kCorrupt; return; }
+        if (r == 0) {
+          DeviceScope gk(dev_);
+          hip_check(hipEventRecord(ev0_, s_), "hipEventRecord");
+          launch_scan(nbits);
+          return;
+        }
+      }
       if (k == 0) {  // colour: entropy decode, then the network half on the frame stream
+        scan_inflight_ = false;
         int* meta = (int*)h_meta_;
         rdp_jpeg_meta(hi, meta);
         uint16_t qt[3 * 64];
@@ -308,7 +372,8 @@ class FrameRunner {
   }
 
   // (payload bytes, mean, max, coverage %, status code, gpu ms); status code 4 = the fit needs the host
-  // (the caller finishes that frame from the device edge buffers)
+  // (the caller finishes that frame from the device edge buffers), 5 = the GPU entropy stage found the
+  // JPEG scan corrupt (the caller handles the frame as a submit code 3)
   py::tuple collect_encoded(int level, int bands) {
     float gpu_ms = 0.f;
     double mean = 0, maxc = 0, cov = 0;
@@ -321,9 +386,10 @@ class FrameRunner {
       hip_check(hipEventElapsedTime(&gpu_ms, ev0_, ev1_), "hipEventElapsedTime");
       const double* r = (const double*)h_res_;
       st = (int)r[0];
+      if (scan_status() != 0) st = 5;  // corrupt scan, found by the entropy stage: the caller decodes the frame
       const double count = r[8 + 3 * ns_];
       cov = 100.0 * count / ((double)H_ * W_);
-      if (st != 4) {
+      if (st != 4 && st != 5) {
         static const char* names[4] = {"ok", "too_few_points", "too_few_edge_points", "fit_failed"};
         const std::string status = (st >= 0 && st < 4) ? names[st] : "fit_failed";
         if (st == 0) { mean = r[4]; maxc = r[5]; }
@@ -396,13 +462,17 @@ class FrameRunner {
   bool depth_stream_ = true;
   int H_ = 0, W_ = 0, ns_ = 0;
   void *h_meta_ = nullptr, *h_coef_ = nullptr;
+  void *d_blk_ = nullptr, *h_blk_ = nullptr;  // the scan source's device block and its pinned staging
+  size_t scan_off_ = 0, scan_cap_ = 0;
+  volatile int* h_status_ = nullptr;
+  bool gpu_entropy_ = false, scan_inflight_ = false;
   std::chrono::steady_clock::time_point t0_;
   int dev_;
   hipStream_t s_;
   hipEvent_t ev0_ = nullptr, ev1_ = nullptr, evd_ = nullptr;
   hipStream_t cs_ = nullptr;
   std::vector<void*> host_;
-  hipGraphExec_t exec_[4] = {nullptr, nullptr, nullptr, nullptr};
+  hipGraphExec_t exec_[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   void *d_color_ = nullptr, *h_color_ = nullptr, *d_depth_ = nullptr, *h_depth_ = nullptr;
   bool kernel_copy_ = true;  // uploads by copy kernel (upload())
   std::vector<std::pair<const void*, void*>> hmap_;  // host staging pointer -> device mapping
@@ -830,6 +900,11 @@ void register_serve_runtime(py::module_& m) {
       .def("submit_array", &FrameRunner::submit_array)
       .def("submit_jpeg", &FrameRunner::submit_jpeg)
       .def("submit_depth", &FrameRunner::submit_depth)
+      .def("set_scan_buffers", &FrameRunner::set_scan_buffers, py::arg("d_blk"), py::arg("scan_off"), py::arg("scan_cap"),
+           py::arg("status"), py::arg("gpu_entropy"))
+      .def("set_gpu_entropy", &FrameRunner::set_gpu_entropy)
+      .def("submit_scan", &FrameRunner::submit_scan)
+      .def("scan_status", &FrameRunner::scan_status)
       .def("configure_encoded", &FrameRunner::configure_encoded, py::arg("H"), py::arg("W"), py::arg("num_samples"))
       .def("submit_encoded", &FrameRunner::submit_encoded, py::arg("color"), py::arg("depth"),
            "0 launched, 1 not a native frame, 2 other frame size, 3 corrupt (nothing in flight)")

@@ -90,6 +90,10 @@ class ServeConfig:
     replicas_per_device: int = 2  # independent stream pipelines (hipGraph + buffers) per GPU
     frame_errors: str = "degrade"  # "degrade": bad frame -> error status, stream goes on; "abort": reference
     gpu_jpeg: bool = True  # baseline JPEGs: native entropy decode on the host, pixel stage in the frame graph
+    # marker-less baseline JPEGs (a stock cv2.imencode client): entropy decode on the host (one serial loop),
+    # on the GPU in the frame graph (csrc/jpeg_entropy.hip), or auto = the GPU for marker-less scans only.
+    # RDP_SERVE_JPEG_ENTROPY overrides. The default follows profiles/jpeg_gpu_entropy.md.
+    jpeg_entropy: str = "host"
     workers: int = 1  # server processes sharing the port (SO_REUSEPORT): one interpreter lock each
     hot_reload_alias: Optional[str] = None  # e.g. "staging": reload when alias moves
 

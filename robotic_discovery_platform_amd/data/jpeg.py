@@ -11,6 +11,12 @@ integer IDCT, "fancy" chroma upsampling and fixed-point YCbCr -> RGB, all on one
 * ``csrc/serve_kernels.hip`` (``jpeg_to_rgb``, inside the per-frame graph): dequantisation + IDCT +
   upsampling + colour conversion on the GPU, straight into the frame buffer the preprocess reads.
 
+A stock client's JPEG (``cv2.imencode``: one scan, no restart markers) has nothing for that thread pool
+to split, so its entropy decode can run on the GPU instead: ``scan_jpeg`` (``csrc/jpeg.cpp``
+``rdp_jpeg_scan``) only parses the headers and strips the byte stuffing, and ``entropy_decode``
+(``csrc/jpeg_entropy.hip``, a self-synchronising parallel Huffman decode) writes the same coefficient
+planes, bit for bit. Without a GPU ``entropy_decode`` runs the same stages as CPU loops.
+
 ``coefs_to_rgb_reference`` is the same pixel math in NumPy (the CPU oracle of the GPU kernels; tests
 check it against PIL's libjpeg decode). Unsupported streams (progressive, arithmetic, 12-bit ...) make
 ``decode_coefs`` return None and the caller decodes with PIL.
@@ -71,6 +77,84 @@ def decode_coefs(data: bytes, parallel: bool = True, pin: bool = False) -> Optio
     if r is None:
         return None
     return JpegCoefs(*r)
+
+
+@dataclass
+class JpegScan:
+    """One marker-less baseline scan ready for the GPU entropy decoder: ``meta`` as ``JpegCoefs.meta``,
+    the packed Huffman ``tables`` (u8), the ``scan`` bytes with the 0xFF00 stuffing removed (u8, a
+    multiple of 4 bytes) and the number of scan bits. A stand-in for the HxWx3 array it decodes to."""
+    meta: "object"    # torch int32 [224]
+    tables: "object"  # torch uint8 [jpeg_tables_bytes()]
+    scan: "object"    # torch uint8 [>= nbits / 8]
+    nbits: int
+    ndim = 3
+
+    @property
+    def geo(self):
+        return self.meta[:32]
+
+    @property
+    def width(self) -> int:
+        return int(self.meta[0])
+
+    @property
+    def height(self) -> int:
+        return int(self.meta[1])
+
+    @property
+    def blocks(self) -> int:
+        return int(self.meta[5])
+
+    @property
+    def shape(self):
+        return (self.height, self.width, 3)
+
+
+def _native():
+    from ..ops import native
+    C = native(build_if_missing=False)
+    if C is None:
+        raise RuntimeError("native extension not built")
+    return C
+
+
+def scan_jpeg(data: bytes, pin: bool = False, capacity: int = 0) -> Optional[JpegScan]:
+    """Header parse + de-stuffing of a baseline JPEG without restart markers; no entropy work. None: the
+    host decoder (or PIL) has to take the stream -- restart markers, anything ``decode_coefs`` declines,
+    or a scan of more than ``capacity`` bytes (0: no limit)."""
+    r = _native().jpeg_scan(bytes(data), pin, int(capacity))
+    if r is None:
+        return None
+    return JpegScan(*r)
+
+
+def entropy_decode(js: JpegScan, device=None, subseq_bits: int = 0, stats: Optional[list] = None) -> Optional[JpegCoefs]:
+    """Entropy-decode a ``JpegScan`` into the planes ``decode_coefs`` gives: on ``device`` when it is a
+    GPU (the result stays there), otherwise through the CPU emulation of the same stages. None: the scan
+    is corrupt (exactly where ``decode_coefs`` returns None). ``stats``: receives (subsequences, rounds)."""
+    import torch
+    C = _native()
+    dev = torch.device(device) if device is not None else torch.device("cpu")
+    n = js.blocks * 64
+    if dev.type == "cuda":
+        scan, tables, meta = js.scan.to(dev), js.tables.to(dev), js.meta.to(dev)
+        coefs = torch.empty(n, dtype=torch.int16, device=dev)
+        work = torch.empty(C.jpeg_entropy_work_words(scan.numel(), subseq_bits), dtype=torch.int32, device=dev)
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            st = C.jpeg_entropy_gpu(scan, int(js.nbits), tables, meta[:32], coefs, work, status, subseq_bits)
+    else:
+        meta = js.meta.clone()
+        coefs = torch.empty(n, dtype=torch.int16)
+        status = torch.zeros(1, dtype=torch.int32)
+        st = C.jpeg_entropy_emulate(js.scan, int(js.nbits), js.tables, meta[:32].contiguous(), coefs,
+                                    torch.empty(0, dtype=torch.int32), status, subseq_bits)
+    if stats is not None:
+        stats[:] = list(st)
+    if int(status.item()) != 0:
+        return None
+    return JpegCoefs(meta, coefs)
 
 
 # ---------------------------------------------------------------------------------------- oracle

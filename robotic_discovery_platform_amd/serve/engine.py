@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from ..config import GeometryConfig
-from ..data.jpeg import JpegCoefs, coefs_to_rgb_reference
+from ..data.jpeg import JpegCoefs, JpegScan, coefs_to_rgb_reference, entropy_decode
 from ..geometry.curvature import CurvatureResult, GeometryEngine, compute_curvature_profile
 from ..utils import trace
 
@@ -93,6 +93,24 @@ class WireResult:
 
 SRC_BGR, SRC_RGB, SRC_JPEG = 0, 1, 2  # colour sources of a network graph
 GEO, GEO_SLOT = "geo", 3  # the geometry graph (FrameRunner slot 3)
+SRC_SCAN = 4  # a marker-less JPEG scan, entropy-decoded in the network graph (FrameRunner slot 4)
+
+
+class CorruptScan(ValueError):
+    """The GPU entropy decoder found the frame's JPEG scan corrupt (known when the frame is collected)."""
+
+
+def jpeg_entropy_policy(value: Optional[str] = None) -> str:
+    """Where marker-less baseline JPEGs are entropy-decoded on the encoded-request path: ``host``
+    (csrc/jpeg.cpp, one serial loop), ``gpu`` (csrc/jpeg_entropy.hip, in the frame graph) or ``auto`` (the GPU
+    for marker-less scans only -- streams with restart markers always decode on the host pool, so today the
+    same as ``gpu``). None: RDP_SERVE_JPEG_ENTROPY, else ServeConfig's default."""
+    if value is None:
+        from ..config import ServeConfig
+        value = os.environ.get("RDP_SERVE_JPEG_ENTROPY") or ServeConfig.jpeg_entropy
+    if value not in ("host", "gpu", "auto"):
+        raise ValueError(f"jpeg_entropy must be host, gpu or auto (got {value!r})")
+    return value
 
 
 def _host_tensor(runner, shape, dtype) -> torch.Tensor:
@@ -127,7 +145,8 @@ class FramePipeline:
 
     def __init__(self, model, K: np.ndarray, depth_scale: float, H: int = 480, W: int = 640, size: int = 256,
                  threshold: float = 0.5, graph: bool = True, geo_cfg: Optional[GeometryConfig] = None,
-                 device: Optional[torch.device] = None, rgb: bool = False, jpeg: bool = False):
+                 device: Optional[torch.device] = None, rgb: bool = False, jpeg: bool = False,
+                 jpeg_entropy: Optional[str] = None):
         from ..models.unet import UNetNative
         if not isinstance(model, UNetNative):
             raise TypeError("FramePipeline needs the native UNet (UNetNative); use CpuFramePipeline otherwise")
@@ -137,9 +156,10 @@ class FramePipeline:
         # everything below (buffers, stream, graph capture) belongs to the model's GPU, whatever device
         # the calling thread has current
         with torch.cuda.device(dev):
-            self._init(model, K, depth_scale, H, W, size, threshold, graph, geo_cfg, dev, rgb, jpeg)
+            self._init(model, K, depth_scale, H, W, size, threshold, graph, geo_cfg, dev, rgb, jpeg,
+                       jpeg_entropy_policy(jpeg_entropy))
 
-    def _init(self, model, K, depth_scale, H, W, size, threshold, graph, geo_cfg, dev, rgb, jpeg):
+    def _init(self, model, K, depth_scale, H, W, size, threshold, graph, geo_cfg, dev, rgb, jpeg, entropy="host"):
         from ..models.unet import UNetExecutor
         from ..ops import native
         self.C = native()
@@ -173,12 +193,31 @@ class FramePipeline:
         self.d_coef = torch.empty(self.C.jpeg_max_coefs(H, W), dtype=torch.int16, device=dev)
         self.d_meta = torch.zeros(32 + 192, dtype=torch.int32, device=dev)
         self.d_planes = torch.empty(self.C.jpeg_plane_bytes(H, W), dtype=torch.uint8, device=dev)
+        # scan source (marker-less baseline JPEGs, what a stock cv2.imencode client sends): the entropy decode
+        # runs on the GPU too (csrc/jpeg_entropy.hip), first in the network graph. One device block holds
+        # everything a frame uploads -- meta, the scan's bit count, the Huffman tables, the de-stuffed scan
+        # -- so a frame is one copy of the block's used prefix. The scan capacity (the launch grids are
+        # sized from it) is the frame's raw 4:2:0 size: a JPEG larger than that takes the host decoder.
+        self.jpeg_entropy = entropy
+        # bits per subsequence of the entropy stage; 0: the tuned default (RDP_SERVE_JPEG_SUBSEQ_BITS: the
+        # tuning sweep of scripts/refclient_bench.py)
+        self.subseq_bits = int(os.environ.get("RDP_SERVE_JPEG_SUBSEQ_BITS", "0"))
+        self.scan_off = 912 + ((self.C.jpeg_tables_bytes() + 15) // 16) * 16
+        self.scan_cap = ((H * W * 3 // 2 + 1023) // 1024) * 1024
+        self.d_scanblk = torch.zeros(self.scan_off + self.scan_cap, dtype=torch.uint8, device=dev)
+        self.d_smeta = self.d_scanblk[:896].view(torch.int32)
+        self.d_nbits = self.d_scanblk[896:900].view(torch.int32)
+        self.d_tables = self.d_scanblk[912:912 + self.C.jpeg_tables_bytes()]
+        self.d_scan = self.d_scanblk[self.scan_off:]
+        self.d_ework = torch.zeros(self.C.jpeg_entropy_work_words(self.scan_cap, self.subseq_bits), dtype=torch.int32, device=dev)
+        self.scan_status = torch.zeros(1, dtype=torch.int32, device=dev)  # (runner: host memory the kernels write)
         self.ev0 = torch.cuda.Event(enable_timing=True)
         self.ev1 = torch.cuda.Event(enable_timing=True)
         self.graphs = {}  # colour source (SRC_BGR / SRC_RGB arrays, SRC_JPEG coefficients) -> hipGraph
         self.use_graph = graph
         self.lock = threading.Lock()
         self._hold = None  # the submitted frame's JPEG buffers, alive until its copies are done
+        self._scan_frame = False  # the frame in flight came as a JpegScan (collect checks its status word)
         self._pending_src = None  # colour half submitted, depth half not yet
         # native per-frame host path (csrc/serve_runtime.cpp): staging copies, H2D, graph launch, D2H and
         # events in one call without the GIL; the Python path below stays for eager pipelines
@@ -200,6 +239,11 @@ class FramePipeline:
                           self.d_meta.data_ptr(), nb(self.d_meta), self.d_coef.data_ptr(), nb(self.d_coef),
                           self.mask.data_ptr(), self.h_mask.data_ptr(), 0,
                           self.geo.res.data_ptr(), self.h_res.data_ptr(), 0)
+            # the entropy stage's status word: as the result vector, host memory the kernels write and
+            # the host reads at collect time -- no copy, no extra sync
+            self.scan_status = _host_tensor(r, (1,), np.int32)
+            r.set_scan_buffers(self.d_scanblk.data_ptr(), self.scan_off, self.scan_cap, self.scan_status.data_ptr(),
+                               entropy != "host")
             self.runner = r
         # the graphs for the sources this pipeline will be fed (the gRPC server: JPEG coefficients, or
         # RGB arrays for streams the native decoder does not take) are captured here, at build time --
@@ -209,6 +253,7 @@ class FramePipeline:
             self._capture(SRC_RGB if rgb else SRC_BGR)
             if jpeg:
                 self._capture(SRC_JPEG)
+                self._capture(SRC_SCAN)
         else:
             self.refresh_weights()
         # whole encoded requests natively (FrameRunner.submit_encoded): JPEG pipelines with a runner
@@ -230,6 +275,10 @@ class FramePipeline:
         C, ex, m = self.C, self.ex, self.model
         if src == SRC_JPEG:
             C.jpeg_to_rgb(self.d_coef, self.d_meta[:32], self.d_meta[32:], self.d_planes, self.d_color)
+        elif src == SRC_SCAN:
+            C.jpeg_entropy_gpu(self.d_scan, self.d_nbits, self.d_tables, self.d_smeta[:32], self.d_coef, self.d_ework,
+                               self.scan_status, self.subseq_bits)
+            C.jpeg_to_rgb(self.d_coef, self.d_smeta[:32], self.d_smeta[32:], self.d_planes, self.d_color)
         C.preprocess(self.d_color, *self.tab, ex.x_in, int(src != SRC_BGR))
         # BN-fold coefficients: see refresh_weights(); the head (+ threshold) is fused into the last conv
         ex.forward(head=False, refresh_eval=False,
@@ -298,11 +347,16 @@ class FramePipeline:
         """First half of ``submit``: stage the colour frame and enqueue the network graph."""
         if color.shape != (self.H, self.W, 3):
             raise ValueError(f"colour frame {color.shape} != pipeline ({self.H},{self.W})")
-        src = SRC_JPEG if isinstance(color, JpegCoefs) else (SRC_RGB if rgb else SRC_BGR)
+        src = SRC_JPEG if isinstance(color, JpegCoefs) else SRC_SCAN if isinstance(color, JpegScan) else (
+            SRC_RGB if rgb else SRC_BGR)
         if src == SRC_JPEG:
             n = color.coefs.numel()
             if n > self.d_coef.numel() or color.blocks * 64 > n:
                 raise ValueError(f"JPEG coefficient planes ({n}) exceed the pipeline's capacity")
+        if src == SRC_SCAN:
+            if color.scan.numel() > self.scan_cap or color.blocks * 64 > self.d_coef.numel() or \
+                    color.nbits > color.scan.numel() * 8:
+                raise ValueError(f"JPEG scan ({color.scan.numel()} bytes) exceeds the pipeline's capacity")
         if self.use_graph and src not in self.graphs:  # first frame from this source (stream-ordered)
             self._capture(src)
         with trace.range("serve.frame.enqueue_color"):
@@ -311,11 +365,14 @@ class FramePipeline:
                     self._hold = color  # its (pinned) buffers must outlive the async copies
                     self.runner.submit_jpeg(color.meta.data_ptr(), color.meta.numel() * 4, color.coefs.data_ptr(),
                                             color.coefs.numel() * 2)
+                elif src == SRC_SCAN:
+                    self.runner.submit_scan(color.meta.data_ptr(), color.tables.data_ptr(), color.scan.data_ptr(),
+                                            color.scan.numel(), int(color.nbits))
                 else:
                     self.runner.submit_array(src, np.ascontiguousarray(color))
             else:
                 s = self.stream
-                if src != SRC_JPEG:
+                if src not in (SRC_JPEG, SRC_SCAN):
                     _stage(self.h_color, color)
                 with torch.cuda.device(self.dev), torch.cuda.stream(s):
                     self.ev0.record(s)
@@ -323,6 +380,12 @@ class FramePipeline:
                         self._hold = color
                         self.d_meta.copy_(color.meta, non_blocking=True)
                         self.d_coef[:color.coefs.numel()].copy_(color.coefs, non_blocking=True)
+                    elif src == SRC_SCAN:
+                        self._hold = color
+                        self.d_smeta.copy_(color.meta, non_blocking=True)
+                        self.d_nbits.fill_(int(color.nbits))
+                        self.d_tables.copy_(color.tables, non_blocking=True)
+                        self.d_scan[:color.scan.numel()].copy_(color.scan, non_blocking=True)
                     else:
                         self.d_color.copy_(self.h_color, non_blocking=True)
                     if self.use_graph:
@@ -330,6 +393,7 @@ class FramePipeline:
                     else:
                         self._net_program(src)
         self._pending_src = src
+        self._scan_frame = src == SRC_SCAN
 
     def submit_depth(self, depth: np.ndarray):
         """Second half of ``submit``: stage the depth frame, enqueue the geometry graph and the result
@@ -368,6 +432,13 @@ class FramePipeline:
         with trace.range("serve.frame.submit_encoded"):
             return self.runner.submit_encoded(color, depth)
 
+    def set_jpeg_entropy(self, policy: str) -> None:
+        """Switch where ``submit_encoded`` entropy-decodes marker-less JPEGs (``jpeg_entropy_policy``);
+        between frames."""
+        self.jpeg_entropy = jpeg_entropy_policy(policy)
+        if self.runner is not None:
+            self.runner.set_gpu_entropy(self.jpeg_entropy != "host")
+
     def submit_request(self, raw: bytes) -> int:
         """A whole serialized AnalysisRequest, its image payloads read in place natively
         (csrc/serve_runtime.cpp parse_request); codes as ``submit_encoded`` (1 also for a message the native
@@ -382,6 +453,8 @@ class FramePipeline:
         must finish on the host (the device's capacity was exceeded: rare)."""
         with trace.range("serve.frame.collect_encoded"):
             payload, mean, maxc, cov, st, gpu_ms = self.runner.collect_encoded(RESP_PNG_LEVEL, RESP_PNG_BANDS)
+        if st == 5:  # known only now; the caller handles the frame as it handles submit code 3
+            raise CorruptScan("corrupt JPEG scan")
         if st == 4:
             from ..geometry.curvature import coverage_from_device
             h_res = self.h_res.numpy()
@@ -403,6 +476,10 @@ class FramePipeline:
                 self.ev1.synchronize()
                 gpu_ms = self.ev0.elapsed_time(self.ev1)
             self._hold = None
+            if getattr(self, "_scan_frame", False):
+                self._scan_frame = False
+                if int(self.scan_status.item()) != 0:
+                    raise CorruptScan("corrupt JPEG scan")
         t1 = time.perf_counter()
         from ..geometry.curvature import coverage_from_device
         h_res = self.h_res.numpy()
@@ -900,6 +977,11 @@ class CpuFramePipeline:
     def submit(self, color_bgr, depth: np.ndarray, rgb: bool = False):
         if color_bgr.shape != (self.H, self.W, 3) or depth.shape != (self.H, self.W):
             raise ValueError(f"frame shape {color_bgr.shape}/{depth.shape} != pipeline ({self.H},{self.W})")
+        if isinstance(color_bgr, JpegScan):  # the GPU entropy decoder's stages as CPU loops
+            jc = entropy_decode(color_bgr)
+            if jc is None:
+                raise CorruptScan("corrupt JPEG scan")
+            color_bgr = jc
         if isinstance(color_bgr, JpegCoefs):  # (the server only sends these to GPU pipelines)
             color_bgr, rgb = coefs_to_rgb_reference(color_bgr), True
         self._pending = (color_bgr[..., ::-1] if rgb else color_bgr, depth)
@@ -987,7 +1069,8 @@ class EnginePool:
 
     def __init__(self, model, K, depth_scale, H: int = 480, W: int = 640, size: int = 256, n: int = 2,
                  threshold: float = 0.5, graph: bool = True, geo_cfg: Optional[GeometryConfig] = None,
-                 devices=None, rgb: bool = False, jpeg: bool = False, max_sizes: int = 3, batch: Optional[int] = None):
+                 devices=None, rgb: bool = False, jpeg: bool = False, max_sizes: int = 3, batch: Optional[int] = None,
+                 jpeg_entropy: Optional[str] = None):
         self.model = model
         self.home_size = (H, W)
         self.max_sizes = max(0, max_sizes)
@@ -997,6 +1080,9 @@ class EnginePool:
         self.n = max(1, n)
         self.gpu = _is_native(model)
         self.jpeg = jpeg and self.gpu  # GPU pipelines also fed JpegCoefs (their graph captured at build)
+        # marker-less JPEGs of encoded requests: host / gpu / auto (jpeg_entropy_policy). Frames that go
+        # through a BatchEngine (concurrent streams) keep the host decode.
+        self.jpeg_entropy = jpeg_entropy_policy(jpeg_entropy)
         home = _model_device(model)
         devs = [torch.device(d) for d in (devices or [home])]
         self.devices = devs
@@ -1046,7 +1132,7 @@ class EnginePool:
         m = self.replicas[r]
         if self.gpu:
             return FramePipeline(m, H=H, W=W, graph=self.graph, device=self.devices[r], rgb=self.rgb,
-                                 jpeg=self.jpeg, **self.args)
+                                 jpeg=self.jpeg, jpeg_entropy=self.jpeg_entropy, **self.args)
         return CpuFramePipeline(m, H=H, W=W, **self.args)
 
     def _get(self, r: int, H, W) -> "queue.Queue":
@@ -1116,6 +1202,12 @@ class EnginePool:
         return s.drain()[0][1]
 
 
+def _decode_frame(color: bytes, depth: bytes):
+    from ..data.image_io import decode_image
+    d = decode_image(depth, False)
+    return decode_image(color, True, "RGB"), (d if d.dtype == np.uint16 else d.astype(np.uint16))
+
+
 class EngineSession:
     """One stream's view of the pool: up to ``depth`` frames in flight on its replica's pipelines.
 
@@ -1126,6 +1218,9 @@ class EngineSession:
         self.pool, self.replica, self.depth = pool, replica, max(1, depth)
         self.inflight: "collections.deque" = collections.deque()
         self.sid = id(self)
+        # (colour bytes, depth bytes) -> (colour frame in RGB order or JpegCoefs, depth u16): decodes a frame
+        # whose JPEG scan the GPU entropy stage found corrupt at collect time (the server sets its own decode)
+        self.decoder = _decode_frame
 
     def _batch_pos(self, b: "BatchEngine", out: list):
         """A position in ``b``'s open batch: without blocking if one is free, else after collecting this
@@ -1247,7 +1342,8 @@ class EngineSession:
         if code != 0:
             q.put(p)
             return out, code
-        self.inflight.append((tag, p, q, True))
+        # the request bytes stay with the frame: a marker-less scan's corruption shows at collect time
+        self.inflight.append((tag, p, q, (color, depth, raw, self.decoder)))
         return out, 0
 
     def submit_encoded_handle(self, color: bytes, depth: bytes, stop=None):
@@ -1278,22 +1374,39 @@ class EngineSession:
         if code != 0:
             q.put(p)
             return ("d", code)
-        return ("t", (p, q))
+        return ("t", (p, q, (color, depth, None, self.decoder)))
 
     @staticmethod
     def collect_handle(handle):
         """The WireResult (or FrameResult / exception) of a ``submit_encoded_handle`` frame; its pipeline or
         batch position is free afterwards."""
-        obj, x = handle
+        obj, x, *req = handle
         try:
             if isinstance(obj, BatchEngine):
                 return obj.collect_encoded(x)
-            return obj.collect_encoded()
+            return EngineSession._collect_encoded(obj, *req[0]) if req else obj.collect_encoded()
         except Exception as e:
             return e
         finally:
             if not isinstance(obj, BatchEngine):
                 x.put(obj)
+
+    @staticmethod
+    def _collect_encoded(p, color, depth, raw, decoder):
+        """``p.collect_encoded()``; a frame whose scan the GPU entropy stage found corrupt is handled as a
+        submit code 3 is: decoded here and run as an array on the same pipeline, at its place in the order."""
+        try:
+            return p.collect_encoded()
+        except CorruptScan:
+            if raw is not None:
+                from ..proto import vision_pb2 as pb
+                req = pb.AnalysisRequest.FromString(raw)
+                color, depth = req.color_image.data, req.depth_image.data
+            c, d = decoder(color, depth)
+            if c.ndim != 3 or c.shape[:2] != d.shape[:2] or c.shape[:2] != (p.H, p.W):
+                raise ValueError(f"colour {c.shape} and depth {d.shape} frame sizes differ")
+            p.submit(c, d, rgb=True)
+            return p.collect()
 
     def _collect_one(self):
         tag, p, q, *enc = self.inflight.popleft()
@@ -1303,7 +1416,7 @@ class EngineSession:
             except Exception as e:
                 return tag, e
         try:
-            return tag, (p.collect_encoded() if enc else p.collect())
+            return tag, (self._collect_encoded(p, *enc[0]) if enc else p.collect())
         except Exception as e:  # a failed frame must not take the pipeline with it
             return tag, e
         finally:

@@ -176,6 +176,14 @@ class VisionAnalysisService(pb.VisionAnalysisServiceServicer):
         self.stage_ms["decode_color"].append((time.perf_counter() - t) * 1e3)
         return out
 
+    def _session(self):
+        """An engine session that decodes like this service: a frame whose marker-less JPEG scan the GPU
+        entropy stage finds corrupt (known when it is collected) is then decoded and served exactly as a
+        frame the native path declines with code 3."""
+        sess = self.engine.session()
+        sess.decoder = lambda cb, db: (self._decode_color(cb), self._decode_depth(db))
+        return sess
+
     def _decode_depth(self, data: bytes):
         t = time.perf_counter()
         out = self._as_u16(decode_image(data, False))
@@ -352,7 +360,7 @@ class VisionAnalysisService(pb.VisionAnalysisServiceServicer):
             return
         log.info("new analysis stream")
         inflight: "collections.deque" = collections.deque()  # encode futures, request order
-        sess = self.engine.session()
+        sess = self._session()
         times = {}
 
         def encode(results):
@@ -436,7 +444,7 @@ class VisionAnalysisService(pb.VisionAnalysisServiceServicer):
         path, in order. Each response leaves as soon as its frame is collected, in request order."""
         import grpc
         log.info("new analysis stream")
-        sess = self.engine.session()
+        sess = self._session()
         items: "queue.Queue" = queue.Queue()
         END = object()
         lk = threading.Lock()
@@ -632,7 +640,7 @@ def build_server(cfg: ServeConfig, device: Optional[torch.device] = None, pool_s
     metrics = MetricsLog(cfg.metrics_log)
     engine = EnginePool(model, K, ds, n=pool_size or cfg.replicas_per_device, threshold=cfg.mask_threshold,
                         graph=cfg.graph, size=cfg.model_img_size, devices=devices, rgb=True,
-                        jpeg=cfg.gpu_jpeg and _is_native(model))
+                        jpeg=cfg.gpu_jpeg and _is_native(model), jpeg_entropy=cfg.jpeg_entropy)
     service = VisionAnalysisService(engine, metrics, frame_errors=cfg.frame_errors, faults=faults)
     server = grpc.server(futures.ThreadPoolExecutor(max_workers=cfg.max_workers))
     pb.add_VisionAnalysisServiceServicer_to_server(service, server)
