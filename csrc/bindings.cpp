@@ -85,6 +85,12 @@ int rdp_head_bwd(const void*, int, const float*, const float*, const float*, con
 int rdp_head_bn_bwd_apply(const void*, int, const float*, const float*, const float*, const float*, const float*,
                           const float*, void*, int, int, float, float, float, hipStream_t);
 int rdp_head_mask(const void*, int, const float*, const float*, float, void*, int, hipStream_t);
+int rdp_headk_partial_blocks(long);
+int rdp_headk_fwd(const void*, int, const float*, const float*, const void*, float*, float*, float*, float*, int, int,
+                  hipStream_t);
+int rdp_headk_bwd(const void*, int, const float*, const float*, const void*, const float*, void*, int, float*, float*,
+                  float*, int, int, float, hipStream_t);
+int rdp_headk_mask(const void*, int, const float*, const float*, int, void*, int, int, hipStream_t);
 int rdp_adam(float*, const void*, int, float*, float*, void*, long, float, float, float, float, float, float, int*, int,
              int, hipStream_t);
 int rdp_cast_bf16(const float*, void*, long, hipStream_t);
@@ -1265,6 +1271,80 @@ void head_mask(torch::Tensor a, torch::Tensor w, torch::Tensor b, double logit_t
                 x.N * x.H * x.W, st));
 }
 
+// ---- K-class head (csrc/head_multi.hip): w [K][64] fp32 (outc.conv.weight's physical layout), b [K] ----
+int headk_partial_blocks(long M) { return rdp_headk_partial_blocks(M); }
+
+// the class count of a K-class head call, from its weight / bias operands (2 <= K <= 8)
+int headk_classes(const torch::Tensor& w, const torch::Tensor& b, const char* who) {
+  check_f32(w, "w");
+  check_f32(b, "b");
+  const long K = b.numel();
+  TORCH_CHECK(K >= 2 && K <= 8, who, ": the K-class head takes 2 <= K <= 8 classes, got ", K);
+  TORCH_CHECK(w.numel() == K * 64, who, ": w must be [K][64]");
+  return (int)K;
+}
+
+void check_u8(const torch::Tensor& t, long numel, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kUInt8 && t.is_contiguous() && t.numel() == numel, name,
+              ": must be a contiguous u8 GPU tensor of ", numel, " elements");
+}
+
+// logits [M][K] fp32, softmax cross-entropy over the labels < K (u8; 255 and every label >= K ignored):
+// loss[0] = loss[1] = mean over the kept pixels, sums[0..1] = {sum ce, kept pixels}
+void headk_fwd(torch::Tensor a, torch::Tensor w, torch::Tensor b, torch::Tensor labels, torch::Tensor logits,
+               torch::Tensor partial, torch::Tensor sums, torch::Tensor loss) {
+  Act x = act(a, "a");
+  const int K = headk_classes(w, b, "headk_fwd");
+  TORCH_CHECK(x.C == 64, "head expects 64 channels");
+  const long M = (long)x.N * x.H * x.W;
+  TORCH_CHECK(M > 0 && M < (1L << 31), "headk_fwd: pixel count");
+  check_u8(labels, M, "labels");
+  check_f32(logits, "logits");
+  check_f32(partial, "partial");
+  check_f32(sums, "sums");
+  check_f32(loss, "loss");
+  TORCH_CHECK(logits.numel() == M * K, "headk_fwd: logits must hold M * K values");
+  TORCH_CHECK(partial.numel() >= (long)rdp_headk_partial_blocks(M) * 2, "headk_fwd: partial too small");
+  TORCH_CHECK(sums.numel() >= 2 && loss.numel() >= 2, "headk_fwd: sums / loss need 2 values");
+  TORCH_CHECK(RDP_PLAN(rdp_headk_fwd(x.ptr, x.pitch, w.data_ptr<float>(), b.data_ptr<float>(), labels.data_ptr(),
+                                     logits.data_ptr<float>(), partial.data_ptr<float>(), sums.data_ptr<float>(),
+                                     loss.data_ptr<float>(), (int)M, K, st)) > 0, "headk_fwd");
+}
+
+// da = d loss / d a (bf16), gw [K][64] / gb [K] = the head's gradients; partial: >= blocks * (K * 65) floats
+void headk_bwd(torch::Tensor a, torch::Tensor w, torch::Tensor logits, torch::Tensor labels, torch::Tensor sums,
+               torch::Tensor da, torch::Tensor partial, torch::Tensor gw, torch::Tensor gb, double gscale) {
+  Act x = act(a, "a"), d = act(da, "da");
+  const int K = headk_classes(w, gb, "headk_bwd");
+  const long M = (long)x.N * x.H * x.W;
+  TORCH_CHECK(M > 0 && M < (1L << 31), "headk_bwd: pixel count");
+  TORCH_CHECK(x.C == 64 && d.C == 64 && (long)d.N * d.H * d.W == M, "headk_bwd: a / da shapes");
+  check_u8(labels, M, "labels");
+  check_f32(logits, "logits");
+  check_f32(partial, "partial");
+  check_f32(sums, "sums");
+  check_f32(gw, "gw");
+  TORCH_CHECK(logits.numel() == M * K && sums.numel() >= 2 && gw.numel() == K * 64, "headk_bwd: logits / sums / gw sizes");
+  TORCH_CHECK(partial.numel() >= (long)rdp_headk_partial_blocks(M) * (K * 65), "headk_bwd: partial too small");
+  TORCH_CHECK(RDP_PLAN(rdp_headk_bwd(x.ptr, x.pitch, w.data_ptr<float>(), logits.data_ptr<float>(), labels.data_ptr(),
+                                     sums.data_ptr<float>(), d.ptr, d.pitch, partial.data_ptr<float>(),
+                                     gw.data_ptr<float>(), gb.data_ptr<float>(), (int)M, K, (float)gscale, st)) > 0,
+              "headk_bwd");
+}
+
+// serving: mask[p] = (argmax_k logits[p][k] == cls), ties to the lowest class
+void headk_mask(torch::Tensor a, torch::Tensor w, torch::Tensor b, int cls, torch::Tensor mask) {
+  Act x = act(a, "a");
+  const int K = headk_classes(w, b, "headk_mask");
+  TORCH_CHECK(x.C == 64, "head expects 64 channels");
+  const long M = (long)x.N * x.H * x.W;
+  TORCH_CHECK(M > 0 && M < (1L << 31), "headk_mask: pixel count");
+  TORCH_CHECK(cls >= 0 && cls < K, "headk_mask: class ", cls, " outside 0..", K - 1);
+  check_u8(mask, M, "mask");
+  TORCH_CHECK(RDP_PLAN(rdp_headk_mask(x.ptr, x.pitch, w.data_ptr<float>(), b.data_ptr<float>(), cls, mask.data_ptr(),
+                                      (int)M, K, st)) == 0, "headk_mask");
+}
+
 void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow,
           double lr, double b1, double b2, double eps, double wd, double gscale, torch::Tensor step, bool inc,
           int max_blocks) {
@@ -1920,6 +2000,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("gscale"), py::arg("coef") = py::none(), py::arg("bnpart") = py::none());
   m.def("head_bn_bwd_apply", on_device(&head_bn_bwd_apply));
   m.def("head_mask", on_device(&head_mask));
+  m.def("headk_partial_blocks", &headk_partial_blocks);
+  m.def("headk_fwd", on_device(&headk_fwd), py::arg("a"), py::arg("w"), py::arg("b"), py::arg("labels"),
+        py::arg("logits"), py::arg("partial"), py::arg("sums"), py::arg("loss"));
+  m.def("headk_bwd", on_device(&headk_bwd), py::arg("a"), py::arg("w"), py::arg("logits"), py::arg("labels"),
+        py::arg("sums"), py::arg("da"), py::arg("partial"), py::arg("gw"), py::arg("gb"), py::arg("gscale") = 1.0);
+  m.def("headk_mask", on_device(&headk_mask), py::arg("a"), py::arg("w"), py::arg("b"), py::arg("cls"),
+        py::arg("mask"));
   m.def("conv_head_mask", on_device(&conv_head_mask));
   m.def("conv_rowband_chain", on_device(&conv_rowband_chain));
   m.def("conv_rowband", on_device(&conv_rowband));

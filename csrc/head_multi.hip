@@ -1,0 +1,402 @@
+// 1x1 output head for K classes (64 -> K, with bias, 2 <= K <= 8) fused with softmax cross-entropy,
+// and its serving form (class-selected mask). The one-class head lives in head_loss.hip.
+//
+// Reference: OutConv = nn.Conv2d(64, n_classes, 1); loss = F.cross_entropy(logits, labels,
+// ignore_index=255), mean over the kept pixels.
+//
+// headk_fwd: logits[p][k] = sum_c a[p][c]*w[k][c] + b[k] (pixel-major fp32); per-block partials of
+//   {sum ce, kept pixels}, ce = logsumexp(x) - x[label] with the max subtracted.
+//   Labels are uint8; 255 is ignored, and so is every label >= K (never used as an index).
+//   headk_loss_finalize: sums = {sum ce, count}, loss = sum ce / max(count, 1) (fp64 sum).
+//   If every pixel is ignored the loss is 0 and every gradient is 0 (torch returns NaN there).
+// headk_bwd: dlogit[k] = (softmax(x)[k] - [k == label]) * gscale / count for kept pixels, 0 for
+//   ignored ones (count read from `sums` on the device); da[p][c] = bf16(sum_k dlogit[k]*w[k][c]);
+//   per-block partials [blk][K*64 + K] of dW and db; headk_grad_finalize sums them into the gradient
+//   views in the parameter's [K][64] order.
+// headk_mask: mask[p] = argmax_k(a[p].w[k] + b[k]) == cls, ties to the lowest index.
+//
+// Memory pattern of head_loss.hip: 8 lanes per pixel, one 16-B load of 8 bf16 channels per lane,
+// HPX pixels in flight per lane group, grid capped at 2048 blocks, per-block partial rows and a
+// one-launch finalize. No float atomics: results are bitwise repeatable.
+//
+// The K per-lane partial dots of a pixel are reduced over its 8 lanes transpose-style: at each step
+// a lane keeps one half of its values and hands the other half to its partner, so after log2(KP)
+// steps (KP = K rounded up to a power of two) lane `sub` owns logit `sub & (KP - 1)` -- 7 shuffles
+// at K = 8 where K separate butterflies would take 24.
+#include "common.h"
+#include <algorithm>
+
+#define HEAD_C 64
+#define HPX 4  // pixels in flight per 8-lane group
+
+namespace {
+
+RDP_DEV void unpack8h(const uint4& v, float* f) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    f[2 * k] = __uint_as_float(w[k] << 16);
+    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
+  }
+}
+
+constexpr int pow2_classes(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : 8; }
+
+// v[k] = this lane's partial of logit k (0 for the padding k >= K). Returns the full sum over the
+// pixel's 8 lanes of logit (sub & (KP - 1)).
+template <int KP>
+RDP_DEV float reduce_transpose(float (&v)[KP], int sub) {
+#pragma unroll
+  for (int h = KP / 2; h >= 1; h >>= 1) {
+    const bool up = (sub & h) != 0;
+#pragma unroll
+    for (int j = 0; j < h; ++j) {
+      const float send = up ? v[j] : v[j + h];
+      const float keep = up ? v[j + h] : v[j];
+      v[j] = keep + __shfl_xor(send, h, 64);
+    }
+  }
+  float r = v[0];
+#pragma unroll
+  for (int o = KP; o < 8; o <<= 1) r += __shfl_xor(r, o, 64);
+  return r;
+}
+
+// the logit this lane owns for the pixel whose 8 channels it holds in `f` (bias not added)
+template <int K>
+RDP_DEV float lane_logit(const float* f, const float (&wl)[K][8], int sub) {
+  constexpr int KP = pow2_classes(K);
+  float d[KP];
+#pragma unroll
+  for (int k = 0; k < KP; ++k) {
+    float s = 0.f;
+    if (k < K) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s = fmaf(f[j], wl[k][j], s);
+    }
+    d[k] = s;
+  }
+  return reduce_transpose<KP>(d, sub);
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void headk_fwd_kernel(const u16* __restrict__ a, int apitch,
+                                                        const float* __restrict__ w, const float* __restrict__ b,
+                                                        const uint8_t* __restrict__ labels,
+                                                        float* __restrict__ logits, float* __restrict__ partial,
+                                                        int M) {
+  constexpr int KP = pow2_classes(K);
+  __shared__ float red[4][2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane & 7;
+  const int kk = sub & (KP - 1);  // the logit this lane ends up owning
+  const bool own = kk < K;
+  float wl[K][8];
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wl[k][j] = w[k * HEAD_C + sub * 8 + j];
+  const float bias = own ? b[kk] : 0.f;
+  float sce = 0.f, scnt = 0.f;
+  const long stride = (long)gridDim.x * 32;  // 32 pixel groups per block
+  for (long p0 = blockIdx.x * 32l + (threadIdx.x >> 3); p0 < M; p0 += stride * HPX) {
+    uint4 v[HPX];
+    int lab[HPX];
+#pragma unroll
+    for (int u = 0; u < HPX; ++u) {
+      const long p = p0 + u * stride;
+      v[u] = make_uint4(0u, 0u, 0u, 0u);
+      lab[u] = 255;
+      if (p < M) {
+        v[u] = *(const uint4*)(a + (size_t)p * apitch + sub * 8);
+        lab[u] = labels[p];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < HPX; ++u) {  // every lane runs the shuffles (zeros past M); only stores are guarded
+      const long p = p0 + u * stride;
+      float f[8];
+      unpack8h(v[u], f);
+      const float x = lane_logit<K>(f, wl, sub) + bias;
+      float mx = own ? x : -INFINITY;
+#pragma unroll
+      for (int o = 1; o < KP; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+      float se = own ? __expf(x - mx) : 0.f;
+#pragma unroll
+      for (int o = 1; o < KP; o <<= 1) se += __shfl_xor(se, o, 64);
+      if (p < M) {
+        if (sub < K) logits[(size_t)p * K + sub] = x;  // sub < K: kk == sub
+        if (lab[u] < K && sub == lab[u]) {  // kept pixel: the lane that owns x[label] finishes it
+          sce += mx + logf(se) - x;
+          scnt += 1.f;
+        }
+      }
+    }
+  }
+  sce = wave_sum(sce);
+  scnt = wave_sum(scnt);
+  if (lane == 0) { red[wave][0] = sce; red[wave][1] = scnt; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int q = threadIdx.x;
+    partial[blockIdx.x * 2 + q] = red[0][q] + red[1][q] + red[2][q] + red[3][q];
+  }
+}
+
+// sums[0..1] = {sum ce, kept pixels}; loss[0] = loss[1] = mean ce over the kept pixels (0 if none)
+__global__ void headk_loss_finalize_kernel(const float* __restrict__ partial, int T, float* __restrict__ sums,
+                                           float* __restrict__ loss) {
+  __shared__ double red[2][64];
+  const int q = threadIdx.x >> 6, l = threadIdx.x & 63;  // 128 threads: 2 quantities x 64 lanes
+  double s = 0.0;
+  for (int t = l; t < T; t += 64) s += (double)partial[t * 2 + q];
+  red[q][l] = s;
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double tot = 0.0;
+    for (int k = 0; k < 64; ++k) tot += red[threadIdx.x][k];
+    sums[threadIdx.x] = (float)tot;
+    red[threadIdx.x][0] = tot;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double cnt = red[1][0] > 1.0 ? red[1][0] : 1.0;
+    const float L = (float)(red[0][0] / cnt);
+    loss[0] = L;
+    loss[1] = L;
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void headk_bwd_kernel(const u16* __restrict__ a, int apitch,
+                                                        const float* __restrict__ w,
+                                                        const float* __restrict__ logits,
+                                                        const uint8_t* __restrict__ labels,
+                                                        const float* __restrict__ sums, u16* __restrict__ da,
+                                                        int dapitch, float* __restrict__ partial, int M,
+                                                        float gscale) {
+  constexpr int ROW = K * HEAD_C + K;
+  __shared__ float red[4][ROW];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int sub = lane & 7;
+  float wl[K][8], gw[K][8], gb[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    gb[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      wl[k][j] = w[k * HEAD_C + sub * 8 + j];
+      gw[k][j] = 0.f;
+    }
+  }
+  // Everything accumulates the unscaled (softmax - onehot) / count; the loss scale multiplies the
+  // finished values (da per pixel before its bf16 rounding, dW / db in the finalize), so it scales
+  // the gradients exactly
+  const float invc = 1.f / fmaxf(sums[1], 1.f);
+  const long stride = (long)gridDim.x * 32;
+  for (long p0 = blockIdx.x * 32l + (threadIdx.x >> 3); p0 < M; p0 += stride * HPX) {
+    uint4 vq[HPX];
+    float xq[HPX][K];
+    int lab[HPX];
+#pragma unroll
+    for (int u = 0; u < HPX; ++u) {
+      const long p = p0 + u * stride;
+      if (p < M) {
+        vq[u] = *(const uint4*)(a + (size_t)p * apitch + sub * 8);
+        lab[u] = labels[p];
+#pragma unroll
+        for (int k = 0; k < K; ++k) xq[u][k] = logits[(size_t)p * K + k];  // all 8 lanes: one broadcast line
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < HPX; ++u) {
+      const long p = p0 + u * stride;
+      if (p >= M) break;
+      float o[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = 0.f;
+      if (lab[u] < K) {  // kept pixel (the 8 lanes of the group agree)
+        float mx = xq[u][0];
+#pragma unroll
+        for (int k = 1; k < K; ++k) mx = fmaxf(mx, xq[u][k]);
+        float e[K], se = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          e[k] = __expf(xq[u][k] - mx);
+          se += e[k];
+        }
+        const float inv = 1.f / se;
+        float f[8];
+        unpack8h(vq[u], f);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float dl = (e[k] * inv - (k == lab[u] ? 1.f : 0.f)) * invc;
+          gb[k] += dl;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            gw[k][j] = fmaf(dl, f[j], gw[k][j]);
+            o[j] = fmaf(dl, wl[k][j], o[j]);
+          }
+        }
+      }
+      uint4 ov;
+      ov.x = pack2bf(o[0] * gscale, o[1] * gscale);
+      ov.y = pack2bf(o[2] * gscale, o[3] * gscale);
+      ov.z = pack2bf(o[4] * gscale, o[5] * gscale);
+      ov.w = pack2bf(o[6] * gscale, o[7] * gscale);
+      *(uint4*)(da + (size_t)p * dapitch + sub * 8) = ov;
+    }
+  }
+  // reduce over the 8 pixel groups of the wave that share `sub` (gb: every lane of a group holds the
+  // same value, so the same three steps leave the wave total in every lane)
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float v = gw[k][j];
+      v += __shfl_xor(v, 8, 64);
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      gw[k][j] = v;
+    }
+    float g = gb[k];
+    g += __shfl_xor(g, 8, 64);
+    g += __shfl_xor(g, 16, 64);
+    g += __shfl_xor(g, 32, 64);
+    gb[k] = g;
+  }
+  if (lane < 8) {
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) red[wave][k * HEAD_C + lane * 8 + j] = gw[k][j];
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[wave][K * HEAD_C + k] = gb[k];
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < ROW; c += 256)
+    partial[(size_t)blockIdx.x * ROW + c] = red[0][c] + red[1][c] + red[2][c] + red[3][c];
+}
+
+// gw[0 .. K*64) = dW in [K][64] order, gbias[0 .. K) = db, both times the loss scale: one block per
+// column of the [T][row] partials
+__global__ void headk_grad_finalize_kernel(const float* __restrict__ partial, int T, int row, int nw, float gscale,
+                                           float* __restrict__ gw, float* __restrict__ gbias) {
+  __shared__ float red[4];
+  const int c = blockIdx.x;
+  float s = 0.f;
+  for (int t = threadIdx.x; t < T; t += 256) s += partial[(size_t)t * row + c];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float tot = (red[0] + red[1] + red[2] + red[3]) * gscale;
+    if (c < nw) gw[c] = tot; else gbias[c - nw] = tot;
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void headk_mask_kernel(const u16* __restrict__ a, int apitch,
+                                                         const float* __restrict__ w, const float* __restrict__ b,
+                                                         int cls, uint8_t* __restrict__ mask, int M) {
+  constexpr int KP = pow2_classes(K);
+  const int sub = threadIdx.x & 7;
+  const int kk = sub & (KP - 1);
+  const bool own = kk < K;
+  float wl[K][8];
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) wl[k][j] = w[k * HEAD_C + sub * 8 + j];
+  const float bias = own ? b[kk] : 0.f;
+  const long stride = (long)gridDim.x * 32;
+  // (the trip count is the same for the 8 lanes of a group, and the shuffles stay inside the group)
+  for (long p = blockIdx.x * 32l + (threadIdx.x >> 3); p < M; p += stride) {
+    const uint4 v = *(const uint4*)(a + (size_t)p * apitch + sub * 8);
+    float f[8];
+    unpack8h(v, f);
+    float x = lane_logit<K>(f, wl, sub) + bias;
+    if (!own) x = -INFINITY;
+    int idx = kk;
+#pragma unroll
+    for (int o = 1; o < KP; o <<= 1) {
+      const float ox = __shfl_xor(x, o, 64);
+      const int oi = __shfl_xor(idx, o, 64);
+      if (ox > x || (ox == x && oi < idx)) { x = ox; idx = oi; }
+    }
+    if (sub == 0) mask[p] = idx == cls ? 1 : 0;
+  }
+}
+
+int blocks_for(long M) { return (int)std::max<long>(1, std::min<long>((M + 31) / 32, 2048)); }
+
+template <int K>
+void launch_fwd(int nb, hipStream_t s, const void* a, int apitch, const float* w, const float* b, const void* labels,
+                float* logits, float* partial, int M) {
+  hipLaunchKernelGGL(headk_fwd_kernel<K>, dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, b,
+                     (const uint8_t*)labels, logits, partial, M);
+}
+
+template <int K>
+void launch_bwd(int nb, hipStream_t s, const void* a, int apitch, const float* w, const float* logits,
+                const void* labels, const float* sums, void* da, int dapitch, float* partial, int M, float gscale) {
+  hipLaunchKernelGGL(headk_bwd_kernel<K>, dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, logits,
+                     (const uint8_t*)labels, sums, (u16*)da, dapitch, partial, M, gscale);
+}
+
+template <int K>
+void launch_mask(int nb, hipStream_t s, const void* a, int apitch, const float* w, const float* b, int cls, void* mask,
+                 int M) {
+  hipLaunchKernelGGL(headk_mask_kernel<K>, dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, b, cls,
+                     (uint8_t*)mask, M);
+}
+
+#define HEADK_DISPATCH(K, FN, ...)          \
+  switch (K) {                              \
+    case 2: FN<2>(__VA_ARGS__); break;      \
+    case 3: FN<3>(__VA_ARGS__); break;      \
+    case 4: FN<4>(__VA_ARGS__); break;      \
+    case 5: FN<5>(__VA_ARGS__); break;      \
+    case 6: FN<6>(__VA_ARGS__); break;      \
+    case 7: FN<7>(__VA_ARGS__); break;      \
+    case 8: FN<8>(__VA_ARGS__); break;      \
+    default: return -1;                     \
+  }
+
+}  // namespace
+
+extern "C" {
+int rdp_headk_partial_blocks(long M) { return blocks_for(M); }
+
+// partial: >= blocks * 2 floats. Returns the number of partial rows, < 0 if nothing was launched.
+int rdp_headk_fwd(const void* a, int apitch, const float* w, const float* b, const void* labels, float* logits,
+                  float* partial, float* sums, float* loss, int M, int K, hipStream_t s) {
+  if (apitch % 8 || M <= 0) return -1;
+  const int nb = blocks_for(M);
+  HEADK_DISPATCH(K, launch_fwd, nb, s, a, apitch, w, b, labels, logits, partial, M)
+  hipLaunchKernelGGL(headk_loss_finalize_kernel, dim3(1), dim3(128), 0, s, partial, nb, sums, loss);
+  return nb;
+}
+
+// partial: >= blocks * (K * 64 + K) floats; gw [K][64], gb [K]
+int rdp_headk_bwd(const void* a, int apitch, const float* w, const float* logits, const void* labels,
+                  const float* sums, void* da, int dapitch, float* partial, float* gw, float* gb, int M, int K,
+                  float gscale, hipStream_t s) {
+  if (apitch % 8 || dapitch % 8 || M <= 0) return -1;
+  const int nb = blocks_for(M);
+  HEADK_DISPATCH(K, launch_bwd, nb, s, a, apitch, w, logits, labels, sums, da, dapitch, partial, M, gscale)
+  const int row = K * HEAD_C + K;
+  hipLaunchKernelGGL(headk_grad_finalize_kernel, dim3(row), dim3(256), 0, s, partial, nb, row, K * HEAD_C,
+                     gscale, gw, gb);
+  return nb;
+}
+
+int rdp_headk_mask(const void* a, int apitch, const float* w, const float* b, int cls, void* mask, int M, int K,
+                   hipStream_t s) {
+  if (apitch % 8 || M <= 0 || cls < 0 || cls >= K) return -1;
+  HEADK_DISPATCH(K, launch_mask, blocks_for(M), s, a, apitch, w, b, cls, mask, M)
+  return 0;
+}
+}

@@ -49,7 +49,9 @@ class TrainConfig:
     epochs: int = 50
     validation_split: float = 0.2
     image_size: int = 256
-    loss: str = "bce"  # "bce" (reference) or "bce_dice" (north star)
+    # "bce" (reference) or "bce_dice" (north star); "ce" = softmax cross-entropy, the only loss of a
+    # K-class model (NativeTrainer / EagerTrainer; train_model and the on-disk dataset stay binary)
+    loss: str = "bce"
     dice_weight: float = 1.0
     seed: int = 0  # the reference split is unseeded; we seed it
     dataset_dir: str = os.path.join("ml", "datasets", "processed")  # CWD-relative like the reference
@@ -83,7 +85,11 @@ class ServeConfig:
     mlruns_dir: str = str(PROJECT_ROOT / "ml" / "mlruns")
     calib_file: str = str(PROJECT_ROOT / "ml" / "configs" / "calibration_data.npz")
     metrics_log: str = str(PROJECT_ROOT / "logs" / "vision_service_metrics.csv")
-    mask_threshold: float = 0.5
+    mask_threshold: float = 0.5  # one-class models: sigmoid(logit) > threshold (not used by a K-class model)
+    # K-class models (n_classes > 1): the class whose arg-max pixels form the mask that goes to geometry
+    # and into the response (class 0 is background by convention). Ignored by a one-class model.
+    # RDP_SERVE_MASK_CLASS overrides.
+    mask_class: int = 1
     backend: str = "auto"
     graph: bool = True
     devices: str = ""  # comma-separated GPU indices for per-GPU replicas ("" = current device only; "all")

@@ -161,8 +161,8 @@ class UNetNative(nn.Module):
     def __init__(self, n_channels: int = 3, n_classes: int = 1, bilinear: bool = True, base_width: int = 64,
                  depth: int = 4, device: Optional[torch.device] = None, init_from: Optional[nn.Module] = None):
         super().__init__()
-        if n_classes != 1:
-            raise NotImplementedError("native head supports n_classes == 1 (reference: UNet(3, 1))")
+        if not 1 <= n_classes <= 8:
+            raise NotImplementedError("native head supports 1 <= n_classes <= 8 (csrc/head_loss.hip, head_multi.hip)")
         if n_channels > 8:
             raise NotImplementedError("native first layer packs <= 8 input channels")
         if base_width != 64:
@@ -383,13 +383,20 @@ class UNetNative(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """NCHW float input -> NCHW fp32 logits (inference helper; training uses UNetExecutor)."""
-        ex = self.executor(x.shape[0], x.shape[2], x.shape[3], training=False)
+        ex = self.executor(x.shape[0], x.shape[2], x.shape[3], training=False,
+                           loss="ce" if self.n_classes > 1 else "bce")
         ex.set_input(x)
         ex.forward()
         return ex.logits_nchw()
 
     def executor(self, batch: int, h: int, w: int, training: bool = True, loss: str = "bce",
                  dice_weight: float = 1.0) -> "UNetExecutor":
+        """``loss``: "bce" / "bce_dice" for the one-class head; a K-class model (``n_classes > 1``) takes
+        "ce" only (softmax cross-entropy over integer labels, 255 and labels >= K ignored)."""
+        if self.n_classes > 1 and loss != "ce":
+            raise ValueError(f'a {self.n_classes}-class model trains with loss="ce" only, got {loss!r}')
+        if self.n_classes == 1 and loss == "ce":
+            raise ValueError('loss="ce" needs n_classes > 1 (the one-class head takes "bce" / "bce_dice")')
         key = (batch, h, w, training, loss, dice_weight)
         cache = self.__dict__.setdefault("_executors", {})
         if key not in cache:
@@ -538,7 +545,10 @@ class UNetExecutor:
         # boundaries, upsample backward + BN reduce at the Up boundaries; in training the 1x1 head
         # applies the last conv's BN+ReLU itself (forward) and produces that BN's backward partials and
         # dy from the logits (backward), so the 64-ch activation and its gradient are never stored.
-        self.fuse_head = training
+        # A K-class head (csrc/head_multi.hip) has no BN-fused form: the last BN apply materialises
+        # ``final``, headk_bwd writes the last layer's da and the ordinary BN backward passes follow.
+        self.K = model.n_classes
+        self.fuse_head = training and self.K == 1
         C = _native()
         D = model.depth
         bf = torch.bfloat16
@@ -554,7 +564,8 @@ class UNetExecutor:
             return torch.zeros(N, h, w, c, dtype=bf, device=dev)
 
         self.x_in = t(H, W, 8)
-        self.target = torch.zeros(N * H * W, dtype=torch.float32, device=dev)
+        # one-class: fp32 mask values; K classes: uint8 class ids (255 and ids >= K are ignored by the loss)
+        self.target = torch.zeros(N * H * W, dtype=torch.float32 if self.K == 1 else torch.uint8, device=dev)
         self.layers: List[_Layer] = []
         it = iter(specs)
 
@@ -624,8 +635,12 @@ class UNetExecutor:
                            (fu == "1" if fu is not None else N * H * W <= (1 << 20)))
         M = N * H * W
         self.M = M
-        self.logits = torch.zeros(M, dtype=torch.float32, device=dev)
-        self.head_partial = torch.zeros(C.head_partial_blocks(M) * 65, dtype=torch.float32, device=dev)
+        if self.K == 1:
+            self.logits = torch.zeros(M, dtype=torch.float32, device=dev)
+            self.head_partial = torch.zeros(C.head_partial_blocks(M) * 65, dtype=torch.float32, device=dev)
+        else:  # pixel-major [M][K] logits; per-block rows of K x 64 dW + K db (the forward uses 2 per block)
+            self.logits = torch.zeros(M * self.K, dtype=torch.float32, device=dev)
+            self.head_partial = torch.zeros(C.headk_partial_blocks(M) * self.K * 65, dtype=torch.float32, device=dev)
         # BCE-only training with the BN-fused head: the forward pass also emits the head's backward
         # partials (d loss / d logit is local), so backward only finalizes them (no second read of y)
         self.head_grads_in_fwd = self.fuse_head and self.dice_w == 0.0
@@ -761,7 +776,8 @@ class UNetExecutor:
 
     # ------------------------------------------------------------------ data
     def set_input(self, x: torch.Tensor, target: Optional[torch.Tensor] = None):
-        """x: [N,C,H,W] (float, values in [0,1]) or NHWC8 bf16; target: [N,1,H,W] float masks."""
+        """x: [N,C,H,W] (float, values in [0,1]) or NHWC8 bf16; target: [N,1,H,W] float masks, or for a
+        K-class model [N,H,W] / [N,1,H,W] integer class ids of any integer dtype (255 = ignore)."""
         with torch.no_grad():
             if x.dim() == 4 and x.shape[-1] == 8 and x.dtype == torch.bfloat16:
                 self.x_in.copy_(x)
@@ -851,7 +867,9 @@ class UNetExecutor:
         pipeline recomputes them only when the weights change, not per frame).
         ``mask_head=(head_w, head_b, logit_thr, mask_u8)`` (eval, with ``head=False``): the serving mask
         ``head(a_final) > logit_thr``; where the row-ring kernel runs the last conv, the head is fused
-        into its epilogue and ``final`` is not materialised (elsewhere the separate ``head_mask`` launch)."""
+        into its epilogue and ``final`` is not materialised (elsewhere the separate ``head_mask`` launch).
+        K-class model: ``mask_head=(head_w [K*64], head_b [K], cls, mask_u8)``, the mask of the pixels
+        whose arg-max class is ``cls``; always the separate ``headk_mask`` launch."""
         C = _native()
         D = self.m.depth
         if not self.training and refresh_eval:
@@ -907,7 +925,12 @@ class UNetExecutor:
             low_layer = lb
         if not head:
             if mask_head is not None:
-                C.head_mask(self.final, *mask_head)
+                (C.headk_mask if self.K > 1 else C.head_mask)(self.final, *mask_head)
+            return
+        if self.K > 1:
+            st = self.m.store
+            C.headk_fwd(self.final, st.flat_slice("outc.conv.weight"), st.view("outc.conv.bias"), self.target,
+                        self.logits, self.head_partial, self.loss_sums, self.loss)
             return
         head_w = self.m.store.view("outc.conv.weight").reshape(-1)
         head_b = self.m.store.view("outc.conv.bias")
@@ -928,12 +951,16 @@ class UNetExecutor:
     def _conv_head_mask(self, C, L: _Layer, mask_head: tuple) -> bool:
         """Eval: the last conv + BN fold + ReLU + 1x1 head + threshold in one row-ring launch."""
         sp = L.spec
+        if self.K > 1:  # the row-ring fused head is one-class: K classes take the separate headk_mask launch
+            return False
         if self.training or L.x2 is not None or sp.taps != 9 or sp.packed:
             return False
         hw, hb, thr, mask = mask_head
         return bool(C.conv_head_mask(L.x1, self.m.fwd_weight(sp), L.coef, hw, hb, float(thr), mask))
 
     def logits_nchw(self) -> torch.Tensor:
+        if self.K > 1:  # stored pixel-major [N,H,W,K]
+            return self.logits.view(self.N, self.H, self.W, self.K).permute(0, 3, 1, 2)
         return self.logits.view(self.N, 1, self.H, self.W)
 
     # ------------------------------------------------------------------ backward
@@ -1200,7 +1227,10 @@ class UNetExecutor:
         last = self.up_layers[-1][1] if D else self.down_layers[0][1]
         hgw, hgb = st.flat_slice("outc.conv.weight", st.grad), st.flat_slice("outc.conv.bias", st.grad)
         head_gscale = None
-        if self.fuse_head and self._head_fwd_grads and gscale == self.head_gscale:
+        if self.K > 1:  # softmax CE head: da of the last layer + dW [K][64] / db [K] (csrc/head_multi.hip)
+            C.headk_bwd(self.final, st.flat_slice("outc.conv.weight"), self.logits, self.target, self.loss_sums,
+                        last.da, self.head_partial, hgw, hgb, gscale)
+        elif self.fuse_head and self._head_fwd_grads and gscale == self.head_gscale:
             C.head_grad_finalize(self.head_gpart, self.M, hgw, hgb)  # partials came with the forward
             last.bwd_rows = C.head_partial_blocks(self.M)
             head_gscale = gscale

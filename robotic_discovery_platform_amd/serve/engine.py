@@ -140,16 +140,26 @@ def _logit(p: float) -> float:
 RESP_PNG_LEVEL, RESP_PNG_BANDS = 1, 8
 
 
+def _check_mask_class(n_classes: int, mask_class: int):
+    """A K-class model serves the mask of one class: it must be one of 0..K-1 (one-class models ignore it)."""
+    if n_classes > 1 and not 0 <= int(mask_class) < n_classes:
+        raise ValueError(f"mask_class {mask_class} outside 0..{n_classes - 1} for a {n_classes}-class model")
+
+
 class FramePipeline:
     """One static-shape (H, W) per-frame program on its own HIP stream (GPU, native kernels)."""
 
     def __init__(self, model, K: np.ndarray, depth_scale: float, H: int = 480, W: int = 640, size: int = 256,
                  threshold: float = 0.5, graph: bool = True, geo_cfg: Optional[GeometryConfig] = None,
                  device: Optional[torch.device] = None, rgb: bool = False, jpeg: bool = False,
-                 jpeg_entropy: Optional[str] = None):
+                 jpeg_entropy: Optional[str] = None, mask_class: int = 1):
+        """``threshold``: one-class models (``sigmoid(logit) > threshold``). ``mask_class``: K-class models
+        (``n_classes > 1``): the mask is the pixels whose arg-max class it is; ``threshold`` is not used."""
         from ..models.unet import UNetNative
         if not isinstance(model, UNetNative):
             raise TypeError("FramePipeline needs the native UNet (UNetNative); use CpuFramePipeline otherwise")
+        _check_mask_class(model.n_classes, mask_class)
+        self.mask_class = int(mask_class)
         dev = _norm_device(device if device is not None else model.store.device)
         if dev != _norm_device(model.store.device):
             raise ValueError(f"FramePipeline on {dev} for a model on {model.store.device}: replicate it first")
@@ -171,7 +181,7 @@ class FramePipeline:
         self.thr_logit = _logit(threshold)
         self.cfg = geo_cfg or GeometryConfig()
         self.stream = torch.cuda.Stream(dev)
-        self.ex = UNetExecutor(model, 1, size, size, False, "bce", 1.0)
+        self.ex = UNetExecutor(model, 1, size, size, False, "ce" if model.n_classes > 1 else "bce", 1.0)
         # AA resize tables (device)
         ys, yn, yw = aa_tables(H, size)
         xs, xn, xw = aa_tables(W, size)
@@ -280,6 +290,11 @@ class FramePipeline:
                                self.scan_status, self.subseq_bits)
             C.jpeg_to_rgb(self.d_coef, self.d_smeta[:32], self.d_smeta[32:], self.d_planes, self.d_color)
         C.preprocess(self.d_color, *self.tab, ex.x_in, int(src != SRC_BGR))
+        if m.n_classes > 1:  # K-class model: arg-max class == mask_class (the separate headk_mask launch)
+            ex.forward(head=False, refresh_eval=False,
+                       mask_head=(m.store.flat_slice("outc.conv.weight"), m.store.view("outc.conv.bias"),
+                                  self.mask_class, self.m256))
+            return
         # BN-fold coefficients: see refresh_weights(); the head (+ threshold) is fused into the last conv
         ex.forward(head=False, refresh_eval=False,
                    mask_head=(m.store.view("outc.conv.weight").reshape(-1), m.store.view("outc.conv.bias"),
@@ -523,6 +538,8 @@ class BatchEngine:
                  geo_cfg: Optional[GeometryConfig] = None, device: Optional[torch.device] = None, src: int = SRC_JPEG,
                  frames: Optional[int] = None, positions: int = 4, window_us: float = 300.0,
                  lanes: Optional[int] = None):
+        if model.n_classes != 1:
+            raise NotImplementedError("BatchEngine serves one-class models (a K-class model keeps per-stream pipelines)")
         dev = _norm_device(device if device is not None else model.store.device)
         if lanes is None:
             lanes = int(os.environ.get("RDP_BATCH_LANES", "1"))
@@ -961,9 +978,13 @@ class CpuFramePipeline:
     """Same contract on the CPU: torch (any UNet module) + numpy geometry + native C++ spline."""
 
     def __init__(self, model, K, depth_scale, H: int = 480, W: int = 640, size: int = 256, threshold: float = 0.5,
-                 geo_cfg: Optional[GeometryConfig] = None, **_):
+                 geo_cfg: Optional[GeometryConfig] = None, mask_class: int = 1, **_):
         self.model, self.K, self.scale = model, np.asarray(K, np.float64), float(depth_scale)
         self.H, self.W, self.S, self.thr = H, W, size, threshold
+        # K-class models: the mask is arg-max == mask_class (checked against the model's class count when
+        # it is known here, else against the output's on the first frame); one-class models ignore it
+        self.mask_class = int(mask_class)
+        _check_mask_class(int(getattr(model, "n_classes", 1)), self.mask_class)
         self.cfg = geo_cfg or GeometryConfig()
         self.lock = threading.Lock()
         self._pending = None
@@ -1012,7 +1033,11 @@ class CpuFramePipeline:
         x = F.interpolate(rgb[None], size=(self.S, self.S), mode="bilinear", align_corners=False, antialias=True)
         with torch.no_grad():
             out = self.model(x.to(next(self.model.parameters()).device))
-        m = (torch.sigmoid(out.float()) > self.thr)[0, 0].cpu().numpy().astype(np.uint8)
+        if out.shape[1] > 1:  # K-class model: the pixels whose arg-max class is mask_class
+            _check_mask_class(out.shape[1], self.mask_class)
+            m = (out.float().argmax(1) == self.mask_class)[0].cpu().numpy().astype(np.uint8)
+        else:
+            m = (torch.sigmoid(out.float()) > self.thr)[0, 0].cpu().numpy().astype(np.uint8)
         mask = resize_nearest(m, (color_bgr.shape[1], color_bgr.shape[0]))
         t1 = time.perf_counter()
         res = compute_curvature_profile(mask, depth, self.K, self.scale, self.cfg, device="cpu")
@@ -1070,12 +1095,15 @@ class EnginePool:
     def __init__(self, model, K, depth_scale, H: int = 480, W: int = 640, size: int = 256, n: int = 2,
                  threshold: float = 0.5, graph: bool = True, geo_cfg: Optional[GeometryConfig] = None,
                  devices=None, rgb: bool = False, jpeg: bool = False, max_sizes: int = 3, batch: Optional[int] = None,
-                 jpeg_entropy: Optional[str] = None):
+                 jpeg_entropy: Optional[str] = None, mask_class: int = 1):
         self.model = model
         self.home_size = (H, W)
         self.max_sizes = max(0, max_sizes)
         self.rgb = rgb  # channel order of the frames this pool will be fed (graphs captured for it)
-        self.args = dict(K=K, depth_scale=depth_scale, size=size, threshold=threshold, geo_cfg=geo_cfg)
+        # mask_class: the served class of a K-class model (ServeConfig.mask_class; one-class models ignore it)
+        self.args = dict(K=K, depth_scale=depth_scale, size=size, threshold=threshold, geo_cfg=geo_cfg,
+                         mask_class=mask_class)
+        multi = int(getattr(model, "n_classes", 1)) > 1
         self.graph = graph
         self.n = max(1, n)
         self.gpu = _is_native(model)
@@ -1099,12 +1127,14 @@ class EnginePool:
         # a lone stream keeps its double-buffered pipelines (no batching wait on its latency).
         if batch is None:
             batch = int(os.environ.get("RDP_SERVE_BATCH", "4"))
-        self.batch_positions = batch if (self.gpu and graph and batch >= 2) else 0
+        # (BatchEngine is one-class: the streams of a K-class model keep their per-stream pipelines)
+        self.batch_positions = batch if (self.gpu and graph and batch >= 2 and not multi) else 0
         self.batchers = []
         if self.batch_positions:
             src = SRC_JPEG if self.jpeg else (SRC_RGB if rgb else SRC_BGR)
+            bargs = {k: v for k, v in self.args.items() if k != "mask_class"}
             self.batchers = [BatchEngine(self.replicas[r], H=H, W=W, device=self.devices[r], src=src,
-                                         positions=self.batch_positions, **self.args) for r in range(len(self.replicas))]
+                                         positions=self.batch_positions, **bargs) for r in range(len(self.replicas))]
         self._recent = [dict() for _ in self.replicas]  # replica -> {session id: last submit time}
         self.batch_active_s = 0.005
         for r, b in enumerate(self.batchers):

@@ -305,7 +305,8 @@ class NativeTrainer:
 
     def eval_loss(self) -> torch.Tensor:
         """Validation forward (batch statistics are NOT updated: eval-mode BN)."""
-        ev = self.model.executor(self.ex.N, self.ex.H, self.ex.W, training=False)
+        kw = {"loss": "ce"} if self.model.n_classes > 1 else {}  # a K-class model takes "ce" only
+        ev = self.model.executor(self.ex.N, self.ex.H, self.ex.W, training=False, **kw)
         ev.target.copy_(self.ex.target)
         ev.x_in.copy_(self.ex.x_in)
         ev.dice_w = self.ex.dice_w
@@ -349,6 +350,11 @@ class EagerTrainer:
 
     def compute_loss(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         logits = logits.float()
+        if self.loss_kind == "ce":  # K-class logits [N,K,H,W], integer labels [N,H,W] or [N,1,H,W]; 255 = ignore
+            labels = target.long()
+            if labels.dim() == 4:
+                labels = labels.squeeze(1)
+            return nn.functional.cross_entropy(logits, labels, ignore_index=255)
         loss = nn.functional.binary_cross_entropy_with_logits(logits, target)
         if self.loss_kind == "bce_dice":
             p = torch.sigmoid(logits)
