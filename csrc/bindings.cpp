@@ -11,6 +11,7 @@
 #include <dlfcn.h>
 #include <link.h>
 #include <chrono>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -136,6 +137,8 @@ long rdp_png_encode_bound(int, int, int, int);
 int rdp_area_maxtap();
 int rdp_resize_area_u8(const void*, int, int, int, const int*, const int*, const double*, const int*, const int*,
                        const double*, int, int, int, void*, hipStream_t);
+int rdp_batch_augment(const void*, const void*, const int*, const float*, int, int, int, int, void*, float*, void*,
+                      hipStream_t);
 int rdp_geo_spline(const double*, int, int, const int*, const int*, double*, int*, double*, int, double, int, int,
                    double, int, int, const int*, int, double*, double*, int, const void*, void*, long, hipStream_t);
 }
@@ -1657,6 +1660,35 @@ void resize_area_u8(torch::Tensor in, torch::Tensor ys, torch::Tensor yn, torch:
   TORCH_CHECK(r == 0, "resize_area_u8: C must be 1..4");
 }
 
+// Fused batch gather + augmentation (csrc/data_kernels.hip): resident u8 samples idx[0..N) -> the executor's
+// x_in (bf16 NHWC8) and target (fp32: one-class mask values; u8: K-class ids, 255 outside the frame).
+// Runs outside a launch plan, where UNetExecutor.set_input's copies run.
+void batch_augment(torch::Tensor x_res, torch::Tensor y_res, torch::Tensor idx, torch::Tensor params,
+                   torch::Tensor x_out, torch::Tensor target) {
+  TORCH_CHECK(x_res.is_cuda() && x_res.scalar_type() == torch::kUInt8 && x_res.dim() == 4 && x_res.size(3) == 3 &&
+              x_res.is_contiguous(), "batch_augment: x_res u8 [S,H,W,3]");
+  const long S = x_res.size(0), H = x_res.size(1), W = x_res.size(2);
+  TORCH_CHECK(y_res.is_cuda() && y_res.scalar_type() == torch::kUInt8 && y_res.dim() == 3 && y_res.size(0) == S &&
+              y_res.size(1) == H && y_res.size(2) == W && y_res.is_contiguous(), "batch_augment: y_res u8 [S,H,W]");
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt32 && idx.dim() == 1 && idx.is_contiguous(),
+              "batch_augment: idx i32 [N]");
+  const long N = idx.size(0);
+  TORCH_CHECK(params.is_cuda() && params.scalar_type() == torch::kFloat32 && params.dim() == 2 &&
+              params.size(0) == N && params.size(1) == 8 && params.is_contiguous(), "batch_augment: params f32 [N,8]");
+  TORCH_CHECK(x_out.is_cuda() && x_out.scalar_type() == torch::kBFloat16 && x_out.dim() == 4 && x_out.size(0) == N &&
+              x_out.size(1) == H && x_out.size(2) == W && x_out.size(3) == 8 && x_out.is_contiguous() &&
+              (uintptr_t)x_out.data_ptr() % 16 == 0, "batch_augment: x_out bf16 [N,H,W,8], 16-byte aligned");
+  const bool one_class = target.scalar_type() == torch::kFloat32;
+  TORCH_CHECK(target.is_cuda() && (one_class || target.scalar_type() == torch::kUInt8) &&
+              target.numel() == N * H * W && target.is_contiguous(), "batch_augment: target f32 | u8 [N*H*W]");
+  TORCH_CHECK(S >= 1 && N >= 1 && S <= INT_MAX && N <= INT_MAX, "batch_augment: empty batch or resident set");
+  const int r = rdp_batch_augment(x_res.data_ptr(), y_res.data_ptr(), idx.data_ptr<int>(), params.data_ptr<float>(),
+                                  (int)S, (int)N, (int)H, (int)W, x_out.data_ptr(),
+                                  one_class ? target.data_ptr<float>() : nullptr,
+                                  one_class ? nullptr : target.data_ptr(), unplanned_stream());
+  TORCH_CHECK(r == 0, "batch_augment: shape outside the kernel");
+}
+
 // grayscale 8/16-bit PNG -> u8 / int16 (u16 bits) CPU tensor, decoded without the GIL; None when the
 // PNG is not one this reader handles (or is corrupt): the caller falls back to PIL. `parallel`: inflate
 // the bands of a banded stream (codecs.cpp) concurrently (2: only that way, else None -- tests).
@@ -2051,6 +2083,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("png_encode", &png_encode, py::arg("img"), py::arg("level") = 1, py::arg("bands") = 1);
   m.def("resize_area_u8", on_device(&resize_area_u8));
   m.def("area_maxtap", &rdp_area_maxtap);
+  m.def("batch_augment", on_device(&batch_augment));
   m.def("geo_spline_res_len", &rdp_geo_spline_res_len);
   m.def("geo_work_ints", &geo_work_ints);
   m.def("preprocess", on_device(&preprocess), py::arg("bgr"), py::arg("ystart"), py::arg("ysize"), py::arg("yw"),

@@ -72,6 +72,16 @@ class TrainConfig:
     graph: bool = False  # hipGraph-capture the train step (measured slower than eager launches, engine.py)
     model_depth: int = 4  # U-Net levels (reference: 4; the plumbing config uses 2)
     bilinear: bool = True  # decoder: bilinear upsample (reference default) or transposed conv (fixed)
+    # Training augmentation (data/augment.py), off by default: a random flip / rotation / scale / shift about
+    # the image centre and a contrast / brightness jitter per training sample and epoch; validation is never
+    # augmented. The ranges below are read only when ``augment`` is on.
+    augment: bool = False
+    aug_hflip: float = 0.5  # probability of a horizontal flip
+    aug_rotate_deg: float = 15.0  # angle ~ U(-r, r) degrees
+    aug_scale: float = 0.1  # scale ~ U(1 - a, 1 + a)
+    aug_translate: float = 0.05  # shift ~ U(-t, t) of the width / height, per axis
+    aug_contrast: float = 0.1  # gain ~ U(1 - c, 1 + c)
+    aug_brightness: float = 0.1  # bias ~ U(-b, b) on the [0, 1] value scale
 
 
 @dataclass

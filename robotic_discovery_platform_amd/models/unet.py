@@ -787,6 +787,19 @@ class UNetExecutor:
             if target is not None:
                 self.target.copy_(target.reshape(-1))
 
+    def set_input_resident(self, x_res: torch.Tensor, y_res: torch.Tensor, idx, params: torch.Tensor):
+        """The batch ``idx`` [N] of a device-resident u8 dataset (``x_res`` [S,H,W,3], ``y_res`` [S,H,W]),
+        warped by the augmentation rows ``params`` [N,8] (data/augment.py), written into ``x_in`` and
+        ``target`` by ONE kernel (csrc/data_kernels.hip batch_augment): no gathered u8 batch, no fp32 batch,
+        no zero fill. One-class: fp32 mask values; K classes: u8 ids, 255 where the warp leaves the frame.
+        It is issued where :meth:`set_input`'s copies are, on the current stream between steps: the
+        backward's closing side -> main join orders it after the first layer's weight gradient, the last
+        reader of ``x_in``."""
+        from ..data.augment import batch_augment
+        if tuple(x_res.shape[1:3]) != (self.H, self.W):
+            raise ValueError(f"resident samples are {tuple(x_res.shape[1:3])}, the executor is {(self.H, self.W)}")
+        batch_augment(x_res, y_res, idx, params, self.x_in, self.target)
+
     # ------------------------------------------------------------------ forward
     def _conv_bn_relu(self, C, L: _Layer, pool: Optional[torch.Tensor] = None, apply: bool = True,
                       up: Optional[torch.Tensor] = None):

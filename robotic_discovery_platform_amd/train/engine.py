@@ -250,6 +250,11 @@ class NativeTrainer:
     def set_batch(self, x: torch.Tensor, target: torch.Tensor):
         self.ex.set_input(x, target)
 
+    def set_batch_resident(self, x_res: torch.Tensor, y_res: torch.Tensor, idx, params: torch.Tensor):
+        """The next batch straight from a device-resident u8 dataset, gathered and augmented by one kernel
+        (``UNetExecutor.set_input_resident``); like :meth:`set_batch` it runs between steps, outside the plan."""
+        self.ex.set_input_resident(x_res, y_res, idx, params)
+
     def step(self) -> torch.Tensor:
         """One training step on the current input buffers; returns the (device) loss tensor."""
         if self.use_plan:

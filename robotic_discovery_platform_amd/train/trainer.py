@@ -13,7 +13,9 @@ Mirrors ``/root/reference/scripts/train_segmenter.py:103-210`` step by step:
 MI355X-native differences: the step runs on the HIP kernels (hipGraph-captured on one GPU), the
 loss is accumulated on device and read once per epoch (the reference syncs with ``.item()`` every
 step), DDP over RCCL with rank-0-only store writes, and a full resume checkpoint
-(model + Adam state + epoch + best val + RNG) beside the best-only one.
+(model + Adam state + epoch + best val + RNG) beside the best-only one. Optional augmentation
+(``augment``, off by default; the reference has none): per-sample flip / rotate / scale / shift and
+contrast / brightness jitter, fused into the batch gather on the native backend (data/augment.py).
 """
 from __future__ import annotations
 
@@ -73,6 +75,13 @@ class _NativeRunner:
     def train_step(self, x, y) -> torch.Tensor:
         tr = self._get(x.shape[0], x.shape[2], x.shape[3])
         tr.set_batch(x, y)
+        return tr.step()[0]
+
+    def train_step_resident(self, x_res, y_res, idx, params) -> torch.Tensor:
+        """A step on the samples ``idx`` of the device-resident u8 dataset, gathered and augmented by one
+        kernel straight into the executor's buffers (``idx`` / ``params``: device views of the epoch's)."""
+        tr = self._get(idx.shape[0], x_res.shape[1], x_res.shape[2])
+        tr.set_batch_resident(x_res, y_res, idx, params)
         return tr.step()[0]
 
     def eval_loss(self, x, y) -> torch.Tensor:
@@ -159,7 +168,9 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
         mlstore.log_params({"learning_rate": cfg.learning_rate, "batch_size": cfg.batch_size, "epochs": cfg.epochs,
                             "validation_split": cfg.validation_split, "image_size": cfg.image_size,
                             "device": str(dev), "architecture": "UNet", "backend": backend, "world_size": world,
-                            "loss": cfg.loss, "dtype": cfg.dtype})
+                            "loss": cfg.loss, "dtype": cfg.dtype, "augment": cfg.augment})
+        if cfg.augment:
+            mlstore.log_params({k: v for k, v in asdict(cfg).items() if k.startswith("aug_")})
 
     # ---- data ----
     # GPU: the processed dataset is built once on the device (u8 NHWC; INTER_AREA / nearest resizes
@@ -203,6 +214,15 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
         torch.set_rng_state(state["rng_cpu"])
         log.info("Resumed from epoch %d (best val %.4f)", start_epoch, best_val)
 
+    # augmentation (off by default: nothing below changes a step then). Native backend on device-resident
+    # data: the fused gather kernel; any other path: the plain-torch reference on the float batch.
+    aug_spec, fused_aug = None, False
+    if cfg.augment:
+        from ..data.augment import (AugmentSpec, augment_batch_reference, device_order, draw_params,
+                                    epoch_generator)
+        aug_spec = AugmentSpec.from_config(cfg)
+        fused_aug = backend == "native" and device_data
+
     history = []
     from ..utils.launch import maybe_crash
     for epoch in range(start_epoch, cfg.epochs):
@@ -212,9 +232,28 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
         order = torch.tensor(list(iter(sampler)), dtype=torch.long)
         tl = torch.zeros((), device=dev)
         nb = 0
-        for xb, yb in _batches(xtr, ytr, order, cfg.batch_size, dev):
-            tl += runner.train_step(xb, yb).float()
-            nb += 1
+        if aug_spec is not None:
+            # one transform per sample of this rank's order, from a generator that is a function of
+            # (seed, epoch, rank) alone: a resumed run draws the same epoch again
+            params = draw_params(aug_spec, len(order), cfg.image_size, cfg.image_size,
+                                 epoch_generator(cfg.seed, epoch, rank))
+        if aug_spec is not None and fused_aug:
+            # order and transforms go up once per epoch; each step hands views of them to the one kernel
+            # that gathers, warps and writes the executor's input and target (no per-step H2D copy)
+            idx_dev, params_dev = device_order(order, len(xtr), dev), params.to(dev)
+            for i in range(0, len(order), cfg.batch_size):
+                sl = slice(i, i + cfg.batch_size)
+                tl += runner.train_step_resident(xtr, ytr, idx_dev[sl], params_dev[sl]).float()
+                nb += 1
+        elif aug_spec is not None:
+            for xb, yb in _batches(xtr, ytr, order, cfg.batch_size, dev):
+                xb, yb = augment_batch_reference(xb, yb, params[nb * cfg.batch_size:(nb + 1) * cfg.batch_size])
+                tl += runner.train_step(xb, yb).float()
+                nb += 1
+        else:
+            for xb, yb in _batches(xtr, ytr, order, cfg.batch_size, dev):
+                tl += runner.train_step(xb, yb).float()
+                nb += 1
         if dev.type == "cuda":
             torch.cuda.synchronize(dev)
         t_train = time.time() - t0
