@@ -245,8 +245,9 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const WgradArgs a) {
 // FLOP per staged byte at BN = 64, 3.4x at BN = 128).
 //
 // Block = BN/16 waves; wave w owns input channels 16*(w&3) .. +15 of the chunk for all 9 taps and
-// output channels 64*(w>>2) .. +63: 9 x 4 MFMA 16x16x32 accumulators (144 VGPRs), A fragments by
-// ds_read_b64_tr_b16 from the shifted windows, B fragments from the dY tile (same LDS image and
+// output channels 64*(w>>2) .. +63: 9 x 4 MFMA 16x16x32 accumulators (144 VGPRs), A fragments of the
+// three column shifts formed in registers from one 12-pixel window per (region, half step) read by
+// ds_read_b64_tr_b16 (wgrad_win_step below), B fragments from the dY tile (same LDS image and
 // swizzle as the generic kernel). Split-K over row segments into the same fp32 slab format, reduced
 // by wgrad_reduce_kernel.
 struct WgradHaloArgs {
@@ -264,9 +265,140 @@ struct WgradHaloArgs {
   uint32_t fw_m, fw_s, fh_m, fh_s;
 };
 
-// (Measured dead ends, numbers in profiles/dead_ends.md: a staggered two-group schedule and a 3-stage
-// ring of this kernel; ablations: the DMA stream and the MFMA / LDS-read work each take ~70 % of the
-// kernel but barely overlap -- the reason conv_wgrad_pp.hip exists.)
+// ---- fragment reads of one K step (64 pixels), shared by the halo and the ring kernel ----
+//
+// Transposed-read lane geometry (see conv_wgrad_kernel): lane = 16 tg + 4 tq + tpp. One
+// ds_read_b64_tr_b16 whose 16-lane group addresses pixel rows R + tq leaves pixels R .. R + 3 of the
+// lane's channel in the lane, two per dword. The A fragment of column shift sh (tap column ds = sh - 1)
+// is the 8 pixels 32 hf + 8 tg + sh + e, e = 0..7, of a region: the three shifts overlap in all but two
+// pixels, so a (region, half step) is read ONCE as the 12-pixel window 32 hf + 8 tg + 0..11 (three reads,
+// dwords d0..d5) and the shifts are formed in registers: sh 0 = (d0..d3), sh 2 = (d1..d4), sh 1 = the four
+// 16-bit funnel shifts between them (one v_perm_b32 each). Highest row read: 32 + 24 + 3 + 8 = 67 < 72 staged
+// rows; rows >= 66 are zero fill and land only in d5, which no fragment uses.
+//
+// Offsets are hoisted: the swizzle reads pixel-row bits 1 and 3 only, so the half step's 32-row offset is
+// a constant 4 KB and one set of lane offsets serves both halves (immediates).
+struct WgradFragOff {
+  int a[3];     // window groups: rows 8 tg + tq + 0 / 4 / 8 of this wave's 16 input channels
+  int b[2][4];  // dY: rows 8 tg + tq + 0 / 4 of 16-cout group i
+};
+
+RDP_DEV WgradFragOff wgrad_frag_off(int lane, int cf) {
+  const int tg = lane >> 4, tq = (lane >> 2) & 3, tpp = lane & 3;
+  const int ca = 2 * cf + (tpp >> 1);  // 16-B chunk of this lane's A fragment row (input channels)
+  const int q0 = 8 * tg + tq;
+  WgradFragOff o;
+#pragma unroll
+  for (int g = 0; g < 3; ++g) o.a[g] = (q0 + 4 * g) * 128 + 8 * (tpp & 1) + 16 * (ca ^ swz(q0 + 4 * g));
+#pragma unroll
+  for (int g = 0; g < 2; ++g)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      o.b[g][i] = (q0 + 4 * g) * 128 + 8 * (tpp & 1) + 16 * ((2 * i + (tpp >> 1)) ^ swz(q0 + 4 * g));
+  return o;
+}
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+struct WgradWin { u32x2 g[3]; };  // d0..d5: 12 consecutive pixels of one channel
+
+RDP_DEV void wgrad_read_win(WgradWin& w, const char* xb, const WgradFragOff& o) {
+  typedef __attribute__((address_space(3))) bf16x4 lds_v4;
+#pragma unroll
+  for (int g = 0; g < 3; ++g)
+    w.g[g] = __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(xb + o.a[g])));
+}
+
+template <int SH>
+RDP_DEV bf16x8 wgrad_win_frag(const WgradWin& w) {
+  const uint32_t d0 = w.g[0][0], d1 = w.g[0][1], d2 = w.g[1][0], d3 = w.g[1][1], d4 = w.g[2][0];
+  u32x4 f;
+  if (SH == 0) f = u32x4{d0, d1, d2, d3};
+  else if (SH == 2) f = u32x4{d1, d2, d3, d4};
+  else
+    f = u32x4{__builtin_amdgcn_alignbit(d1, d0, 16), __builtin_amdgcn_alignbit(d2, d1, 16),
+              __builtin_amdgcn_alignbit(d3, d2, 16), __builtin_amdgcn_alignbit(d4, d3, 16)};
+  return __builtin_bit_cast(bf16x8, f);
+}
+
+RDP_DEV bf16x8 wgrad_read_b(const char* db, const WgradFragOff& o, int i) {
+  typedef __attribute__((address_space(3))) bf16x4 lds_v4;
+  const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(db + o.b[0][i]));
+  const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(db + o.b[1][i]));
+  return __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// One K step: acc[3 r + sh][i] += window(region r, shift sh)^T x dY[16-cout group i] over both 32-pixel
+// half steps. The six (half step, region) groups are unrolled with two window sets alternating: group
+// g + 1's three reads are issued before group g's 12 MFMAs, and at the half-step boundary (g = 2) each
+// dY fragment of the next half is read into the registers of the one it replaces right after that one's
+// last MFMA (the MFMAs run cout-group-outer for this), so every LDS round trip runs under the matrix
+// cores and the waits in between are counted (LDS returns in order). Only group 0 and the first dY
+// fragments wait for a read that nothing covers, once per K step -- they cannot start before the step
+// barrier, the buffer is still being filled. The sched_barriers pin that order; without them the
+// scheduler sinks every read to its first use. Every accumulator still receives the same products in
+// the same (K step, half step) order as a plain shift-by-shift loop.
+//
+// x0..x2: the three input row regions (dr = -1, 0, +1). zero0 / zero2 (wave-uniform; ring kernel, first /
+// last image row, where the neighbouring ring slot holds another column's row) make the dr = -1 / +1
+// window the zero padding row it stands for. The step stays one basic block that way: with a branch
+// around a region's MFMAs the register allocator no longer keeps each accumulator in place and spills
+// all 144 of them, and the extra MFMAs are 2 / (3 H) of the kernel's.
+// MULTIROW (W < 64): window pixel p + ds of tap ds = -1 / +1 crosses into the neighbouring image row
+// where w = 0 / W - 1; those dY pixels are zero for that tap. This lane holds B rows (pixels)
+// 32 hf + 8 tg + e, e = 0..7 (MFMA 16x16x32 B layout), so the masks touch only e = 0 (low half of
+// dword 0, sh = 0) and e = 7 (high half of dword 3, sh = 2).
+template <bool MULTIROW, bool LEAN = false>
+RDP_DEV void wgrad_win_step(f32x4 (&acc)[9][4], const char* x0, const char* x1, const char* x2, const char* db,
+                            const WgradFragOff& o, bool zero0, bool zero2, int lane, int W) {
+  WgradWin win[2];
+  bf16x8 fb[4];
+  auto read_group = [&](int g) {
+    const int r = g % 3;
+    wgrad_read_win(win[g & 1], (r == 0 ? x0 : r == 1 ? x1 : x2) + (g / 3) * 4096, o);
+  };
+  read_group(0);  // window first, dY fragments in the order of their use: the first MFMAs wait for 5 reads, not 11
+#pragma unroll
+  for (int i = 0; i < 4; ++i) fb[i] = wgrad_read_b(db, o, i);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int g = 0; g < 6; ++g) {
+    const int hf = g / 3, r = g % 3;
+    if (g + 1 < 6) read_group(g + 1);
+    __builtin_amdgcn_sched_barrier(0);
+    const int pl = 32 * hf + 8 * (lane >> 4);
+    uint32_t ml = MULTIROW && (pl & (W - 1)) == 0 ? 0xffff0000u : 0xffffffffu;        // e = 0 has w = 0
+    uint32_t mr = MULTIROW && ((pl + 8) & (W - 1)) == 0 ? 0x0000ffffu : 0xffffffffu;  // e = 7 has w = W - 1
+    // LEAN (no register room, halo<64, MULTIROW>): hide the masks' values from the compiler per group, or it
+    // forms the eight masked copies of the dY fragments once per half step and holds them (32 VGPRs, spills)
+    if (MULTIROW && LEAN) asm volatile("" : "+v"(ml), "+v"(mr));
+    WgradWin w = win[g & 1];
+    if ((r == 0 && zero0) || (r == 2 && zero2)) w.g[0] = w.g[1] = w.g[2] = u32x2{0u, 0u};
+    const bf16x8 fa[3] = {wgrad_win_frag<0>(w), wgrad_win_frag<1>(w), wgrad_win_frag<2>(w)};
+#pragma unroll
+    for (int u = 0; u < 12; ++u) {
+      const int i = u / 3, sh = u % 3;
+      u32x4 b = __builtin_bit_cast(u32x4, fb[i]);
+      if (MULTIROW && sh == 0) b[0] &= ml;
+      if (MULTIROW && sh == 2) b[3] &= mr;
+      acc[3 * r + sh][i] =
+          __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[sh], __builtin_bit_cast(bf16x8, b), acc[3 * r + sh][i], 0, 0, 0);
+      if (g == 2 && sh == 2) {  // last use of this half's fb[i]: the next half's goes out under the remaining MFMAs
+        __builtin_amdgcn_sched_barrier(0);
+        fb[i] = wgrad_read_b(db + 4096, o, i);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// K loop: wait for the staged buffer + barrier, issue the next stage's DMA, then wgrad_win_step above: 34
+// transposed reads (was 52: two per shift) and one full lgkmcnt(0) per K step (was 18, one in front of
+// every 4 MFMAs with the A fragment in a single reused register quad); numbers before / after in
+// profiles/wgrad_frag_pipeline.md. (Measured dead ends, profiles/dead_ends.md: a staggered two-group
+// schedule and a 3-stage ring of this kernel. Its ablations -- 535 us full, 382 without the DMA stream,
+// 381 without the MFMAs, 344 with neither -- put most of the time in the loop skeleton, not in either
+// stream: the exposed fragment-read round trips this loop no longer has were part of it.)
 template <int BN, bool MULTIROW>
 __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_halo_kernel(const WgradHaloArgs a) {
   constexpr int STAGES = 2;
@@ -336,26 +468,8 @@ __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_halo_kernel(const WgradH
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // transposed-read lane geometry (see conv_wgrad_kernel): lane = 16 tg + 4 tq + tpp
-  const int tg = lane >> 4, tq = (lane >> 2) & 3, tpp = lane & 3;
   const int cf = wave & 3, cg = wave >> 2;
-  const int ca = 2 * cf + (tpp >> 1);  // 16-B chunk of this lane's A fragment row (input channels)
-  typedef __attribute__((address_space(3))) bf16x4 lds_v4;
-  // LDS fragment offsets, hoisted: the swizzle reads pixel-row bits 1 and 3 only, so the half step's
-  // 32-row offset (hf) is a constant 4 KB -- one set of lane offsets serves both halves (immediates)
-  const int q0 = 8 * tg + tq;
-  int offB[2][4], offA[2][3];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = 2 * i + (tpp >> 1);
-    offB[0][i] = q0 * 128 + 8 * (tpp & 1) + 16 * (c ^ swz(q0));
-    offB[1][i] = (q0 + 4) * 128 + 8 * (tpp & 1) + 16 * (c ^ swz(q0 + 4));
-  }
-#pragma unroll
-  for (int sh = 0; sh < 3; ++sh) {
-    offA[0][sh] = (q0 + sh) * 128 + 8 * (tpp & 1) + 16 * (ca ^ swz(q0 + sh));
-    offA[1][sh] = (q0 + sh + 4) * 128 + 8 * (tpp & 1) + 16 * (ca ^ swz(q0 + sh + 4));
-  }
+  const WgradFragOff fo = wgrad_frag_off(lane, cf);
 
 #pragma unroll
   for (int st = 0; st < STAGES - 1; ++st)
@@ -366,45 +480,7 @@ __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_halo_kernel(const WgradH
     raw_barrier();
     if (ks + STAGES - 1 < nks) issue(ks + STAGES - 1, smem + ((ks + STAGES - 1) % STAGES) * BUF);
     const char* cur = smem + (ks % STAGES) * BUF;
-    const char* db = cur + 3 * XREG + cg * DSUB;
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      bf16x8 fb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const char* dbi = db + hf * 4096;
-        const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(dbi + offB[0][i]));
-        const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(dbi + offB[1][i]));
-        fb[i] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-      }
-      // multi-row segments (W < 64): window pixel p + ds of tap ds = -1 / +1 crosses into the
-      // neighbouring image row where w = 0 / W - 1; zero those dY pixels for that tap. This lane
-      // holds B rows (pixels) 32 hf + 8 (lane >> 4) + e, e = 0..7 (MFMA 16x16x32 B layout).
-      const int pl = 32 * hf + 8 * (lane >> 4);
-      const bool mL = MULTIROW && (pl & (a.W - 1)) == 0;      // e = 0 has w = 0
-      const bool mR = MULTIROW && ((pl + 8) & (a.W - 1)) == 0;  // e = 7 has w = W - 1
-#pragma unroll
-      for (int sh = 0; sh < 3; ++sh) {  // ds + 1: window row shift
-        bf16x8 fbs[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          fbs[i] = fb[i];
-          if (MULTIROW && sh == 0) fbs[i][0] = mL ? (short)0 : fb[i][0];
-          if (MULTIROW && sh == 2) fbs[i][7] = mR ? (short)0 : fb[i][7];
-        }
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {  // dr + 1: input row region
-          const char* xb = cur + r * XREG + hf * 4096;
-          const bf16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(xb + offA[0][sh]));
-          const bf16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(xb + offA[1][sh]));
-          const bf16x8 fa = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-          const int tap = r * 3 + sh;
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            acc[tap][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fbs[i], acc[tap][i], 0, 0, 0);
-        }
-      }
-    }
+    wgrad_win_step<MULTIROW, MULTIROW && BN == 64>(acc, cur, cur + XREG, cur + 2 * XREG, cur + 3 * XREG + cg * DSUB, fo, false, false, lane, a.W);
   }
 
   // acc[tap][i][r]: cin = cin0 + 16 cf + 4 (lane >> 4) + r, cout = cout0 + 64 cg + 16 i + (lane & 15)
@@ -433,8 +509,8 @@ __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_halo_kernel(const WgradH
 // stages ONE new input row region (9 KB) plus its dY tile instead of three regions: half the DMA
 // bytes of conv_wgrad_halo_kernel at BN = 64. Input rows live in a 5-slot ring (slot = P % 5), dY
 // in a 3-slot ring; two steps stay in flight across the per-step barrier (counted vmcnt). At a
-// column's first / last row the dr = -1 / +1 taps are skipped (the neighbouring ring slot holds
-// another column's row: that is the zero padding row of this one).
+// column's first / last row the dr = -1 / +1 window is zeroed in registers (the neighbouring ring slot
+// holds another column's row: that is the zero padding row of this one).
 struct WgradRingArgs {
   const u16* x1;
   const u16* x2;
@@ -525,10 +601,8 @@ __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_ring_kernel(const WgradR
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int tg = lane >> 4, tq = (lane >> 2) & 3, tpp = lane & 3;
   const int cf = wave & 3, cg = wave >> 2;
-  const int ca = 2 * cf + (tpp >> 1);
-  typedef __attribute__((address_space(3))) bf16x4 lds_v4;
+  const WgradFragOff fo = wgrad_frag_off(lane, cf);
 
   // prologue: rows P0 - 1, P0 (x only), then steps 0 and 1 (row P + 1 and dY P)
   if (nks > 0) {
@@ -548,40 +622,11 @@ __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_ring_kernel(const WgradR
     int m0, h, w0;
     locate(P, m0, h, w0);
     const bool top = h == 0, bottom = h == a.H - 1;
+    const char* x0 = xring + ((P - 1 + NX) % NX) * XREG;
+    const char* x1 = xring + ((P + NX) % NX) * XREG;
+    const char* x2 = xring + ((P + 1 + NX) % NX) * XREG;
     const char* db = dring + ((ks % ND) * DT) + cg * DSUB;
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int p0 = 32 * hf + 8 * tg + tq;
-      bf16x8 fb[4];
-      {
-        const int sw0 = swz(p0), sw1 = swz(p0 + 4);
-        const int ro0 = p0 * 128 + 8 * (tpp & 1), ro1 = ro0 + 4 * 128;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int c = 2 * i + (tpp >> 1);
-          const bf16x4 b0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(db + ro0 + 16 * (c ^ sw0)));
-          const bf16x4 b1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(db + ro1 + 16 * (c ^ sw1)));
-          fb[i] = __builtin_shufflevector(b0, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-        }
-      }
-#pragma unroll
-      for (int sh = 0; sh < 3; ++sh) {
-        const int pa = p0 + sh, pb = p0 + sh + 4;
-        const int oa = pa * 128 + 8 * (tpp & 1) + 16 * (ca ^ swz(pa));
-        const int ob = pb * 128 + 8 * (tpp & 1) + 16 * (ca ^ swz(pb));
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          if ((r == 0 && top) || (r == 2 && bottom)) continue;  // wave-uniform
-          const char* xb = xring + ((P + r - 1 + NX) % NX) * XREG;
-          const bf16x4 a0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(xb + oa));
-          const bf16x4 a1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(xb + ob));
-          const bf16x8 fa = __builtin_shufflevector(a0, a1, 0, 1, 2, 3, 4, 5, 6, 7);
-          const int tap = r * 3 + sh;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc[tap][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa, fb[i], acc[tap][i], 0, 0, 0);
-        }
-      }
-    }
+    wgrad_win_step<false>(acc, x0, x1, x2, db, fo, top, bottom, lane, a.W);
   }
 
   const auto rs = make_rsrc(a.slab, a.slab_bytes);

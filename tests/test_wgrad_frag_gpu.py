@@ -1,0 +1,107 @@
+"""Exact tests of the halo / row-ring weight-gradient kernels' fragment reads (GPU only).
+
+The A fragments of the three column shifts of a 3x3 tap row come from one 12-pixel register window
+(conv_wgrad.hip: wgrad_win_step). A shift that is off by one pixel, or a wrong 16-lane-group boundary,
+moves single pixels between taps, which random data only shows as a small relative error. Here every
+operand is a small integer: x and dY hold integers in [-4, 4] (exact in bf16) over M = N H W <= 1024
+pixels, so every product and every partial sum is an integer below 2^24, fp32 holds it exactly in any
+order of additions, and the result must EQUAL the fp32 reference bit for bit.
+"""
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+# (N, H, W, C1, C2, Cout, variant): one per code path. variant 0 = auto dispatch, 5 = force the halo kernel
+SHAPES = [
+    (2, 3, 64, 64, 0, 64, 5),      # halo<64, false>
+    (1, 4, 128, 64, 64, 128, 0),   # halo<128, false>: dual source, two segments per row
+    (2, 8, 16, 64, 0, 128, 0),     # W = 16 on the auto dispatch
+    (1, 8, 32, 128, 0, 128, 0),    # halo<128, true>
+    (2, 8, 8, 64, 0, 128, 5),      # halo<128, true>, 8 image rows per segment
+    (2, 8, 16, 64, 0, 64, 5),      # halo<64, true>
+    (2, 5, 64, 64, 0, 64, 0),      # ring<64>
+    (1, 3, 128, 64, 64, 64, 0),    # ring<64>: dual source, two columns per image
+    (3, 1, 64, 64, 0, 64, 0),      # ring<64>: top and bottom in one row
+    (2, 8, 16, 64, 0, 128, 5),     # halo<128, true> at W = 16 (the auto dispatch takes W >= 32 only)
+]
+SPLITS = [1, 3, 1000]  # 1000 = more splits than 64-pixel segments (at most 16 here)
+
+
+@pytest.fixture(scope="module")
+def C():
+    from robotic_discovery_platform_amd.ops import native
+    return native()
+
+
+def takes_halo(H, W, variant):
+    return variant == 5 or W % 64 == 0 or (W >= 32 and 64 % W == 0 and (H * W) % 64 == 0)
+
+
+def run_wgrad(C, x1, x2, dy, splits, variant):
+    N, H, W, C1 = x1.shape
+    Cin, Cout = C1 + (x2.shape[3] if x2 is not None else 0), dy.shape[3]
+    # the halo / ring dispatch takes as many splits as the slab holds (up to one resident wave of blocks
+    # and the segment count); the generic kernel takes the argument. One more than the segments is "more
+    # splits than segments" to both, and keeps the slab small.
+    splits = min(splits, N * H * W // 64 + 1)
+    elems = splits * Cout * 9 * Cin if takes_halo(H, W, variant) else C.wgrad_slab_elems(N, H, W, Cin, Cout, 9, 0, splits)
+    slab = torch.zeros(elems, device="cuda")
+    out = torch.full((Cout * 9 * Cin,), 3.0, device="cuda")
+    used = C.conv_wgrad(x1, x2, dy, 9, 0, 0, slab, out, 0, splits, variant)
+    assert 1 <= used <= splits
+    return out.view(Cout, 3, 3, Cin)
+
+
+@functools.lru_cache(maxsize=None)
+def int_case(N, H, W, C1, C2, Cout):
+    """Integer operands and their fp32 torch weight gradient [Cout][kh][kw][Cin], once per shape."""
+    g = torch.Generator(device="cuda").manual_seed(1000 * H + W + C1 + C2 + Cout)
+    x = torch.randint(-4, 5, (N, H, W, C1 + C2), device="cuda", generator=g).float()
+    dy = torch.randint(-4, 5, (N, H, W, Cout), device="cuda", generator=g).float()
+    w = torch.zeros(Cout, C1 + C2, 3, 3, device="cuda", requires_grad=True)
+    F.conv2d(x.permute(0, 3, 1, 2), w, padding=1).backward(dy.permute(0, 3, 1, 2))
+    ref = w.grad.permute(0, 2, 3, 1).contiguous()
+    assert torch.equal(ref, ref.round()) and ref.abs().max() < 2 ** 24
+    x1 = x[..., :C1].to(torch.bfloat16).contiguous()
+    x2 = x[..., C1:].to(torch.bfloat16).contiguous() if C2 else None
+    return x1, x2, dy.to(torch.bfloat16), ref
+
+
+@pytest.mark.parametrize("splits", SPLITS)
+@pytest.mark.parametrize("N,H,W,C1,C2,Cout,variant", SHAPES)
+def test_wgrad_integer_exact(C, N, H, W, C1, C2, Cout, variant, splits):
+    x1, x2, dy, ref = int_case(N, H, W, C1, C2, Cout)
+    out = run_wgrad(C, x1, x2, dy, splits, variant)
+    bad = (out != ref).nonzero()
+    print(f"mismatches {bad.shape[0]} of {ref.numel()}")
+    assert torch.equal(out, ref), f"first mismatch at [cout, kh, kw, cin] = {bad[0].tolist()}: {out[tuple(bad[0])].item()} vs {ref[tuple(bad[0])].item()}"
+
+
+@pytest.mark.parametrize("N,H,W,C1,C2,Cout,variant", SHAPES)
+def test_wgrad_one_hot(C, N, H, W, C1, C2, Cout, variant):
+    """dY = 1 at one pixel and output channel, x[n, h, w, c] = ((7 w + 3 h + c) mod 9) - 4: the weight
+    gradient of that channel is x at the pixel's nine neighbours (0 outside the image), every other
+    channel's is 0 -- a failure names the tap and the pixel."""
+    Cin = C1 + C2
+    h_, w_, c_ = torch.meshgrid(torch.arange(H), torch.arange(W), torch.arange(Cin), indexing="ij")
+    x = (((7 * w_ + 3 * h_ + c_) % 9) - 4).float().cuda().expand(N, H, W, Cin)
+    xpad = F.pad(x, (0, 0, 1, 1, 1, 1))  # [N][H + 2][W + 2][Cin]
+    x1 = x[..., :C1].to(torch.bfloat16).contiguous()
+    x2 = x[..., C1:].to(torch.bfloat16).contiguous() if C2 else None
+    n0 = N - 1
+    for h0 in sorted({0, H // 2, H - 1}):
+        for w0 in [w for w in (0, 1, 7, 8, 31, 32, 62, 63) if w < W]:
+            co = (5 * w0 + h0) % Cout
+            dy = torch.zeros(N, H, W, Cout, dtype=torch.bfloat16, device="cuda")
+            dy[n0, h0, w0, co] = 1
+            out = run_wgrad(C, x1, x2, dy, 3, variant)
+            ref = torch.zeros_like(out)
+            ref[co] = xpad[n0, h0:h0 + 3, w0:w0 + 3]
+            if not torch.equal(out, ref):
+                o, kh, kw, ci = (out != ref).nonzero()[0].tolist()
+                pytest.fail(f"dY at (h, w) = ({h0}, {w0}), cout {co}: tap (kh, kw) = ({kh}, {kw}) cin {ci} of cout {o} "
+                            f"is {out[o, kh, kw, ci].item()}, expected {ref[o, kh, kw, ci].item()}")
