@@ -1,0 +1,653 @@
+"""Integer-lattice inputs, fp64 references and the case tables of the exact conv tests.
+
+Every MFMA kernel here multiplies bf16 operands and accumulates in fp32. For integer-valued operands
+whose partial sums stay below 2^24 every summation order gives the same exact integer, so a kernel's
+bf16 output is one fixed value: that integer rounded to nearest even. The GPU tests
+(tests/test_conv_exact_gpu.py) therefore demand bitwise equality with a CPU fp64 reference; this module
+builds the inputs and references and states the preconditions under which that demand is sound.
+tests/test_lattice_cpu.py checks, without a GPU, that every case of the tables meets them.
+
+Pure torch on the CPU: the native extension is never imported here.
+"""
+import functools
+import math
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import torch
+import torch.nn.functional as F
+
+BF16 = torch.bfloat16
+SENTINEL = 30080.0   # exact in bf16, far outside every expected output
+F32_EXACT = float(1 << 24)
+
+
+# ---------------------------------------------------------------------------------------------
+# inputs
+# ---------------------------------------------------------------------------------------------
+
+def generator(seed: int) -> torch.Generator:
+    g = torch.Generator()
+    g.manual_seed(seed)
+    return g
+
+
+def ternary(shape, density: float, gen: torch.Generator) -> torch.Tensor:
+    """bf16 tensor with values in {-1, 0, 1}; P(non-zero) = density."""
+    shape = tuple(shape)
+    nz = torch.rand(shape, generator=gen) < density
+    sign = torch.randint(0, 2, shape, generator=gen) * 2 - 1
+    return (nz * sign).to(BF16)
+
+
+def small_ints(shape, gen: torch.Generator, amax: int = 3) -> torch.Tensor:
+    """bf16 tensor of uniform integers in -amax..amax (the rounding class' wider form)."""
+    return torch.randint(-amax, amax + 1, tuple(shape), generator=gen).to(BF16)
+
+
+def densities(K: int, target: float = 100.0) -> Tuple[float, float]:
+    """(p, q) with p * q ~ target / K: the output's variance is ~target (sigma ~ 10) whatever K is."""
+    p = min(1.0, math.sqrt(target / K))
+    return p, p
+
+
+def pow2_signed(n: int, gen: torch.Generator, kmin: int = -2, kmax: int = 1) -> torch.Tensor:
+    """fp32 vector of +-2^k, k in kmin..kmax, both signs present."""
+    k = torch.randint(kmin, kmax + 1, (n,), generator=gen)
+    s = torch.randint(0, 2, (n,), generator=gen) * 2 - 1
+    s[0], s[1] = 1, -1
+    return (s * torch.pow(2.0, k.double())).float()
+
+
+def int_vector(n: int, gen: torch.Generator, amax: int) -> torch.Tensor:
+    return torch.randint(-amax, amax + 1, (n,), generator=gen).float()
+
+
+# ---------------------------------------------------------------------------------------------
+# layouts
+# ---------------------------------------------------------------------------------------------
+
+def ohwi(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, kh, kw] -> [Cout, kh * kw * Cin], the forward kernels' weight layout."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
+
+
+def dgrad_weight(w: torch.Tensor) -> torch.Tensor:
+    """[Cout, Cin, 3, 3] -> [Cin, 9 * Cout]: dX = conv(dY, flip(W)^T) through the forward kernels."""
+    return w.flip(2, 3).permute(1, 2, 3, 0).reshape(w.shape[1], -1).contiguous()
+
+
+def pack_first(x3: torch.Tensor, w: torch.Tensor):
+    """The packed first layer: x [N,H,W,3] -> 8 stored channels, w [64,3,3,3] -> [64][16 taps][8] = [64][128]."""
+    x8 = torch.zeros(*x3.shape[:3], 8, dtype=BF16)
+    x8[..., :3] = x3
+    wp = torch.zeros(w.shape[0], 16, 8, dtype=BF16)
+    wp[:, :9, :3] = w.permute(0, 2, 3, 1).reshape(w.shape[0], 9, 3)
+    return x8, wp.view(w.shape[0], 128)
+
+
+# ---------------------------------------------------------------------------------------------
+# fp64 references (CPU only: integer sums below 2^53 are exact in every order)
+# ---------------------------------------------------------------------------------------------
+
+def conv_ref(x_nhwc: torch.Tensor, w_oihw: torch.Tensor) -> torch.Tensor:
+    """fp64 'same' conv of an NHWC tensor, NHWC result."""
+    pad = w_oihw.shape[-1] // 2
+    y = F.conv2d(x_nhwc.double().permute(0, 3, 1, 2), w_oihw.double(), padding=pad)
+    return y.permute(0, 2, 3, 1).contiguous()
+
+
+def conv_grads_ref(x_nhwc: torch.Tensor, w_oihw: torch.Tensor, dy_nhwc: torch.Tensor, want_x: bool, want_w: bool):
+    """fp64 autograd gradients of the 'same' conv: (dx NHWC or None, dw [Cout, Cin, kh, kw] or None)."""
+    x = x_nhwc.double().permute(0, 3, 1, 2).requires_grad_(want_x)
+    w = w_oihw.double().clone().requires_grad_(want_w)
+    y = F.conv2d(x, w, padding=w.shape[-1] // 2)
+    y.backward(dy_nhwc.double().permute(0, 3, 1, 2))
+    dx = x.grad.permute(0, 2, 3, 1).contiguous() if want_x else None
+    return dx, (w.grad if want_w else None)
+
+
+def expected_bf16(ref64: torch.Tensor) -> torch.Tensor:
+    """The one bf16 value a correct kernel can write: exact in fp32 below 2^24, then RNE to bf16."""
+    return ref64.to(torch.float32).to(BF16)
+
+
+# ---------------------------------------------------------------------------------------------
+# preconditions: asserted on the reference alone. A case that violates one is a broken case.
+# ---------------------------------------------------------------------------------------------
+
+def assert_exact_class(ref64: torch.Tensor) -> None:
+    """max|y| <= 256 (integers: no bf16 rounding) and per-channel sum(y^2) < 2^24 over the whole tensor,
+    which bounds every partial sum of y or y^2 any tiling can form. Channels are the last dim."""
+    assert torch.equal(ref64, ref64.round()), "reference is not integer-valued"
+    amax = ref64.abs().max().item()
+    assert amax <= 256, f"exact class: max|y| = {amax} > 256"
+    assert amax > 0, "degenerate case: the reference is all zero"
+    ssq = (ref64 * ref64).reshape(-1, ref64.shape[-1]).sum(0).max().item()
+    assert ssq < F32_EXACT, f"exact class: per-channel sum y^2 = {ssq} >= 2^24"
+
+
+def true_ties(ref64: torch.Tensor) -> int:
+    """Odd integers in (256, 512): spacing of bf16 there is 2, so each is a true round-to-even tie."""
+    a = ref64.abs()
+    return int(((a > 256) & (a < 512) & (a % 2 == 1)).sum().item())
+
+
+def assert_rounding_class(ref64: torch.Tensor, min_ties: int = 16) -> None:
+    assert torch.equal(ref64, ref64.round()), "reference is not integer-valued"
+    amax = ref64.abs().max().item()
+    assert amax < F32_EXACT, f"rounding class: max|y| = {amax} >= 2^24"
+    n = true_ties(ref64)
+    assert n >= min_ties, f"rounding class: only {n} true bf16 ties in the reference (need {min_ties})"
+
+
+def assert_f32_sums(terms64: torch.Tensor, what: str) -> None:
+    """Per-channel sum|t| / quantum < 2^24, quantum = the largest power of two dividing every term: then
+    every partial sum of the terms is a multiple of the quantum with < 24 significant bits, exact in fp32."""
+    nz = terms64[terms64 != 0].abs()
+    assert nz.numel() > 0, f"{what}: all terms are zero"
+    q = 1.0
+    while not torch.equal(nz / q, (nz / q).round()):
+        q /= 2.0
+        assert q >= 2.0 ** -16, f"{what}: terms are not dyadic"
+    tot = terms64.abs().reshape(-1, terms64.shape[-1]).sum(0).max().item() / q
+    assert tot < F32_EXACT, f"{what}: per-channel sum|t| / {q} = {tot} >= 2^24"
+
+
+# ---------------------------------------------------------------------------------------------
+# guard-banded, pitch-sliced buffers
+# ---------------------------------------------------------------------------------------------
+
+GUARD = 512  # elements on each side (a multiple of 8: the view stays 16-byte aligned)
+
+
+def embed(t: Optional[torch.Tensor], shape, pad_lo: int, pad_hi: int, device, dtype=BF16, fill=SENTINEL):
+    """A [N,H,W,C] view (pixel pitch pad_lo + C + pad_hi, channel offset pad_lo) inside a flat buffer
+    with GUARD sentinel elements before and after. pad_lo and the pitch must be multiples of 8.
+    Returns (flat, view); the view holds t (or the sentinel if t is None)."""
+    N, H, W, C = shape
+    pitch = pad_lo + C + pad_hi
+    assert pad_lo % 8 == 0 and pitch % 8 == 0
+    flat = torch.full((2 * GUARD + N * H * W * pitch,), fill, dtype=dtype, device=device)
+    view = flat[GUARD:GUARD + N * H * W * pitch].view(N, H, W, pitch)[..., pad_lo:pad_lo + C]
+    if t is not None:
+        view.copy_(t)
+    return flat, view
+
+
+def outside_view_intact(flat: torch.Tensor, view: torch.Tensor, fill=SENTINEL) -> bool:
+    """True if every element of flat that is not part of view still holds the sentinel, bit for bit."""
+    probe = flat.clone()
+    off = view.storage_offset() - flat.storage_offset()
+    probe.as_strided(view.shape, view.stride(), off).fill_(fill)
+    bits = torch.int16 if flat.dtype == BF16 else torch.int32
+    return torch.equal(probe.view(bits), torch.full_like(flat, fill).view(bits))
+
+
+# ---------------------------------------------------------------------------------------------
+# forward / eval / dgrad cases
+# ---------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Conv:
+    """One conv_fwd launch: cat(x1, x2) [N,H,W,C1+C2] -> Cout, forced onto dispatch path `pref`."""
+    name: str
+    N: int
+    H: int
+    W: int
+    C1: int
+    C2: int
+    Cout: int
+    pref: int
+    taps: int = 9
+    packed: bool = False     # first layer: 3 real channels stored as 8, C1 = 8
+    cls: str = "exact"       # "exact" | "round"
+    stats: bool = True       # exact class only
+    split: int = 0           # > 0: two destinations y1 [.., split] | y2 [.., Cout - split]
+    views: bool = False      # pitch-sliced inputs / outputs inside guard bands
+    ws: bool = False         # split-K workspace of conv_ws_elems (must be > 0), NaN-filled
+    evalmode: bool = False   # affine = +-2^k scales, integer shifts, ReLU
+    pool: bool = False       # eval: fused 2x2 max pool output
+    wfrag: int = 0           # eval through the fragment-major weight copy: expected rowband_frag_mode
+    amax: int = 3            # rounding class: operand range -amax..amax
+    seed: int = 0
+
+    @property
+    def K(self) -> int:
+        return 27 if self.packed else self.taps * (self.C1 + self.C2)
+
+    @property
+    def M(self) -> int:
+        return self.N * self.H * self.W
+
+
+def _c(name, shape, pref, **kw):
+    return Conv(name, *shape, pref, **kw)
+
+
+S_TINY = (3, 7, 5, 64, 0, 64)          # M = 105: one ragged tile, odd H / W, N > 1
+S_DUAL = (2, 9, 13, 64, 64, 128)       # M = 234: ragged, odd, two sources
+S_PP = (3, 37, 29, 128, 0, 256)        # M = 3219: 13 tiles of 256, ragged last
+S_PPD = (1, 24, 40, 128, 128, 256)     # ping-pong, two sources
+S_SK7 = (5, 37, 29, 256, 0, 512)       # M = 5365: split-K ping-pong 256 x 128, ragged
+S_SK8 = (4, 32, 32, 512, 0, 512)       # split-K ping-pong 256 x 256
+S_FIRST = (1, 7, 9, 8, 0, 64)
+S_FIRST2 = (2, 20, 12, 8, 0, 64)
+
+FWD_CASES = [
+    # implicit GEMM, 4- and 8-wave tiles, auto
+    _c("auto-256x64", S_TINY, 0),
+    _c("auto-128x128", S_DUAL, 0),
+    _c("tile128-split-views", S_DUAL, 128, split=64, views=True),
+    _c("tile256", S_TINY, 256),
+    _c("wave8-128", S_DUAL, 2),
+    _c("wave8-256-views", S_TINY, 3, views=True),
+    _c("tile128-round", S_DUAL, 128, cls="round", stats=False),
+    # ping-pong
+    _c("pp256", S_PP, 4),
+    _c("pp128-split-views", S_PPD, 5, split=128, views=True),
+    _c("pp256-round", S_PP, 4, cls="round", stats=False),
+    # split-K ping-pong (NaN-filled workspace)
+    _c("ppsk128", S_SK7, 7, ws=True),
+    _c("ppsk256-split", S_SK8, 8, ws=True, split=256),
+    _c("ppsk128-views", (4, 32, 32, 256, 0, 512), 7, ws=True, views=True),
+    _c("ppsk128-round", S_SK7, 7, ws=True, cls="round", stats=False),
+    # auto split-K of the implicit GEMM (small M, long K)
+    _c("splitk-auto", (2, 7, 9, 128, 0, 64), 0, ws=True),
+    _c("splitk-auto-dual-split", (1, 8, 8, 256, 256, 256), 0, ws=True, split=128),
+    _c("splitk-auto-round", (1, 8, 8, 256, 256, 256), 0, ws=True, cls="round", stats=False),
+    # halo tiles 16 x 16, 64 x 4, 32 x 8
+    _c("halo16", (3, 16, 16, 64, 0, 128), 1),
+    _c("halo64-dual-views", (1, 8, 128, 64, 64, 128), 1, views=True),
+    _c("halo32", (2, 16, 32, 128, 0, 64), 1),
+    _c("halo16-round", (3, 16, 16, 64, 0, 128), 1, cls="round", stats=False),
+    # row ring, 64 -> 64 and 64 -> 128 (two destinations)
+    _c("ring-3seg", (3, 2, 192, 64, 0, 64), 6),
+    _c("ring-views", (2, 6, 64, 64, 0, 64), 6, views=True),
+    _c("ring-cout128-split", (2, 2, 64, 64, 0, 128), 6, split=64),
+    _c("ring-round", (2, 6, 64, 64, 0, 64), 6, cls="round", stats=False),
+    # two-source ring, 128 -> 64 (pref 14) and 128 -> 128 as halves (pref 15)
+    _c("ring2-concat", (3, 2, 192, 64, 64, 64), 14),
+    _c("ring2-one128-views", (2, 6, 64, 128, 0, 64), 14, views=True),
+    _c("ring2x2-concat", (1, 6, 64, 64, 64, 128), 15),
+    _c("ring2x2-one128-views", (2, 8, 128, 128, 0, 128), 15, views=True),
+    _c("ring2-round", (2, 6, 64, 128, 0, 64), 14, cls="round", stats=False),
+    # first layer, packed (K = 27: the rounding case needs operands in -7..7 to reach 256)
+    _c("first", S_FIRST, 13, packed=True),
+    _c("first-views", S_FIRST2, 13, packed=True, views=True),
+    _c("first-round", S_FIRST2, 13, packed=True, cls="round", stats=False, amax=7),
+    # taps = 1 (the transposed decoder's GEMMs)
+    _c("taps1-auto", (1, 4, 5, 256, 0, 512), 0, taps=1),
+    _c("taps1-pp128", (3, 20, 52, 256, 0, 512), 5, taps=1, stats=False),
+]
+
+EVAL_CASES = [
+    _c("eval-tile128", S_DUAL, 128, evalmode=True, stats=False),
+    _c("eval-splitk-auto-pool", (1, 8, 8, 256, 256, 256), 0, ws=True, evalmode=True, pool=True, stats=False),
+    _c("eval-ppsk256-pool", S_SK8, 8, ws=True, evalmode=True, pool=True, stats=False),
+    _c("eval-halo64-views", (1, 8, 128, 64, 64, 128), 1, evalmode=True, views=True, stats=False),
+    _c("eval-ring-pool", (2, 6, 64, 64, 0, 64), 6, evalmode=True, pool=True, stats=False),
+    _c("eval-ring2", (2, 6, 64, 128, 0, 64), 14, evalmode=True, stats=False),
+    _c("eval-ring2x2", (1, 6, 64, 64, 64, 128), 15, evalmode=True, stats=False),
+    _c("eval-first", S_FIRST, 13, packed=True, evalmode=True, stats=False),
+    # row band (eval only), forced and through the fragment-major weights
+    _c("rowband-dual", (3, 16, 32, 64, 64, 96), 16, evalmode=True, stats=False),
+    _c("rowband-pool-views", (2, 16, 16, 256, 256, 128), 16, evalmode=True, pool=True, views=True, stats=False),
+    _c("rowband-round", (3, 16, 32, 64, 64, 96), 16, evalmode=True, cls="round", stats=False),
+    _c("wfrag-mode1", (1, 16, 16, 64, 0, 64), 0, evalmode=True, wfrag=1, stats=False),
+    _c("wfrag-mode2-pool", (1, 16, 16, 256, 0, 128), 0, evalmode=True, wfrag=2, pool=True, stats=False),
+]
+
+
+@functools.lru_cache(maxsize=6)
+def _conv_data(N, H, W, C1, C2, Cout, taps, packed, cls, amax, seed, cout_limit):
+    g = generator(1000 + seed)
+    co = Cout if cout_limit is None else min(Cout, cout_limit)
+    k = 3 if taps == 9 else 1
+    cin = 3 if packed else C1 + C2
+    K = k * k * cin
+    if cls == "exact":
+        p, q = densities(K)
+        x = ternary((N, H, W, cin), p, g)
+        w = ternary((Cout, cin, k, k), q, g)
+    else:
+        x = small_ints((N, H, W, cin), g, amax)
+        w = small_ints((Cout, cin, k, k), g, amax)
+    ref = conv_ref(x, w[:co])
+    return x, w, ref
+
+
+def conv_data(c: Conv, cout_limit: Optional[int] = None):
+    """(x [N,H,W,Cin] bf16, w [Cout,Cin,k,k] bf16, ref [N,H,W,Cout'] fp64). cout_limit (CPU test only)
+    references the first channels alone; the inputs are the same."""
+    return _conv_data(c.N, c.H, c.W, c.C1, c.C2, c.Cout, c.taps, c.packed, c.cls, c.amax, c.seed, cout_limit)
+
+
+def eval_coef(c: Conv):
+    """(scale, shift) fp32: +-2^k and integers, so relu(scale * y + shift) is exact in fp32 whether the
+    kernel fuses the multiply-add or not. The rounding-class row-band case keeps the identity."""
+    g = generator(2000 + c.seed)
+    if c.cls == "round":
+        return torch.ones(c.Cout), torch.zeros(c.Cout)
+    return pow2_signed(c.Cout, g), int_vector(c.Cout, g, 8)
+
+
+def eval_ref(c: Conv, ref64: torch.Tensor) -> torch.Tensor:
+    sc, sh = eval_coef(c)
+    n = ref64.shape[-1]
+    return torch.relu(ref64 * sc[:n].double() + sh[:n].double())
+
+
+def check_conv_case(c: Conv, ref64: torch.Tensor) -> None:
+    """The case's preconditions, on the reference alone."""
+    if c.cls == "exact":
+        assert_exact_class(ref64)
+    else:
+        assert not c.stats
+        assert_rounding_class(ref64)
+    if c.evalmode:
+        e = eval_ref(c, ref64)
+        assert e.abs().max().item() * 4 < F32_EXACT          # multiples of 1/4: exact in fp32
+        assert (e == 0).any() and (e > 0).any()              # ReLU cuts and passes
+        sc, _ = eval_coef(c)
+        if c.cls == "exact":
+            assert (sc > 0).any() and (sc < 0).any()         # ... on both sides
+
+
+@dataclass(frozen=True)
+class Dgrad:
+    """dX [N,H,W,Cs+Cu] of a 3x3 conv (Cs+Cu -> Cdy) from dY, through conv_fwd on the flipped transposed
+    weight, written to the concat's two destinations."""
+    name: str
+    N: int
+    H: int
+    W: int
+    Cdy: int
+    Cs: int
+    Cu: int
+    pref: int
+    ws: bool = False
+    views: bool = False
+    seed: int = 0
+
+
+DGRAD_CASES = [
+    Dgrad("dgrad-auto", 2, 12, 10, 64, 64, 64, 0),
+    Dgrad("dgrad-halo-views", 2, 8, 64, 128, 64, 64, 1, views=True),
+    Dgrad("dgrad-ring", 2, 2, 64, 64, 64, 64, 6),
+    Dgrad("dgrad-pp128", 1, 24, 40, 256, 128, 128, 5),
+    Dgrad("dgrad-ppsk128", 4, 32, 32, 256, 256, 256, 7, ws=True),
+    Dgrad("dgrad-splitk-auto-views", 1, 8, 8, 512, 128, 128, 0, ws=True, views=True),
+]
+
+
+@functools.lru_cache(maxsize=4)
+def _dgrad_data(N, H, W, Cdy, Cdx, seed, cdx_limit):
+    g = generator(3000 + seed)
+    p, q = densities(9 * Cdy)
+    dy = ternary((N, H, W, Cdy), p, g)
+    w = ternary((Cdy, Cdx, 3, 3), q, g)  # the forward conv's weight: Cdx inputs -> Cdy outputs
+    cx = Cdx if cdx_limit is None else min(Cdx, cdx_limit)
+    x0 = torch.zeros(N, H, W, cx, dtype=BF16)
+    dx, _ = conv_grads_ref(x0, w[:, :cx], dy, True, False)
+    return dy, w, dx
+
+
+def dgrad_data(N, H, W, Cdy, Cdx, seed=0, cdx_limit=None):
+    """(dy bf16, forward weight w [Cdy, Cdx, 3, 3] bf16, dx [N,H,W,Cdx'] fp64 by autograd)."""
+    return _dgrad_data(N, H, W, Cdy, Cdx, seed, cdx_limit)
+
+
+@dataclass(frozen=True)
+class BnRed:
+    """A dgrad with the owner BN layer's backward reduction fused: rows of sum(g), sum(g * xhat)."""
+    name: str
+    N: int
+    H: int
+    W: int
+    Cdy: int
+    Cdx: int
+    splitk: bool   # conv_dgrad_splitk_bnred (else the ring's conv_dgrad_bnred)
+    seed: int = 0
+
+
+BNRED_CASES = [
+    BnRed("bnred-ring", 2, 6, 64, 64, 64, False),
+    BnRed("bnred-ring-3seg", 3, 2, 192, 64, 64, False),
+    BnRed("bnred-splitk", 2, 8, 8, 128, 64, True),
+    BnRed("bnred-splitk-512", 4, 16, 16, 512, 512, True),
+]
+
+
+def bnred_data(b: BnRed, cdx_limit=None):
+    """dy, w, dx64 as dgrad_data, plus y (ternary pre-BN output of the owner layer), coef = [mean | invstd |
+    scale | shift] (integer mean, power-of-two invstd and scale, integer shift) and the fp64 sums
+    [2][Cdx'] of g = dx * [scale * y + shift > 0] and g * (y - mean) * invstd."""
+    dy, w, dx = dgrad_data(b.N, b.H, b.W, b.Cdy, b.Cdx, 50 + b.seed, cdx_limit)
+    g = generator(4000 + b.seed)
+    y = ternary((b.N, b.H, b.W, b.Cdx), 0.7, g)
+    mean = int_vector(b.Cdx, g, 2)
+    inv = torch.pow(2.0, torch.randint(-2, 2, (b.Cdx,), generator=g).double()).float()
+    scale = pow2_signed(b.Cdx, g)
+    shift = torch.randint(-1, 2, (b.Cdx,), generator=g).float()
+    n = dx.shape[-1]
+    yd = y[..., :n].double()
+    gg = dx * ((yd * scale[:n].double() + shift[:n].double()) > 0)
+    t2 = gg * (yd - mean[:n].double()) * inv[:n].double()
+    sums = torch.stack([gg.reshape(-1, n).sum(0), t2.reshape(-1, n).sum(0)])
+    return dy, w, dx, y, torch.cat([mean, inv, scale, shift]), sums, (gg, t2)
+
+
+def check_bnred_case(b: BnRed, dx, terms) -> None:
+    assert_exact_class(dx)
+    assert_f32_sums(terms[0], "sum g")
+    assert_f32_sums(terms[1], "sum g * xhat")
+    assert (terms[0] != dx).any() and (terms[0] != 0).any()  # the ReLU mask cuts some and keeps some
+
+
+# ---------------------------------------------------------------------------------------------
+# weight gradients
+# ---------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Wgrad:
+    name: str
+    N: int
+    H: int
+    W: int
+    C1: int
+    C2: int
+    Cout: int
+    splits: int
+    variant: int
+    packed: bool = False
+    accumulate: bool = False
+    views: bool = False
+    seed: int = 0
+
+
+def _w(name, shape, splits, variant, **kw):
+    return Wgrad(name, *shape, splits, variant, **kw)
+
+
+WGRAD_CASES = [
+    # generic layout (odd sizes, dual source), splits 1 / mid / two-level (> 8)
+    _w("generic-dual-v0", (2, 9, 13, 64, 64, 128), 2, 0),
+    _w("generic-dual-v4-views", (2, 9, 13, 64, 64, 128), 2, 4, views=True),
+    _w("generic-1split", (1, 8, 8, 256, 0, 512), 1, 0),
+    _w("generic-150-v0", (4, 20, 20, 64, 0, 64), 150, 0),
+    _w("generic-150-v4-acc", (4, 20, 20, 64, 0, 64), 150, 4, accumulate=True),
+    _w("generic-512-v4", (2, 64, 64, 64, 0, 64), 512, 4),
+    # W % 64 == 0: row ring (auto, 64 couts), halo kernel (forced, or 128 couts)
+    _w("w64-ring-v0", (2, 5, 64, 64, 0, 64), 3, 0),
+    _w("w64-halo-v5-acc", (2, 5, 64, 64, 0, 64), 3, 5, accumulate=True),
+    _w("w64-generic-v4", (2, 5, 64, 64, 0, 64), 3, 4),
+    _w("w128-dual-v0-views", (1, 6, 128, 64, 64, 128), 4, 0, views=True),
+    _w("w64-ring-512", (2, 64, 64, 64, 0, 64), 512, 0),
+    _w("w192-v5", (1, 4, 192, 64, 128, 256), 2, 5),
+    # W | 64: multi-row segments
+    _w("w32-v0", (2, 6, 32, 64, 0, 64), 3, 0),
+    _w("w32-v5-views", (2, 6, 32, 64, 0, 64), 3, 5, views=True),
+    _w("w16-dual-v5", (1, 8, 16, 128, 128, 128), 2, 5),
+    _w("w8-v5", (3, 8, 8, 64, 0, 128), 5, 5),
+    _w("w8-v0", (3, 8, 8, 64, 0, 128), 5, 0),
+    # packed first layer
+    _w("packed-5", (2, 18, 14, 8, 0, 64), 5, 0, packed=True),
+    _w("packed-300-acc-views", (2, 64, 64, 8, 0, 64), 300, 0, packed=True, accumulate=True, views=True),
+]
+
+
+@functools.lru_cache(maxsize=4)
+def _wgrad_data(N, H, W, cin, Cout, seed):
+    g = generator(5000 + seed)
+    x = ternary((N, H, W, cin), 0.5, g)
+    dy = ternary((N, H, W, Cout), 0.5, g)
+    w0 = torch.zeros(Cout, cin, 3, 3, dtype=BF16)
+    _, dw = conv_grads_ref(x, w0, dy, False, True)
+    return x, dy, dw.permute(0, 2, 3, 1).reshape(-1).contiguous()
+
+
+def wgrad_data(c: Wgrad):
+    """(x [N,H,W,Cin] bf16 (3 real channels when packed), dy bf16, dw fp64 flat [Cout][9][Cin])."""
+    return _wgrad_data(c.N, c.H, c.W, 3 if c.packed else c.C1 + c.C2, c.Cout, c.seed)
+
+
+def wgrad_init(n: int, seed: int) -> torch.Tensor:
+    """The non-zero integer `out` that accumulate = 1 adds onto."""
+    return torch.randint(-50, 51, (n,), generator=generator(6000 + seed)).float()
+
+
+def check_wgrad_ref(dw64: torch.Tensor, M: int) -> None:
+    """Ternary operands: every partial sum of a weight-gradient element is an integer of magnitude <= M."""
+    assert torch.equal(dw64, dw64.round())
+    assert M + 50 < F32_EXACT and dw64.abs().max().item() <= M
+    assert (dw64 != 0).float().mean().item() > 0.5
+
+
+@dataclass(frozen=True)
+class FirstBn:
+    name: str
+    N: int
+    H: int
+    W: int
+    splits: int
+    accumulate: bool = False
+    views: bool = False
+    seed: int = 0
+
+
+FIRSTBN_CASES = [
+    FirstBn("firstbn-5", 2, 16, 12, 5),
+    FirstBn("firstbn-1-views", 3, 8, 8, 1, views=True),
+    FirstBn("firstbn-300-acc", 2, 64, 64, 300, accumulate=True),
+]
+
+
+def firstbn_data(c: FirstBn):
+    """x (3 real channels), da, y ternary; coef = [mean | invstd | scale | shift] (the kernel reads scale and
+    shift for the ReLU mask), coef2 = [A | B | Cc] with A = +-2^k, B and Cc small integers. Returns the
+    fp64 dz = A * da * [scale * y + shift > 0] + B * y + Cc and the fp64 weight gradient of that dz."""
+    g = generator(7000 + c.seed)
+    shape = (c.N, c.H, c.W)
+    x = ternary(shape + (3,), 0.8, g)
+    da = ternary(shape + (64,), 0.7, g)
+    y = ternary(shape + (64,), 0.7, g)
+    scale = pow2_signed(64, g)
+    shift = torch.randint(-1, 2, (64,), generator=g).float()
+    A = pow2_signed(64, g, -1, 2)
+    B = int_vector(64, g, 2)
+    Cc = int_vector(64, g, 2)
+    yd = y.double()
+    dz = A.double() * (da.double() * ((yd * scale.double() + shift.double()) > 0)) + B.double() * yd + Cc.double()
+    _, dw = conv_grads_ref(x, torch.zeros(64, 3, 3, 3), dz, False, True)
+    coef = torch.cat([torch.zeros(64), torch.ones(64), scale, shift])
+    coef2 = torch.cat([A, B, Cc])
+    return x, da, y, coef, coef2, dz, dw.permute(0, 2, 3, 1).reshape(-1).contiguous()
+
+
+def check_firstbn_case(dz64: torch.Tensor, dw64: torch.Tensor) -> None:
+    """|dz| <= 256 in units of 1/2 with <= 8 significant bits: dz is exact in bf16; the weight-gradient
+    sums are multiples of 1/2 far below 2^24."""
+    assert dz64.abs().max().item() <= 9 and torch.equal(dz64 * 2, (dz64 * 2).round())
+    assert torch.equal(dz64, dz64.to(BF16).double())
+    assert_f32_sums(dz64, "dz")
+    assert (dw64 != 0).any()
+
+
+# ---------------------------------------------------------------------------------------------
+# transposed decoder: ConvTranspose2d(k = 2, s = 2)
+# ---------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class UpT:
+    name: str
+    N: int
+    h: int
+    w: int
+    Cin: int
+    C: int       # output channels of the transposed conv
+    H2: int
+    W2: int
+    oy: int
+    ox: int
+    seed: int = 0
+
+
+# conv_upT_fwd / conv_upT_dgrad decline below 256 ping-pong tiles, so these are the smallest shapes they run
+UPT_FWD_CASES = [
+    UpT("upT-fwd-pp128-odd-pad", 1, 61, 67, 128, 512, 125, 136, 1, 1),   # M = 4087: 16 x 16 tiles, ragged
+    UpT("upT-fwd-pp256", 2, 128, 128, 64, 128, 256, 256, 0, 0),
+]
+UPT_DGRAD_CASES = [
+    UpT("upT-dgrad-pp128-odd-pad", 1, 149, 147, 384, 64, 301, 297, 2, 1),  # M = 21903: 86 x 3 tiles, ragged
+    UpT("upT-dgrad-pp256", 8, 64, 64, 512, 64, 128, 128, 0, 0),
+]
+UPT_SMALL_CASES = [   # the generic weight gradient, the taps = 1 GEMMs and the bias column sums
+    UpT("upT-small", 2, 8, 8, 128, 64, 16, 16, 0, 0),
+    UpT("upT-small-odd-pad", 1, 4, 5, 256, 128, 9, 11, 1, 0),
+    UpT("upT-small-odd-pad2", 2, 5, 7, 128, 64, 13, 17, 1, 2),
+]
+
+
+@functools.lru_cache(maxsize=2)
+def _upT_data(N, h, w, Cin, C, H2, W2, oy, ox, seed, want, cin_limit):
+    g = generator(8000 + seed)
+    p, q = densities(Cin)
+    x = ternary((N, h, w, Cin), p, g)
+    Wt = ternary((Cin, C, 2, 2), q, g)
+    bias = int_vector(C, g, 4)
+    if cin_limit is not None:  # dx of the first input channels alone (u is then not the case's)
+        x, Wt = x[..., :cin_limit].contiguous(), Wt[:cin_limit].contiguous()
+    xr = x.double().permute(0, 3, 1, 2).requires_grad_(want != "fwd")
+    Wr = Wt.double().requires_grad_(want == "bwd")
+    br = bias.double().requires_grad_(want == "bwd")
+    y = F.conv_transpose2d(xr, Wr, br, stride=2)
+    u = F.pad(y, [ox, W2 - 2 * w - ox, oy, H2 - 2 * h - oy])
+    out = {"x": x, "W": Wt, "bias": bias, "u": u.detach().permute(0, 2, 3, 1).contiguous()}
+    if want != "fwd":
+        pd, _ = densities(4 * C)
+        du = ternary((N, H2, W2, C), pd, g)
+        u.backward(du.double().permute(0, 3, 1, 2))
+        out.update(du=du, dx=xr.grad.permute(0, 2, 3, 1).contiguous())
+        if want == "bwd":
+            out.update(dW=Wr.grad, db=br.grad)
+    return out
+
+
+def upT_data(c: UpT, want: str = "fwd", cin_limit: Optional[int] = None):
+    """x [N,h,w,Cin], W [Cin,C,2,2], integer bias; u = pad(conv_transpose2d(x, W, bias)) [N,H2,W2,C] fp64
+    (zero outside the window at (oy, ox)); with want = "dx" also du (ternary, whole padded map) and the
+    fp64 autograd dx [N,h,w,Cin]; with "bwd" dW [Cin,C,2,2] and db [C] too."""
+    return _upT_data(c.N, c.h, c.w, c.Cin, c.C, c.H2, c.W2, c.oy, c.ox, c.seed, want, cin_limit)
+
+
+def upT_weights(Wt: torch.Tensor):
+    """(forward [4C][Cin], dgrad [Cin][4C]) GEMM weights, columns ordered (dh, dw, c)."""
+    wd = Wt.permute(0, 2, 3, 1).reshape(Wt.shape[0], -1).contiguous()
+    return wd.t().contiguous(), wd
+
+
+def upT_window(c: UpT, t: torch.Tensor) -> torch.Tensor:
+    """[N,H2,W2,C] -> the sub-pixel GEMM layout [N,h,w,(dh,dw,c)] of the 2h x 2w window at (oy, ox)."""
+    win = t[:, c.oy:c.oy + 2 * c.h, c.ox:c.ox + 2 * c.w]
+    return win.reshape(c.N, c.h, 2, c.w, 2, c.C).permute(0, 1, 3, 2, 4, 5).reshape(c.N, c.h, c.w, 4 * c.C).contiguous()

@@ -1,0 +1,352 @@
+"""Exact integer-lattice tests of every conv, dgrad and wgrad variant (GPU only).
+
+All these kernels multiply bf16 operands and accumulate in fp32, so on integer-valued inputs whose partial
+sums stay below 2^24 every summation order, tile shape and split count gives the same exact integer and the
+bf16 output is that integer rounded to nearest even. Each case is therefore compared bit for bit with a
+CPU fp64 reference (tests/lattice.py): outputs with torch.equal, BN partial rows and weight gradients with
+==. There is no tolerance anywhere in this file. The preconditions are asserted on the reference alone;
+tests/test_lattice_cpu.py runs the same checks for every case without a GPU.
+"""
+import pytest
+import torch
+import torch.nn.functional as F
+
+import lattice as L
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+NAN = float("nan")
+
+
+@pytest.fixture(scope="module")
+def C():
+    from robotic_discovery_platform_amd.ops import native
+    return native()
+
+
+class Buf:
+    """A device activation: dense, or a channel slice of a wider buffer between sentinel guard bands."""
+
+    def __init__(self, t, shape, views, pads=(8, 24), dtype=L.BF16):
+        self.views = views
+        if views:
+            self.flat, self.t = L.embed(t, shape, pads[0], pads[1], DEV, dtype)
+            self.before = self.flat.clone()
+        elif t is None:
+            self.t = torch.full(tuple(shape), L.SENTINEL, dtype=dtype, device=DEV)
+        else:
+            self.t = t.to(DEV).contiguous()
+            self.before = self.t.clone()
+
+    def assert_unchanged(self):  # an input: the whole buffer, guards and padding included
+        cur = self.flat if self.views else self.t
+        assert torch.equal(cur.view(torch.int16), self.before.view(torch.int16))
+
+    def assert_outside_intact(self):  # an output: everything but the view
+        if self.views:
+            assert L.outside_view_intact(self.flat, self.t)
+
+
+def _inp(t, views, pads=(16, 8)):
+    return None if t is None else Buf(t, t.shape, views, pads)
+
+
+def _out(shape, views, pads=(8, 24)):
+    return Buf(None, shape, views, pads)
+
+
+def _ws(C, c_shape, taps, pref):
+    n = C.conv_ws_elems(*c_shape, taps, 0, pref)
+    assert n > 0, "the case is meant to run split-K"
+    return torch.full((n,), NAN, device=DEV)  # every slab element is written before the reduce reads it
+
+
+def _stats_sums(stats, r, Cout):
+    """The partial rows [r][2][Cout] summed in fp64 -> [2][Cout]."""
+    return stats[: r * 2 * Cout].view(r, 2, Cout).double().sum(0).cpu()
+
+
+def _conv_operands(c):
+    """Device operands of a forward / eval case and its fp64 reference."""
+    x, w, ref = L.conv_data(c)
+    if c.packed:
+        x8, wk = L.pack_first(x, w)
+        x1, x2 = _inp(x8, c.views, (8, 0)), None
+    else:
+        wk = L.ohwi(w)
+        x1 = _inp(x[..., :c.C1].contiguous(), c.views)
+        x2 = _inp(x[..., c.C1:].contiguous(), c.views, (8, 16)) if c.C2 else None
+    return x1, x2, wk.to(DEV), ref
+
+
+def _check_inputs(*bufs):
+    for b in bufs:
+        if b is not None:
+            b.assert_unchanged()
+
+
+# ---------------------------------------------------------------------------------------------
+# 2. forward convs: every dispatch path
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("c", L.FWD_CASES, ids=lambda c: c.name)
+def test_conv_fwd_exact(C, c):
+    """Training forward on the forced path: y bitwise = RNE(fp64 conv); with stats, the BN partial rows sum
+    (in fp64) to exactly sum(y) and sum(y^2) of the reference; split destinations both exact; views leave
+    every byte outside them untouched."""
+    x1, x2, wk, ref = _conv_operands(c)
+    L.check_conv_case(c, ref)
+    shape = (c.N, c.H, c.W)
+    y1 = _out(shape + (c.split or c.Cout,), c.views)
+    y2 = _out(shape + (c.Cout - c.split,), c.views, (24, 8)) if c.split else None
+    stats = None
+    if c.stats:
+        rows = C.conv_stats_rows(c.M, c.Cout, c.pref)
+        stats = torch.full((rows * 2 * c.Cout,), NAN, device=DEV)  # rows [:r] are written, never accumulated
+    ws = _ws(C, (c.N, c.H, c.W, c.C1, c.C2, c.Cout), c.taps, c.pref) if c.ws else None
+    r = C.conv_fwd(x1.t, x2.t if x2 else None, wk, c.taps, int(c.packed), y1.t, y2.t if y2 else None, stats, c.pref,
+                   None, 0, ws)
+    torch.cuda.synchronize()
+    exp = L.expected_bf16(ref)
+    got = y1.t.cpu() if y2 is None else torch.cat([y1.t.cpu(), y2.t.cpu()], -1)
+    assert torch.equal(got, exp)
+    if c.split:
+        assert torch.equal(y1.t.cpu(), exp[..., :c.split]) and torch.equal(y2.t.cpu(), exp[..., c.split:])
+    if c.stats:
+        assert 0 < r <= rows
+        s = _stats_sums(stats, r, c.Cout)
+        flat = ref.reshape(-1, c.Cout)
+        assert (s[0] == flat.sum(0)).all()
+        assert (s[1] == (flat * flat).sum(0)).all()
+    _check_inputs(x1, x2)
+    y1.assert_outside_intact()
+    if y2:
+        y2.assert_outside_intact()
+
+
+@pytest.mark.parametrize("c", L.EVAL_CASES, ids=lambda c: c.name)
+def test_conv_eval_exact(C, c):
+    """Eval epilogue relu(scale * y + shift) with scale = +-2^k and integer shift (exact in fp32, fused or
+    not), and the fused MaxPool2d(2) output (max is exact): bitwise against the fp64 reference. Row-band
+    paths: forced (16) and through the fragment-major weight copy where rowband_frag_mode selects it."""
+    x1, x2, wk, ref = _conv_operands(c)
+    L.check_conv_case(c, ref)
+    sc, sh = L.eval_coef(c)
+    affine = torch.cat([torch.zeros(c.Cout), torch.ones(c.Cout), sc, sh]).to(DEV)  # [mean | invstd | scale | shift]
+    y = _out((c.N, c.H, c.W, c.Cout), c.views)
+    p = _out((c.N, c.H // 2, c.W // 2, c.Cout), c.views, (16, 16)) if c.pool else None
+    ws = _ws(C, (c.N, c.H, c.W, c.C1, c.C2, c.Cout), c.taps, c.pref) if c.ws else None
+    wfrag = None
+    if c.wfrag:
+        from robotic_discovery_platform_amd.models.unet import rowband_frag_weights
+        assert C.rowband_frag_mode(c.N, c.H, c.W, c.C1, c.C2, c.Cout) == c.wfrag
+        wfrag = rowband_frag_weights(wk)
+    C.conv_fwd(x1.t, x2.t if x2 else None, wk, c.taps, int(c.packed), y.t, None, None, c.pref, affine, 1, ws,
+               p.t if p else None, None, 0, 0, wfrag)
+    torch.cuda.synchronize()
+    exp = L.expected_bf16(L.eval_ref(c, ref))
+    assert torch.equal(y.t.cpu(), exp)
+    if c.pool:
+        pexp = F.max_pool2d(exp.float().permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1).to(L.BF16)
+        assert torch.equal(p.t.cpu(), pexp)
+        p.assert_outside_intact()
+    _check_inputs(x1, x2)
+    y.assert_outside_intact()
+
+
+# ---------------------------------------------------------------------------------------------
+# 3. dgrad
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("c", L.DGRAD_CASES, ids=lambda c: c.name)
+def test_conv_dgrad_exact(C, c):
+    """dX = conv(dY, flip(W)^T) into the concat's two destinations: bitwise the fp64 autograd gradient."""
+    Cdx = c.Cs + c.Cu
+    dy, w, dx = L.dgrad_data(c.N, c.H, c.W, c.Cdy, Cdx, c.seed)
+    L.assert_exact_class(dx)
+    a = _inp(dy, c.views)
+    wt = L.dgrad_weight(w).to(DEV)
+    d1 = _out((c.N, c.H, c.W, c.Cs), c.views)
+    d2 = _out((c.N, c.H, c.W, c.Cu), c.views, (24, 8))
+    ws = _ws(C, (c.N, c.H, c.W, c.Cdy, 0, Cdx), 9, c.pref) if c.ws else None
+    assert C.conv_fwd(a.t, None, wt, 9, 0, d1.t, d2.t, None, c.pref, None, 0, ws) >= 0
+    torch.cuda.synchronize()
+    exp = L.expected_bf16(dx)
+    assert torch.equal(d1.t.cpu(), exp[..., :c.Cs])
+    assert torch.equal(d2.t.cpu(), exp[..., c.Cs:])
+    _check_inputs(a)
+    d1.assert_outside_intact()
+    d2.assert_outside_intact()
+
+
+@pytest.mark.parametrize("b", L.BNRED_CASES, ids=lambda b: b.name)
+def test_conv_dgrad_bnred_exact(C, b):
+    """The dgrads that also reduce the owner BN layer's backward sums (row ring; split-K reduce): dx bitwise,
+    and the partial rows sum (in fp64) to exactly sum(g) and sum(g * xhat), g = dx * [scale * y + shift > 0],
+    xhat = (y - mean) * invstd -- integer mean, power-of-two invstd / scale: every term is dyadic."""
+    dy, w, dx, y, coef, sums, terms = L.bnred_data(b)
+    L.check_bnred_case(b, dx, terms)
+    wt = L.dgrad_weight(w).to(DEV)
+    out = torch.full((b.N, b.H, b.W, b.Cdx), L.SENTINEL, dtype=L.BF16, device=DEV)
+    part = torch.full((1024 * 2 * b.Cdx,), NAN, device=DEV)
+    if b.splitk:
+        ws = _ws(C, (b.N, b.H, b.W, b.Cdy, 0, b.Cdx), 9, 0)
+        T = C.conv_dgrad_splitk_bnred(dy.to(DEV), wt, out, y.to(DEV), coef.to(DEV), part, ws)
+    else:
+        T = C.conv_dgrad_bnred(dy.to(DEV), wt, out, y.to(DEV), coef.to(DEV), part)
+    torch.cuda.synchronize()
+    assert 0 < T <= 1024
+    assert torch.equal(out.cpu(), L.expected_bf16(dx))
+    got = _stats_sums(part, T, b.Cdx)
+    assert (got[0] == sums[0]).all()
+    assert (got[1] == sums[1]).all()
+
+
+# ---------------------------------------------------------------------------------------------
+# 4. weight gradients
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("c", L.WGRAD_CASES, ids=lambda c: c.name)
+def test_conv_wgrad_exact(C, c):
+    """conv_wgrad (auto / generic / halo, split counts 1 .. 512, every layout regime, dual source, packed
+    first layer, accumulate): the fp32 result equals the fp64 autograd weight gradient exactly."""
+    x, dy, dw = L.wgrad_data(c)
+    M = c.N * c.H * c.W
+    L.check_wgrad_ref(dw, M)
+    if c.packed:
+        x8 = torch.zeros(c.N, c.H, c.W, 8, dtype=L.BF16)
+        x8[..., :3] = x
+        x1, x2, cin = _inp(x8, c.views, (8, 0)), None, 8
+    else:
+        x1 = _inp(x[..., :c.C1].contiguous(), c.views)
+        x2 = _inp(x[..., c.C1:].contiguous(), c.views, (8, 16)) if c.C2 else None
+        cin = c.C1 + c.C2
+    d = _inp(dy, c.views, (24, 8))
+    # every slab element the reduce reads was written by the gradient kernel of the same call (each split
+    # stores its whole [Cout][ncols] tile): NaN here shows that nothing is read before it is written
+    slab = torch.full((C.wgrad_slab_elems(c.N, c.H, c.W, cin, c.Cout, 9, int(c.packed), c.splits),), NAN, device=DEV)
+    if c.accumulate:
+        init = L.wgrad_init(dw.numel(), c.seed)
+        out, exp = init.to(DEV), (dw + init.double()).float()
+    else:
+        out, exp = torch.full((dw.numel(),), L.SENTINEL, device=DEV), dw.float()
+    r = C.conv_wgrad(x1.t, x2.t if x2 else None, d.t, 9, int(c.packed), 3 if c.packed else 0, slab, out,
+                     int(c.accumulate), c.splits, c.variant)
+    torch.cuda.synchronize()
+    assert r > 0
+    assert torch.equal(out.cpu(), exp)
+    _check_inputs(x1, x2, d)
+
+
+@pytest.mark.parametrize("c", L.FIRSTBN_CASES, ids=lambda c: c.name)
+def test_wgrad_first_bn_exact(C, c):
+    """wgrad_first_bn forms dz = A * g + B * y + Cc (g = da * [scale * y + shift > 0]) in registers; with
+    A = +-2^k and small integer B, Cc on ternary da / y, dz is exact in bf16 and the weight gradient must
+    equal the fp64 gradient of that dz exactly."""
+    x, da, y, coef, coef2, dz, dw = L.firstbn_data(c)
+    L.check_firstbn_case(dz, dw)
+    x8 = torch.zeros(c.N, c.H, c.W, 8, dtype=L.BF16)
+    x8[..., :3] = x
+    bx, bda, by = _inp(x8, c.views, (8, 0)), _inp(da, c.views), _inp(y, c.views, (24, 8))
+    slab = torch.full((C.wgrad_slab_elems(c.N, c.H, c.W, 8, 64, 9, 1, c.splits),), NAN, device=DEV)
+    if c.accumulate:
+        init = L.wgrad_init(dw.numel(), c.seed)
+        out, exp = init.to(DEV), (dw + init.double()).float()
+    else:
+        out, exp = torch.full((dw.numel(),), L.SENTINEL, device=DEV), dw.float()
+    r = C.wgrad_first_bn(bx.t, bda.t, by.t, coef.to(DEV), coef2.to(DEV), slab, out, 3, int(c.accumulate), c.splits)
+    torch.cuda.synchronize()
+    assert r >= 1
+    assert torch.equal(out.cpu(), exp)
+    _check_inputs(bx, bda, by)
+
+
+# ---------------------------------------------------------------------------------------------
+# transposed decoder
+# ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("c", L.UPT_FWD_CASES, ids=lambda c: c.name)
+def test_conv_upT_fwd_exact(C, c):
+    """ConvTranspose2d(2, s2) + integer bias scattered by the ping-pong epilogue (both tile widths; odd
+    (h, w) at a non-zero pad offset): bitwise fp64 conv_transpose2d inside the window; the border, which
+    the kernel must not write, keeps the sentinel."""
+    d = L.upT_data(c, "fwd")
+    L.assert_exact_class(d["u"])
+    wf, _ = L.upT_weights(d["W"])
+    u = torch.full((c.N, c.H2, c.W2, c.C), L.SENTINEL, dtype=L.BF16, device=DEV)
+    assert C.conv_upT_fwd(d["x"].to(DEV), wf.to(DEV), d["bias"].to(DEV), u, c.oy, c.ox) == 0
+    torch.cuda.synchronize()
+    exp = L.expected_bf16(d["u"])
+    inside = torch.zeros(c.H2, c.W2, dtype=torch.bool)
+    inside[c.oy:c.oy + 2 * c.h, c.ox:c.ox + 2 * c.w] = True
+    exp[:, ~inside] = L.SENTINEL
+    assert torch.equal(u.cpu(), exp)
+
+
+@pytest.mark.parametrize("c", L.UPT_DGRAD_CASES, ids=lambda c: c.name)
+def test_conv_upT_dgrad_exact(C, c):
+    """ConvTranspose2d(2, s2) input gradient read from du's sub-pixels (4 'taps'): bitwise fp64 autograd."""
+    d = L.upT_data(c, "dx")
+    L.assert_exact_class(d["dx"])
+    _, wd = L.upT_weights(d["W"])
+    dx = torch.full((c.N, c.h, c.w, c.Cin), L.SENTINEL, dtype=L.BF16, device=DEV)
+    assert C.conv_upT_dgrad(d["du"].to(DEV), wd.to(DEV), dx, c.oy, c.ox) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(dx.cpu(), L.expected_bf16(d["dx"]))
+
+
+@pytest.mark.parametrize("c", L.UPT_SMALL_CASES, ids=lambda c: c.name)
+def test_upT_small_gemms_wgrad_colsum_exact(C, c):
+    """The transposed decoder on small maps: the taps = 1 GEMMs of its forward and input gradient, the
+    weight gradient from du's sub-pixels (conv_wgrad_upT) and from the unshuffled copy (conv_wgrad, taps = 1,
+    roles swapped), and the bias gradient as column sums -- all exactly the fp64 conv_transpose2d autograd."""
+    d = L.upT_data(c, "bwd")
+    L.assert_exact_class(d["u"])
+    L.assert_exact_class(d["dx"])
+    wf, wd = L.upT_weights(d["W"])
+    M = c.N * c.h * c.w
+    x, du = d["x"].to(DEV), d["du"].to(DEV)
+    # forward GEMM (bias is added by the shuffle pass, not here)
+    yT = torch.full((c.N, c.h, c.w, 4 * c.C), L.SENTINEL, dtype=L.BF16, device=DEV)
+    C.conv_fwd(x, None, wf.to(DEV), 1, 0, yT, None, None, 0, None, 0)
+    assert torch.equal(yT.cpu(), L.expected_bf16(L.upT_window(c, d["u"]) - d["bias"].double().repeat(4)))
+    # input gradient GEMM on the unshuffled window
+    dyT = L.upT_window(c, d["du"]).to(DEV)
+    dx = torch.full((c.N, c.h, c.w, c.Cin), L.SENTINEL, dtype=L.BF16, device=DEV)
+    C.conv_fwd(dyT, None, wd.to(DEV), 1, 0, dx, None, None, 0, None, 0)
+    assert torch.equal(dx.cpu(), L.expected_bf16(d["dx"]))
+    # weight gradient [Cin][(dh, dw, c)]
+    dW = d["dW"].permute(0, 2, 3, 1).reshape(-1).float()
+    splits = max(1, M // 64)
+    n_slab = C.wgrad_slab_elems(c.N, c.h, c.w, 4 * c.C, c.Cin, 1, 0, splits)
+    for fused in (True, False):
+        slab = torch.full((n_slab,), NAN, device=DEV)
+        gw = torch.full((c.Cin * 4 * c.C,), L.SENTINEL, device=DEV)
+        if fused:
+            assert C.conv_wgrad_upT(du, x, c.oy, c.ox, slab, gw, 0, splits) > 0
+        else:
+            assert C.conv_wgrad(dyT, None, x, 1, 0, 4 * c.C, slab, gw, 0, splits, 0) > 0
+        assert torch.equal(gw.cpu(), dW)
+    # bias gradient: column sums over the window's 4 sub-pixel groups, then accumulated once more
+    db = torch.full((c.C,), L.SENTINEL, device=DEV)
+    part = torch.full(((1024 * 4 + 64) * c.C,), NAN, device=DEV)
+    C.colsum_bf16(dyT, 4, part, db, 0)
+    assert torch.equal(db.cpu(), d["db"].float())
+    C.colsum_bf16(dyT, 4, part, db, 1)
+    assert torch.equal(db.cpu(), (2 * d["db"]).float())
+
+
+@pytest.mark.parametrize("N,H,W,Ch,groups,views", [(2, 9, 13, 64, 1, True), (1, 64, 64, 256, 4, False),
+                                                   (3, 33, 47, 128, 1, False)])
+def test_colsum_bf16_exact(C, N, H, W, Ch, groups, views):
+    """colsum_bf16 on -3..3 integers (every partial sum an integer below 2^24): exactly the fp64 sums."""
+    x = L.small_ints((N, H, W, Ch), L.generator(9000 + Ch))
+    ref = x.double().reshape(-1, groups, Ch // groups).sum((0, 1))
+    assert 3 * N * H * W * groups < L.F32_EXACT and (ref != 0).any()
+    b = _inp(x, views)
+    out = torch.full((Ch // groups,), L.SENTINEL, device=DEV)
+    part = torch.full((1024 * Ch + 64 * (Ch // groups),), NAN, device=DEV)
+    C.colsum_bf16(b.t, groups, part, out, 0)
+    assert torch.equal(out.cpu(), ref.float())
+    _check_inputs(b)
