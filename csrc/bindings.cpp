@@ -92,6 +92,9 @@ int rdp_headk_fwd(const void*, int, const float*, const float*, const void*, flo
 int rdp_headk_bwd(const void*, int, const float*, const float*, const void*, const float*, void*, int, float*, float*,
                   float*, int, int, float, hipStream_t);
 int rdp_headk_mask(const void*, int, const float*, const float*, int, void*, int, int, hipStream_t);
+int rdp_seg_confusion_blocks(long);
+int rdp_seg_confusion_block_pixels();
+int rdp_seg_confusion(const float*, const void*, void*, long, int, float, int, hipStream_t);
 int rdp_adam(float*, const void*, int, float*, float*, void*, long, float, float, float, float, float, float, int*, int,
              int, hipStream_t);
 int rdp_cast_bf16(const float*, void*, long, hipStream_t);
@@ -1348,6 +1351,33 @@ void headk_mask(torch::Tensor a, torch::Tensor w, torch::Tensor b, int cls, torc
                                       (int)M, K, st)) == 0, "headk_mask");
 }
 
+// ---- validation metrics (csrc/seg_metrics.hip) ----
+int seg_confusion_blocks(long M) { return rdp_seg_confusion_blocks(M); }
+int seg_confusion_block_pixels() { return rdp_seg_confusion_block_pixels(); }
+
+// counts (int64 [KC * KC + 1], KC = max(K, 2)) += the confusion counts of `logits` against `target`:
+// K >= 2: logits fp32 [M * K] pixel-major, target u8 [M], arg-max with ties to the lowest class, labels >= K
+// ignored (last slot); K == 1: logits fp32 [M], target fp32 [M], logit > thr against target > 0.5.
+// `max_blocks` > 0 caps the grid (tests: a small M then takes several passes of the grid-stride loop).
+void seg_confusion(torch::Tensor logits, torch::Tensor target, int K, torch::Tensor counts, double thr,
+                   int max_blocks) {
+  TORCH_CHECK(K >= 1 && K <= 8, "seg_confusion: 1 <= K <= 8 classes, got ", K);
+  TORCH_CHECK(max_blocks >= 0, "seg_confusion: max_blocks");
+  check_f32(logits, "logits");
+  const long M = target.numel();
+  TORCH_CHECK(M > 0 && M < (1L << 31), "seg_confusion: pixel count");
+  TORCH_CHECK(logits.numel() == M * K, "seg_confusion: logits must hold M * K values");
+  TORCH_CHECK((uintptr_t)logits.data_ptr() % 16 == 0, "seg_confusion: logits must be 16-byte aligned");
+  if (K == 1) check_f32(target, "target");
+  else check_u8(target, M, "target");
+  const int KC = K < 2 ? 2 : K;
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == torch::kInt64 && counts.is_contiguous() &&
+                  counts.numel() == (long)KC * KC + 1,
+              "seg_confusion: counts must be a contiguous int64 GPU tensor of ", KC * KC + 1, " elements");
+  TORCH_CHECK(RDP_PLAN(rdp_seg_confusion(logits.data_ptr<float>(), target.data_ptr(), counts.data_ptr(), M, K,
+                                         (float)thr, max_blocks, st)) > 0, "seg_confusion");
+}
+
 void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow,
           double lr, double b1, double b2, double eps, double wd, double gscale, torch::Tensor step, bool inc,
           int max_blocks) {
@@ -2039,6 +2069,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sums"), py::arg("da"), py::arg("partial"), py::arg("gw"), py::arg("gb"), py::arg("gscale") = 1.0);
   m.def("headk_mask", on_device(&headk_mask), py::arg("a"), py::arg("w"), py::arg("b"), py::arg("cls"),
         py::arg("mask"));
+  m.def("seg_confusion_blocks", &seg_confusion_blocks);
+  m.def("seg_confusion_block_pixels", &seg_confusion_block_pixels);
+  m.def("seg_confusion", on_device(&seg_confusion), py::arg("logits"), py::arg("target"), py::arg("K"),
+        py::arg("counts"), py::arg("thr") = 0.0, py::arg("max_blocks") = 0);
   m.def("conv_head_mask", on_device(&conv_head_mask));
   m.def("conv_rowband_chain", on_device(&conv_rowband_chain));
   m.def("conv_rowband", on_device(&conv_rowband));

@@ -4,6 +4,7 @@ One command per reference entry point, with the reference consta
 (config.py) and every field overridable by ``--flag`` or ``RDP_<SECTION>_<FIELD>``:
 
   train        scripts/train_segmenter.py            (torchrun-compatible: one rank per GPU)
+  eval         score a registered model on a dataset: IoU / Dice / pixel accuracy, one JSON line
   serve        services/vision_analysis/server.py
   client       services/vision_analysis/client.py    (headless; --save-dir writes overlays)
   calibrate    scripts/01_calibrate_camera.py
@@ -49,6 +50,15 @@ def cmd_train(args) -> int:
             print(json.dumps({k: v for k, v in res.items() if k in ("run_id", "registered_version", "best_val_loss")}))
     finally:
         shutdown_distributed()
+    return 0
+
+
+def cmd_eval(args) -> int:
+    from .train.evaluate import evaluate_model
+    res = evaluate_model(args.model_uri, dataset_dir=args.dataset_dir, image_size=args.image_size,
+                         batch_size=args.batch_size, mask_values=args.mask_values,
+                         mask_threshold=args.mask_threshold, backend=args.backend, mlruns_dir=args.mlruns_dir)
+    print(json.dumps(res))
     return 0
 
 
@@ -138,6 +148,17 @@ def build_parser() -> argparse.ArgumentParser:
     _section(p, C.TrainConfig, "train")
     p.add_argument("--resume", default=None, help="checkpoint path or 'auto'")
     p.set_defaults(fn=cmd_train)
+    p = sub.add_parser("eval")
+    tc = C.apply_env(C.TrainConfig(), "train")
+    p.add_argument("--model-uri", default=f"models:/{tc.registered_model_name}/latest")
+    p.add_argument("--dataset-dir", default=tc.dataset_dir)
+    p.add_argument("--image-size", type=int, default=tc.image_size)
+    p.add_argument("--batch-size", type=int, default=tc.batch_size)
+    p.add_argument("--mask-values", default=tc.mask_values)
+    p.add_argument("--mask-threshold", type=float, default=tc.mask_threshold)
+    p.add_argument("--backend", default=tc.backend)
+    p.add_argument("--mlruns-dir", default=tc.mlruns_dir)
+    p.set_defaults(fn=cmd_eval)
     p = sub.add_parser("serve")
     _section(p, C.ServeConfig, "serve")
     p.set_defaults(fn=cmd_serve)

@@ -50,7 +50,7 @@ class TrainConfig:
     validation_split: float = 0.2
     image_size: int = 256
     # "bce" (reference) or "bce_dice" (north star); "ce" = softmax cross-entropy, the only loss of a
-    # K-class model (NativeTrainer / EagerTrainer; train_model and the on-disk dataset stay binary)
+    # K-class model (``n_classes`` >= 2 switches the default "bce" to it)
     loss: str = "bce"
     dice_weight: float = 1.0
     seed: int = 0  # the reference split is unseeded; we seed it
@@ -82,6 +82,16 @@ class TrainConfig:
     aug_translate: float = 0.05  # shift ~ U(-t, t) of the width / height, per axis
     aug_contrast: float = 0.1  # gain ~ U(1 - c, 1 + c)
     aug_brightness: float = 0.1  # bias ~ U(-b, b) on the [0, 1] value scale
+    # K-class segmentation (1..8; 1 = the reference's binary model). K >= 2: UNet(3, K), softmax CE over
+    # integer class ids; the mask file's gray value is the class id, or ``mask_values`` ("0,80,160":
+    # comma-separated gray values, the position is the class id, unlisted values are ignored) maps it.
+    n_classes: int = 1
+    mask_values: str = ""
+    # per-epoch validation metrics (per-class IoU / Dice, mean IoU, pixel accuracy: train/metrics.py) from
+    # confusion counts accumulated on the device. ``mask_threshold``: the one-class model's probability
+    # threshold (applied as a logit, like serving); a K-class model predicts by arg-max.
+    val_metrics: bool = False
+    mask_threshold: float = 0.5
 
 
 @dataclass

@@ -129,3 +129,10 @@ def batch_to_float(xb: torch.Tensor, yb: torch.Tensor) -> Tuple[torch.Tensor, to
     x = lut.index_select(0, xb.reshape(-1).int()).view(xb.shape).permute(0, 3, 1, 2)
     y = lut.index_select(0, yb.reshape(-1).int()).view(yb.shape).unsqueeze(1)
     return x, y
+
+
+def batch_to_float_ids(xb: torch.Tensor, yb: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """K-class form: u8 NHWC RGB + u8 NHW class ids -> (float NCHW /255, the u8 ids as they are)."""
+    lut = _u8_lut(xb.device)
+    x = lut.index_select(0, xb.reshape(-1).int()).view(xb.shape).permute(0, 3, 1, 2)
+    return x, yb

@@ -19,18 +19,29 @@ import numpy as np
 DEFAULT_K = np.array([[615.0, 0.0, 320.0], [0.0, 615.0, 240.0], [0.0, 0.0, 1.0]])
 
 
+# BGR hue of segment s (class id s + 1) of a K-class scene; segment 0 is the binary scene's red
+SEGMENT_BGR = np.array([[40, 60, 200], [60, 200, 40], [200, 60, 40], [40, 200, 200], [200, 40, 200], [200, 200, 40],
+                        [40, 130, 230]], np.float64)
+
+
 @dataclass
 class Scene:
     color: np.ndarray  # HxWx3 uint8 BGR
     depth: np.ndarray  # HxW uint16 (depth_scale units)
-    mask: np.ndarray  # HxW uint8 {0, 255}
+    mask: np.ndarray  # HxW uint8 {0, 255}; a K-class scene (n_classes >= 2): class ids 0..K-1
     curvature: float  # analytic curvature of the actuator centre line (1/m)
     radius_m: float
 
 
 def make_scene(seed: int = 0, width: int = 640, height: int = 480, K: np.ndarray = DEFAULT_K,
                depth_scale: float = 0.001, radius_m: Optional[float] = None, thickness_m: float = 0.012,
-               arc_deg: Optional[float] = None, z0: Optional[float] = None, noise: float = 4.0) -> Scene:
+               arc_deg: Optional[float] = None, z0: Optional[float] = None, noise: float = 4.0,
+               n_classes: int = 1) -> Scene:
+    """``n_classes`` >= 2: the K-class form of the same scene (same geometry, depth and random stream as
+    the binary scene of the seed): the band is cut along its arc angle into K - 1 equal segments with
+    ids 1..K-1, each in a hue of its own; the background is id 0 and ``mask`` holds the ids."""
+    if not 1 <= n_classes <= 8:
+        raise ValueError(f"n_classes must be 1..8, got {n_classes}")
     rng = np.random.default_rng(seed)
     R = radius_m if radius_m is not None else float(rng.uniform(0.06, 0.15))
     arc = np.deg2rad(arc_deg if arc_deg is not None else float(rng.uniform(50, 100)))
@@ -66,6 +77,10 @@ def make_scene(seed: int = 0, width: int = 640, height: int = 480, K: np.ndarray
     color = np.stack([base, base + 5, base - 5], -1)
     shade = 0.75 + 0.25 * np.cos(d_ang * 2)
     act = np.stack([40 * shade, 60 * shade, 200 * shade], -1)  # BGR: red actuator
+    if n_classes > 1:
+        seg = np.clip(np.floor((d_ang + arc / 2) / arc * (n_classes - 1)), 0, n_classes - 2).astype(np.int64)
+        mask = np.where(band, seg + 1, 0).astype(np.uint8)
+        act = SEGMENT_BGR[seg] * shade[..., None]
     color = np.where(band[..., None], act, color)
     color = color + rng.normal(0, noise, color.shape)
     color = np.clip(np.rint(color), 0, 255).astype(np.uint8)
@@ -85,15 +100,16 @@ def make_batch(n: int, size: Tuple[int, int] = (256, 256), seed: int = 0):
     return x, y
 
 
-def write_dataset(root: str, n: int, seed: int = 0, fmt: str = "png") -> int:
-    """Materialise ``n`` scenes as ml/datasets/processed/{images,masks}/<name> (paired by filename)."""
+def write_dataset(root: str, n: int, seed: int = 0, fmt: str = "png", n_classes: int = 1) -> int:
+    """Materialise ``n`` scenes as ml/datasets/processed/{images,masks}/<name> (paired by filename).
+    ``n_classes`` >= 2: K-class scenes, the mask's gray value is the class id."""
     import os
     from .image_io import imwrite
     img_dir, mask_dir = os.path.join(root, "images"), os.path.join(root, "masks")
     os.makedirs(img_dir, exist_ok=True)
     os.makedirs(mask_dir, exist_ok=True)
     for i in range(n):
-        s = make_scene(seed + i)
+        s = make_scene(seed + i, n_classes=n_classes)
         name = f"scene_{seed + i:05d}.{fmt}"
         imwrite(os.path.join(img_dir, name), s.color)
         imwrite(os.path.join(mask_dir, name), s.mask)

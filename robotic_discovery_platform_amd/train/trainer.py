@@ -16,13 +16,16 @@ step), DDP over RCCL with rank-0-only store writes, and a full resume checkpoint
 (model + Adam state + epoch + best val + RNG) beside the best-only one. Optional augmentation
 (``augment``, off by default; the reference has none): per-sample flip / rotate / scale / shift and
 contrast / brightness jitter, fused into the batch gather on the native backend (data/augment.py).
+K-class training (``n_classes`` 2..8; the reference is binary): UNet(3, K), softmax cross-entropy over
+integer class ids (255 = ignore). ``val_metrics``: per-epoch IoU / Dice / pixel accuracy from confusion
+counts accumulated on the device (train/metrics.py, csrc/seg_metrics.hip). Both are off by default.
 """
 from __future__ import annotations
 
 import logging
 import os
 import time
-from dataclasses import asdict
+from dataclasses import asdict, replace
 from typing import Optional
 
 import numpy as np
@@ -31,7 +34,8 @@ import torch.distributed as dist
 
 from .. import mlstore
 from ..config import TrainConfig
-from ..data.dataset import SegmentationDataset, SyntheticSegmentationDataset, preload, split_dataset
+from ..data.dataset import (SegmentationDataset, SyntheticSegmentationDataset, check_n_classes, parse_mask_values,
+                            preload, split_dataset)
 from ..data.synthetic import write_dataset
 from ..models.unet_ref import UNetRef
 from ..parallel.ddp import DistributedShardSampler, dist_info
@@ -49,6 +53,31 @@ def _pick_backend(cfg: TrainConfig, dev: torch.device) -> str:
     if cfg.backend != "auto":
         return cfg.backend
     return "native" if dev.type == "cuda" else "eager"
+
+
+def resolve_classes(cfg: TrainConfig) -> TrainConfig:
+    """Validate ``n_classes`` (1..8) and settle the loss of a K-class run: "ce"; the default "bce" is
+    switched to it, an explicit "bce_dice" raises as the trainers do. Returns ``cfg`` or an edited copy."""
+    k = check_n_classes(cfg.n_classes)
+    if k == 1:
+        return cfg
+    if cfg.loss == "bce":
+        log.info('n_classes = %d: the loss is softmax cross-entropy ("ce")', k)
+        return replace(cfg, loss="ce")
+    if cfg.loss != "ce":
+        raise ValueError(f'a {k}-class model trains with loss="ce" only, got {cfg.loss!r}')
+    return cfg
+
+
+def native_eval_batch(model, x, y, loss: str, dice_weight: float = 1.0, confusion=None) -> torch.Tensor:
+    """Eval-mode forward of one batch on the native executor; returns the device loss. ``confusion`` (a
+    ``ConfusionAccumulator``) also takes the batch's counts, from the executor's own logits / target."""
+    ex = model.executor(x.shape[0], x.shape[2], x.shape[3], training=False, loss=loss, dice_weight=dice_weight)
+    ex.set_input(x, y)
+    ex.forward()
+    if confusion is not None:
+        confusion.add_executor(ex)
+    return ex.loss[0]
 
 
 class _NativeRunner:
@@ -84,12 +113,8 @@ class _NativeRunner:
         tr.set_batch_resident(x_res, y_res, idx, params)
         return tr.step()[0]
 
-    def eval_loss(self, x, y) -> torch.Tensor:
-        ex = self.model.executor(x.shape[0], x.shape[2], x.shape[3], training=False, loss=self.cfg.loss,
-                                 dice_weight=self.cfg.dice_weight)
-        ex.set_input(x, y)
-        ex.forward()
-        return ex.loss[0]
+    def eval_loss(self, x, y, confusion=None) -> torch.Tensor:
+        return native_eval_batch(self.model, x, y, self.cfg.loss, self.cfg.dice_weight, confusion)
 
     def optimizer_state(self):
         return self._shared_opt.state_dict()
@@ -111,9 +136,12 @@ class _EagerRunner:
         return self.tr.step(x, y)
 
     @torch.no_grad()
-    def eval_loss(self, x, y):
+    def eval_loss(self, x, y, confusion=None):
         self.model.eval()
-        return self.tr.compute_loss(self.model(x), y)
+        out = self.model(x)
+        if confusion is not None:
+            confusion.add(out, y)
+        return self.tr.compute_loss(out, y)
 
     def optimizer_state(self):
         return self.tr.opt.state_dict()
@@ -122,15 +150,16 @@ class _EagerRunner:
         self.tr.opt.load_state_dict(sd)
 
 
-def _batches(x: torch.Tensor, y: torch.Tensor, order, bs: int, dev):
+def _batches(x: torch.Tensor, y: torch.Tensor, order, bs: int, dev, n_classes: int = 1):
     """Batches (float NCHW image, float N1HW mask) in ``order``; u8 device-resident data is gathered
-    and converted on the device."""
+    and converted on the device. K classes: the mask is the u8 [N,H,W] class ids, handed on as gathered."""
     if x.dtype == torch.uint8:
-        from ..data.device_data import batch_to_float
+        from ..data.device_data import batch_to_float, batch_to_float_ids
+        convert = batch_to_float_ids if n_classes > 1 else batch_to_float
         order = order.to(x.device)
         for i in range(0, len(order), bs):
             idx = order[i:i + bs]
-            yield batch_to_float(x.index_select(0, idx), y.index_select(0, idx))
+            yield convert(x.index_select(0, idx), y.index_select(0, idx))
         return
     for i in range(0, len(order), bs):
         idx = order[i:i + bs]
@@ -142,16 +171,23 @@ def build_dataset(cfg: TrainConfig):
     mask_dir = os.path.join(cfg.dataset_dir, "masks")
     size = (cfg.image_size, cfg.image_size)
     if os.path.isdir(img_dir) and os.path.isdir(mask_dir) and os.listdir(img_dir):
+        if cfg.n_classes > 1:
+            return SegmentationDataset(img_dir, mask_dir, size, n_classes=cfg.n_classes,
+                                       mask_values=parse_mask_values(cfg.mask_values))
         return SegmentationDataset(img_dir, mask_dir, size)
     if not cfg.synthetic_if_missing:
         raise FileNotFoundError(f"dataset not found at {cfg.dataset_dir}")
     log.info("dataset %s missing: using %d synthetic scenes", cfg.dataset_dir, cfg.synthetic_samples)
+    if cfg.n_classes > 1:
+        return SyntheticSegmentationDataset(cfg.synthetic_samples, size, seed=cfg.seed, n_classes=cfg.n_classes)
     return SyntheticSegmentationDataset(cfg.synthetic_samples, size, seed=cfg.seed)
 
 
 def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None) -> dict:
     cfg = cfg or TrainConfig()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
+    cfg = resolve_classes(cfg)
+    K = cfg.n_classes
     rank, world = dist_info()
     dev = _device()
     backend = _pick_backend(cfg, dev)
@@ -171,6 +207,8 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
                             "loss": cfg.loss, "dtype": cfg.dtype, "augment": cfg.augment})
         if cfg.augment:
             mlstore.log_params({k: v for k, v in asdict(cfg).items() if k.startswith("aug_")})
+        if K > 1:
+            mlstore.log_params({"n_classes": K, "mask_values": cfg.mask_values})
 
     # ---- data ----
     # GPU: the processed dataset is built once on the device (u8 NHWC; INTER_AREA / nearest resizes
@@ -192,16 +230,24 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
     sampler = DistributedShardSampler(len(train_set), rank, world, shuffle=True, seed=cfg.seed)
 
     # ---- model / engine ----
-    ref = UNetRef(3, 1, bilinear=cfg.bilinear, depth=cfg.model_depth)
+    ref = UNetRef(3, K, bilinear=cfg.bilinear, depth=cfg.model_depth)
     if backend == "native":
         from ..models.unet import UNetNative
-        model = UNetNative(3, 1, bilinear=cfg.bilinear, depth=cfg.model_depth, device=dev, init_from=ref)
+        model = UNetNative(3, K, bilinear=cfg.bilinear, depth=cfg.model_depth, device=dev, init_from=ref)
         runner = _NativeRunner(model, cfg)
     else:
         model = ref.to(dev)
         if cfg.sync_bn and dev.type == "cuda" and dist_info()[1] > 1:  # torch's SyncBatchNorm is GPU-only
             model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)
         runner = _EagerRunner(model, cfg, dev)
+
+    # validation metrics (off by default: nothing below changes then): the epoch's confusion counts, added
+    # up on the device by seg_confusion after each eval forward (native) or by the torch reference (eager)
+    confusion, best_miou = None, None
+    if cfg.val_metrics:
+        from .metrics import (ConfusionAccumulator, confusion_matrix, metric_items, metrics_from_confusion,
+                              threshold_logit)
+        confusion = ConfusionAccumulator(K, threshold_logit(cfg.mask_threshold), device=dev, native=backend == "native")
 
     start_epoch, best_val = 0, float("inf")
     ckpt_last = os.path.join(cfg.model_output_dir, "last_checkpoint.pt")
@@ -211,6 +257,7 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
         model.load_state_dict(state["model"])
         runner.load_optimizer_state(state["optimizer"])
         start_epoch, best_val = int(state["epoch"]) + 1, float(state["best_val"])
+        best_miou = state.get("best_val_miou")
         torch.set_rng_state(state["rng_cpu"])
         log.info("Resumed from epoch %d (best val %.4f)", start_epoch, best_val)
 
@@ -246,12 +293,13 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
                 tl += runner.train_step_resident(xtr, ytr, idx_dev[sl], params_dev[sl]).float()
                 nb += 1
         elif aug_spec is not None:
-            for xb, yb in _batches(xtr, ytr, order, cfg.batch_size, dev):
-                xb, yb = augment_batch_reference(xb, yb, params[nb * cfg.batch_size:(nb + 1) * cfg.batch_size])
+            for xb, yb in _batches(xtr, ytr, order, cfg.batch_size, dev, K):
+                xb, yb = augment_batch_reference(xb, yb, params[nb * cfg.batch_size:(nb + 1) * cfg.batch_size],
+                                                 n_classes=K)
                 tl += runner.train_step(xb, yb).float()
                 nb += 1
         else:
-            for xb, yb in _batches(xtr, ytr, order, cfg.batch_size, dev):
+            for xb, yb in _batches(xtr, ytr, order, cfg.batch_size, dev, K):
                 tl += runner.train_step(xb, yb).float()
                 nb += 1
         if dev.type == "cuda":
@@ -264,32 +312,56 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
         avg_train = float(tl.item()) / max(nb, 1)
         vl, nv = torch.zeros((), device=dev), 0
         if xva is not None and len(xva):
-            for xb, yb in _batches(xva, yva, torch.arange(len(xva)), cfg.batch_size, dev):
-                vl += runner.eval_loss(xb, yb).float()
+            if confusion is not None:
+                confusion.reset()
+            for xb, yb in _batches(xva, yva, torch.arange(len(xva)), cfg.batch_size, dev, K):
+                vl += (runner.eval_loss(xb, yb, confusion) if confusion is not None
+                       else runner.eval_loss(xb, yb)).float()
                 nv += 1
         avg_val = float(vl.item()) / max(nv, 1) if nv else avg_train
+        vm = None
+        if confusion is not None and nv:
+            # every rank validates the WHOLE validation set, so the counts are equal on all ranks: no
+            # collective is needed, and rank 0 logs its own
+            counts = confusion.result()  # the epoch's one read-back of the counts
+            vm = metrics_from_confusion(counts, K)
         dt = time.time() - t0
         history.append({"epoch": epoch, "train_loss": avg_train, "val_loss": avg_val, "epoch_s": dt,
                         "train_s": t_train, "train_imgs_per_s": len(order) * world / max(t_train, 1e-9)})
+        if vm is not None:
+            history[-1].update(val_metrics=vm, val_confusion=confusion_matrix(counts, K))
         if is_main:
             mlstore.log_metric("train_loss", avg_train, step=epoch)
             mlstore.log_metric("val_loss", avg_val, step=epoch)
             mlstore.log_metric("epoch_time_s", dt, step=epoch)
             mlstore.log_metric("train_imgs_per_s", len(order) * world / max(t_train, 1e-9), step=epoch)
             log.info("Epoch %d/%d: train %.4f val %.4f (%.1fs)", epoch + 1, cfg.epochs, avg_train, avg_val, dt)
+            if vm is not None:
+                for name, value in metric_items(vm, K):
+                    mlstore.log_metric(name, value, step=epoch)
+                log.info("Epoch %d/%d: val mIoU %.4f mDice %.4f pixel acc %.4f", epoch + 1, cfg.epochs, vm["miou"],
+                         vm["mdice"], vm["pixel_acc"])
             if avg_val < best_val:
+                if vm is not None:
+                    best_miou = vm["miou"]  # the value at the best-LOSS epoch: selection stays by val loss
                 best_val = avg_val
                 torch.save({k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()}, best_path)
                 log.info("New best model at epoch %d: val %.4f", epoch + 1, best_val)
-            torch.save({"model": {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()},
-                        "optimizer": _to_cpu(runner.optimizer_state()), "epoch": epoch, "best_val": best_val,
-                        "rng_cpu": torch.get_rng_state()}, ckpt_last)
+            ckpt = {"model": {k: v.detach().cpu().contiguous() for k, v in model.state_dict().items()},
+                    "optimizer": _to_cpu(runner.optimizer_state()), "epoch": epoch, "best_val": best_val,
+                    "rng_cpu": torch.get_rng_state()}
+            if best_miou is not None:
+                ckpt["best_val_miou"] = float(best_miou)
+            torch.save(ckpt, ckpt_last)
         if world > 1:
             dist.barrier()
 
     result = {"history": history, "best_val_loss": best_val, "backend": backend}
     if is_main:
         mlstore.log_metric("best_val_loss", best_val)
+        if confusion is not None and best_miou is not None:
+            mlstore.log_metric("best_val_miou", float(best_miou))
+            result["best_val_miou"] = float(best_miou)
         if os.path.exists(best_path):
             model.load_state_dict(torch.load(best_path, map_location="cpu", weights_only=True))
         info = mlstore.pytorch.log_model(model, name="model", registered_model_name=cfg.registered_model_name)
