@@ -4,6 +4,9 @@
 // of a wider tensor: pixel pitch = stride(2)). Every launcher validates shapes/strides here so a
 // kernel never sees an inconsistent view; the kernels themselves use buffer descriptors sized from
 // these views (out-of-range = zero / dropped, never a fault).
+//
+// The launchers (rdp_*) are declared once, with named parameters and their contracts, in csrc/rdp_api.h (GPU)
+// and csrc/rdp_host_api.h (host codecs / spline): no prototype is written here.
 #include <torch/extension.h>
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -19,132 +22,7 @@
 #include <vector>
 #include <array>
 
-extern "C" {
-int rdp_conv_igemm(const void*, const void*, long, long, int, int, int, int, const void*, long, int, void*, void*, long,
-                   long, int, int, int, float*, int, int, int, int, int, int, int, const float*, const float*, int,
-                   float*, long, void*, int, int*, void*, int, int, int, int, int, const void*, int, const float*,
-                   float*, int*, hipStream_t);
-int rdp_conv_rowband_ex(const void*, const void*, long, long, int, int, int, int, const void*, long, int, void*, long, int,
-                        int, int, int, int, const float*, const float*, int, void*, long, int, int, hipStream_t);
-int rdp_conv_rowband_frag_auto(int, int, int, int, int, int);
-int rdp_conv_rowband_chain(int, const void*, long, int, int, const void* const*, const long*, const int*, void* const*,
-                           const long*, const int*, const int*, const float* const*, const float* const*, int, int, int,
-                           int*, int*, hipStream_t);
-int rdp_conv_ring_ex(const void*, long, int, int, const void*, long, int, void*, long, int, void*, long, int, int, int,
-                     float*, int, int, int, const float*, const float*, int, int, const void*, int, const float*,
-                     const float*, const float*, void*, long, int, hipStream_t);
-long rdp_conv_ws_elems(int, int, int, int, int, int, int, int, int);
-int rdp_geo_nblocks(int);
-long rdp_geo_work_ints(int, int);
-int rdp_geo_edges(const void*, const void*, int, int, double, double, double, double, double, int*, double*, double*,
-                  double*, int, int*, double*, int, int*, int, double, int, double*, int, int*, const void*, int, int,
-                  int*, double*, int*, int, void*, hipStream_t);
-int rdp_preprocess(const void*, int, int, const int*, const int*, const float*, const int*, const int*, const float*, int,
-                   int, int, void*, hipStream_t);
-int rdp_mask_upsample(const void*, int, int, void*, int, int, unsigned*, hipStream_t);
-int rdp_conv_wgrad(const void*, const void*, long, long, int, int, int, int, const void*, long, int, float*, long,
-                   float*, int, int, int, int, int, int, int, int, int, int, hipStream_t);
-long rdp_conv_wgrad_slab_elems(int, int, int, int, int, int, int, int);
-long rdp_conv_wgrad_halo_slab_elems(int, int, int, int, int);
-int rdp_wgrad_first_bn(const void*, long, int, const void*, long, int, const void*, long, int, const float*, const float*,
-                       float*, long, float*, int, int, int, int, int, int, hipStream_t);
-int rdp_bn_finalize(const float*, int, int, long, const float*, const float*, float*, float*, long long*, float, float,
-                    float*, float*, hipStream_t);
-int rdp_bn_eval_coef(int, const float*, const float*, const float*, const float*, float, float*, hipStream_t);
-int rdp_bn_relu_apply(const void*, int, void*, int, const float*, int, int, int, hipStream_t);
-int rdp_bn_relu_bwd_reduce(const void*, int, const void*, int, const float*, int, int, int, float*, int, hipStream_t);
-int rdp_bn_bwd_finalize(const float*, int, int, long, const float*, const float*, float*, float*, float*, float*,
-                        hipStream_t);
-int rdp_bn_relu_bwd_apply(const void*, int, const void*, int, const float*, const float*, void*, int, int, int, int,
-                          hipStream_t);
-int rdp_maxpool2_fwd(const void*, int, void*, int, int, int, int, int, hipStream_t);
-int rdp_conv_ring_head(const void*, long, int, int, const void*, long, int, int, int, int, int, const float*,
-                       const float*, const float*, const float*, float, void*, hipStream_t);
-int rdp_maxpool2_bwd(const void*, int, const void*, int, const void*, int, void*, int, int, int, int, int, hipStream_t);
-int rdp_bn_relu_apply_pool(const void*, int, void*, int, void*, int, const float*, int, int, int, int, hipStream_t);
-int rdp_maxpool2_bwd_bn_reduce(const void*, int, const void*, int, const void*, int, void*, int, const void*, int,
-                               const float*, int, int, int, int, float*, int, hipStream_t);
-int rdp_upsample2_fwd(const void*, int, void*, int, int, int, int, int, int, int, int, int, const float*,
-                      hipStream_t);
-int rdp_upsample2_bwd(const void*, int, void*, int, int, int, int, int, int, int, int, int, const void*, int,
-                      const float*, float*, int, hipStream_t);
-int rdp_conv_upT_fwd(const void*, long, int, int, const void*, long, int, void*, long, int, const float*, int, int, int, int,
-                     int, int, int, int, hipStream_t);
-int rdp_conv_upT_dgrad(const void*, long, int, int, int, int, int, int, const void*, long, int, void*, long, int, int,
-                       int, int, int, hipStream_t);
-int rdp_conv_wgrad_upT(const void*, long, int, int, int, int, int, int, const void*, long, int, int, int, int, int,
-                       float*, long, float*, int, int, hipStream_t);
-int rdp_upT_shuffle(const void*, int, const float*, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
-int rdp_upT_unshuffle(const void*, int, void*, int, int, int, int, int, int, int, int, int, hipStream_t);
-int rdp_colsum_bf16(const void*, int, long, int, int, float*, float*, int, hipStream_t);
-int rdp_head_partial_blocks(long);
-int rdp_head_fwd(const void*, int, const float*, const float*, const float*, float*, float*, float*, float*, int, float,
-                 float, const float*, float*, float*, float, hipStream_t);
-int rdp_head_grad_finalize(const float*, int, float*, float*, hipStream_t);
-int rdp_head_bwd(const void*, int, const float*, const float*, const float*, const float*, void*, int, float*, float*,
-                 float*, int, float, float, float, const float*, float*, hipStream_t);
-int rdp_head_bn_bwd_apply(const void*, int, const float*, const float*, const float*, const float*, const float*,
-                          const float*, void*, int, int, float, float, float, hipStream_t);
-int rdp_head_mask(const void*, int, const float*, const float*, float, void*, int, hipStream_t);
-int rdp_headk_partial_blocks(long);
-int rdp_headk_fwd(const void*, int, const float*, const float*, const void*, float*, float*, float*, float*, int, int,
-                  hipStream_t);
-int rdp_headk_bwd(const void*, int, const float*, const float*, const void*, const float*, void*, int, float*, float*,
-                  float*, int, int, float, hipStream_t);
-int rdp_headk_mask(const void*, int, const float*, const float*, int, void*, int, int, hipStream_t);
-int rdp_seg_confusion_blocks(long);
-int rdp_seg_confusion_block_pixels();
-int rdp_seg_confusion(const float*, const void*, void*, long, int, float, int, hipStream_t);
-int rdp_adam(float*, const void*, int, float*, float*, void*, long, float, float, float, float, float, float, int*, int,
-             int, hipStream_t);
-int rdp_cast_bf16(const float*, void*, long, hipStream_t);
-int rdp_comm_emulate(double, int, hipStream_t);
-int rdp_comm_emulate_traffic(double, int, void*, long, long, hipStream_t);
-int rdp_rows_fold(const float*, int, int, double*, hipStream_t);
-int rdp_rows_hilo(const double*, float*, int, hipStream_t);
-int rdp_wprep(const float*, void*, const void*, int, int*, int, int, hipStream_t);
-int rdp_wseg_size();
-int rdp_h2d_copy(const void*, void*, long, hipStream_t);
-int rdp_parcur(int, int, const double*, const double*, double, int, int, double*, double*, int*, double*);
-double rdp_splev1(const double*, int, const double*, int, double, int);
-int rdp_fit_curvature(const double*, int, double, int, int, double, double*, double*);
-int rdp_geo_spline_res_len(int);
-int rdp_preprocess_batch(int, const void* const*, int, int, const int*, const int*, const float*, const int*,
-                         const int*, const float*, int, int, int, void* const*, hipStream_t);
-int rdp_jpeg_gpu_batch(int, const void* const*, const int* const*, const int* const*, void* const*, int, int, int,
-                       void* const*, hipStream_t);
-int rdp_geo_edges_batch(int, const void* const*, const void* const*, int, int, double, double, double, double, double,
-                        int* const*, double* const*, double* const*, double* const*, int, int* const*, double* const*,
-                        int, int* const*, int, double, int, const void* const*, int, int, int* const*, double* const*,
-                        int* const*, int, void* const*, hipStream_t);
-int rdp_geo_spline_batch(int, int, int, const int* const*, const int* const*, double* const*, double* const*, int,
-                         double, int, int, double, int, int, const int* const*, int, double* const*, const void* const*,
-                         void* const*, long, hipStream_t);
-int rdp_png_info(const uint8_t*, long, int*, int*, int*);
-long rdp_jpeg_info(const uint8_t*, long, int*);
-void rdp_jpeg_meta(const int*, int*);
-int rdp_jpeg_decode(const uint8_t*, long, int16_t*, long, uint16_t*, int);
-int rdp_jpeg_gpu(const void*, const int*, const int*, void*, int, int, int, void*, hipStream_t);
-long rdp_jpeg_plane_bytes(int, int);
-long rdp_jpeg_tables_bytes();
-long rdp_jpeg_entropy_work_words(long, int);
-long rdp_jpeg_scan_bound(const uint8_t*, long);
-int rdp_jpeg_scan(const uint8_t*, long, int*, uint8_t*, uint8_t*, long, int*);
-int rdp_jpeg_entropy_emulate(const uint8_t*, long, int, const uint8_t*, const int*, int16_t*, long, int, int*, int*);
-int rdp_jpeg_entropy_gpu(const void*, long, const int*, const void*, const int*, void*, long, int*, long, int*, int,
-                         long*, hipStream_t);
-long rdp_jpeg_max_coefs(int, int);
-int rdp_png_decode(const uint8_t*, long, uint8_t*, long, int);
-long rdp_png_encode_gray(const uint8_t*, int, int, int, int, int, uint8_t*, long);
-long rdp_png_encode_bound(int, int, int, int);
-int rdp_area_maxtap();
-int rdp_resize_area_u8(const void*, int, int, int, const int*, const int*, const double*, const int*, const int*,
-                       const double*, int, int, int, void*, hipStream_t);
-int rdp_batch_augment(const void*, const void*, const int*, const float*, int, int, int, int, void*, float*, void*,
-                      hipStream_t);
-int rdp_geo_spline(const double*, int, int, const int*, const int*, double*, int*, double*, int, double, int, int,
-                   double, int, int, const int*, int, double*, double*, int, const void*, void*, long, hipStream_t);
-}
+#include "rdp_api.h"
 
 namespace {
 
@@ -538,6 +416,9 @@ struct Act {
   void* ptr = nullptr;
   int N = 0, H = 0, W = 0, C = 0, pitch = 0;
   long bytes = 0;
+  long image_bytes() const { return (long)H * W * pitch * 2; }            // from one image to the next
+  void* image(int n) const { return (char*)ptr + n * image_bytes(); }     // image n
+  long span_bytes(int n) const { return ((long)n * H * W - 1) * pitch * 2 + (long)C * 2; }  // extent of n images
 };
 
 Act act(const torch::Tensor& t, const char* name) {
@@ -553,7 +434,7 @@ Act act(const torch::Tensor& t, const char* name) {
               ": pixels must be densely packed (only channel slicing allowed)");
   TORCH_CHECK(a.pitch % 8 == 0 && ((uintptr_t)t.data_ptr() % 16) == 0, name, ": pitch/base must be 16-B aligned");
   a.ptr = t.data_ptr();
-  a.bytes = ((long)a.N * a.H * a.W - 1) * a.pitch * 2 + (long)a.C * 2;
+  a.bytes = a.span_bytes(a.N);
   return a;
 }
 
@@ -569,9 +450,44 @@ int chunk_images(long bytes_per_image, int N) {
   return (int)std::max(1L, lim / bytes_per_image);
 }
 
+// Images per launch so that each of `ts` stays below 2 GiB (an undefined optional Act counts as empty)
+int chunk_images(std::initializer_list<Act> ts, int N) {
+  long per_img = 0;
+  for (const Act& t : ts) per_img = std::max(per_img, t.image_bytes());
+  return chunk_images(per_img, N);
+}
+
+// One source or destination of a conv operand block = images [n0, n0 + nn) of t; x1 also sets the block's
+// N / H / W, y1 the channel split. An undefined optional Act leaves its slot empty.
+enum ConvSlot { kX1, kX2, kY1, kY2 };
+void conv_bind(RdpConv& c, ConvSlot slot, const Act& t, int n0, int nn) {
+  if (!t.ptr) return;
+  void* const p = t.image(n0);
+  const long b = t.span_bytes(nn);
+  switch (slot) {
+    case kX1: c.x1 = p; c.xbytes1 = b; c.C1 = t.C; c.pitch1 = t.pitch; c.N = nn; c.H = t.H; c.W = t.W; break;
+    case kX2: c.x2 = p; c.xbytes2 = b; c.C2 = t.C; c.pitch2 = t.pitch; break;
+    case kY1: c.y1 = p; c.ybytes1 = b; c.Cy1 = t.C; c.ypitch1 = t.pitch; break;
+    case kY2: c.y2 = p; c.ybytes2 = b; c.ypitch2 = t.pitch; break;
+  }
+}
+
 void check_f32(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous(), name,
               ": must be a contiguous fp32 GPU tensor");
+}
+
+void check_w(const torch::Tensor& w) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous() && w.dim() == 2,
+              "w: bf16 [Cout][K]");
+}
+
+// the OHWI weights of a conv operand block
+void conv_weights(RdpConv& c, const torch::Tensor& w) {
+  check_w(w);
+  c.w = w.data_ptr();
+  c.wbytes = w.numel() * 2;
+  c.ldw = (int)w.size(1);
 }
 
 // reduction workspace for the two-stage BN finalize (>= 64 rows x K floats), or nullptr
@@ -609,7 +525,7 @@ int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w,
     a2 = act(*x2, "x2");
     TORCH_CHECK(a2.N == a1.N && a2.H == a1.H && a2.W == a1.W, "x2 spatial mismatch");
   }
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous() && w.dim() == 2, "w: bf16 [Cout][K]");
+  check_w(w);
   Act o1 = act(y1, "y1"), o2;
   int Cout = o1.C;
   if (y2) { o2 = act(*y2, "y2"); Cout += o2.C; }
@@ -652,45 +568,43 @@ int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w,
   // offsets (< 2 GiB), so a batch whose largest tensor passes that (256^2 x 64 ch bf16 at N >= 256)
   // runs as consecutive launches over image slices (convs never cross images); BN partial rows of
   // the slices are appended, fused pool / upsample outputs sliced alike.
-  const long per_img = std::max(std::max((long)a1.H * a1.W * a1.pitch, x2 ? (long)a2.H * a2.W * a2.pitch : 0L),
-                                std::max((long)o1.H * o1.W * o1.pitch, y2 ? (long)o2.H * o2.W * o2.pitch : 0L)) * 2;
-  const int nc = chunk_images(per_img, a1.N);
+  const int nc = chunk_images({a1, a2, o1, o2}, a1.N);
   const long avail_rows = stats ? stats->numel() / (2l * Cout) : 0;
   int rows = 0;
   for (int n0 = 0; n0 < a1.N; n0 += nc) {
     const int nn = std::min(nc, a1.N - n0);
-    // every launch argument is a value here: RDP_PLAN may keep the launch for replay (plan mode)
-    auto img = [](const Act& t, int n) { return (void*)((char*)t.ptr + (long)n * t.H * t.W * t.pitch * 2); };
-    auto nbytes = [nn](const Act& t) { return ((long)nn * t.H * t.W - 1) * t.pitch * 2 + (long)t.C * 2; };
-    float* spc = sp ? sp + (long)rows * 2 * Cout : nullptr;
     if (sp) TORCH_CHECK(rows + conv_stats_rows((long)nn * a1.H * a1.W, Cout, bm_pref) <= avail_rows, "stats slab too small");
-    void* const px1 = img(a1, n0);
-    void* const px2 = x2 ? img(a2, n0) : nullptr;
-    void* const py1 = img(o1, n0);
-    void* const py2 = y2 ? img(o2, n0) : nullptr;
-    void* const ppo = pool ? img(po, n0) : nullptr;
-    void* const pup = up ? img(uo, n0) : nullptr;
-    const long bx1 = nbytes(a1), bx2 = x2 ? nbytes(a2) : 0, by1 = nbytes(o1), by2 = y2 ? nbytes(o2) : 0;
-    void* const wp = w.data_ptr();
-    const long wb = w.numel() * 2, ldw = w.size(1);
+    // every launch argument is a value here (the blocks are captured by copy): RDP_PLAN may keep the launch for
+    // replay (plan mode)
+    RdpConv c;
+    conv_bind(c, kX1, a1, n0, nn);
+    conv_bind(c, kX2, a2, n0, nn);
+    conv_bind(c, kY1, o1, n0, nn);
+    conv_bind(c, kY2, o2, n0, nn);
+    conv_weights(c, w);
+    c.stats = sp ? sp + (long)rows * 2 * Cout : nullptr;
+    c.Cout = Cout;
+    c.escale = esc; c.eshift = esh; c.erelu = relu;
+    RdpConvFuse fuse;
+    if (pool) { fuse.pool = po.image(n0); fuse.ppitch = po.pitch; }
+    if (up) {
+      fuse.up = uo.image(n0); fuse.upitch = uo.pitch; fuse.uH = uo.H; fuse.uW = uo.W;
+      fuse.uoy = up_oy; fuse.uox = up_ox;
+    }
     float* const wsp = ws ? ws->data_ptr<float>() : nullptr;
     const long wsn = ws ? (long)ws->numel() : 0L;
-    const int C2 = x2 ? a2.C : 0, p2 = x2 ? a2.pitch : 0, yp2 = y2 ? o2.pitch : 0, ppit = pool ? po.pitch : 0;
-    const int upit = up ? uo.pitch : 0, uH = up ? uo.H : 0, uW = up ? uo.W : 0;
     const bool want_fused = pool || up;
     // the fused pool / upsample result flag: a heap cell owned by the launch (kept alive in a plan)
     auto pooled = std::make_shared<int>(0);
     // eval with the fragment-major weight copy (wfrag): the row-band kernel wherever its traffic model picks it
     const int fmode = wfrag && esc && !sp && !y2 && taps == 9 && !packed && bm_pref == 0
-                          ? rdp_conv_rowband_frag_auto(nn, a1.H, a1.W, a1.C, C2, Cout) : 0;
+                          ? rdp_conv_rowband_frag_auto(nn, a1.H, a1.W, a1.C, c.C2, Cout) : 0;
     int r = -1;
     if (fmode > 0) {
-      void* const wfp = wfrag->data_ptr();
-      const long wfb = wfrag->numel() * 2;
-      const long pbytes = pool ? ((long)nn * po.H * po.W - 1) * ppit * 2 + (long)po.C * 2 : 0;
-      const int rb = RDP_PLAN(rdp_conv_rowband_ex(px1, px2, bx1, bx2, a1.C, C2, a1.pitch, p2, wfp, wfb, 0, py1, by1,
-                                                  o1.pitch, nn, a1.H, a1.W, Cout, esc, esh, relu, ppo, pbytes, ppit, fmode,
-                                                  st));
+      RdpConv cf = c;
+      cf.w = wfrag->data_ptr(); cf.wbytes = wfrag->numel() * 2; cf.ldw = 0;
+      const long pbytes = pool ? po.span_bytes(nn) : 0;
+      const int rb = RDP_PLAN(rdp_conv_rowband_ex(cf, fuse.pool, pbytes, fuse.ppitch, fmode, st));
       // the selector checks every predicate of the launch; should one still reject (rb < 0: nothing was
       // launched), the layer runs on the implicit GEMM below instead of failing the eval
       if (rb >= 0) {
@@ -699,17 +613,19 @@ int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w,
       }
     }
     if (r < 0) {
-      r = RDP_PLAN(rdp_conv_igemm(px1, px2, bx1, bx2, a1.C, C2, a1.pitch, p2, wp, wb, (int)ldw, py1, py2, by1, by2, o1.C,
-                                  o1.pitch, yp2, spc, nn, a1.H, a1.W, Cout, taps, packed, bm_pref, esc, esh, relu, wsp,
-                                  wsn, ppo, ppit, want_fused ? pooled.get() : nullptr, pup, upit, uH, uW, up_oy, up_ox,
-                                  nullptr, 0, nullptr, nullptr, nullptr, st));
+      // `pooled` is named inside the closure so that a recorded launch owns the cell it writes on every replay
+      r = RDP_PLAN(rdp_conv_igemm(c, taps, packed, bm_pref, wsp, wsn, fuse, want_fused ? pooled.get() : nullptr,
+                                  RdpConvBnBwd{}, nullptr, st));
     }
-    TORCH_CHECK(r >= 0, "conv_fwd: unsupported shape (C1=", a1.C, ", C2=", C2, ", Cout=", Cout, ")");
-    const int oN = nn, oH = o1.H, oW = o1.W, oC = o1.C, op1 = o1.pitch;
+    TORCH_CHECK(r >= 0, "conv_fwd: unsupported shape (C1=", a1.C, ", C2=", c.C2, ", Cout=", Cout, ")");
+    void* const py1 = c.y1;
+    const int oH = o1.H, oW = o1.W, oC = o1.C, op1 = o1.pitch;
     if (pool && !*pooled)
-      TORCH_CHECK(RDP_PLAN(rdp_maxpool2_fwd(py1, op1, ppo, ppit, oN, oH, oW, oC, st)) == 0, "conv_fwd: maxpool");
+      TORCH_CHECK(RDP_PLAN(rdp_maxpool2_fwd(py1, op1, fuse.pool, fuse.ppitch, nn, oH, oW, oC, st)) == 0,
+                  "conv_fwd: maxpool");
     if (up && !*pooled)
-      TORCH_CHECK(RDP_PLAN(rdp_upsample2_fwd(py1, op1, pup, upit, oN, oH, oW, uH, uW, up_oy, up_ox, oC, nullptr, st)) == 0,
+      TORCH_CHECK(RDP_PLAN(rdp_upsample2_fwd(py1, op1, fuse.up, fuse.upitch, nn, oH, oW, fuse.uH, fuse.uW, fuse.uoy,
+                                             fuse.uox, oC, nullptr, st)) == 0,
                   "conv_fwd: upsample");
     rows += r;
   }
@@ -728,18 +644,14 @@ int conv_wgrad(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor 
   const int Cin = packed ? cin_real : a1.C + (x2 ? a2.C : 0);
   TORCH_CHECK(out.numel() == (long)d.C * taps * Cin, "wgrad out numel mismatch");
   // batch chunks below the 2 GiB buffer-offset reach (see conv_fwd), accumulated into out
-  const long per_img = std::max(std::max((long)a1.H * a1.W * a1.pitch, x2 ? (long)a2.H * a2.W * a2.pitch : 0L),
-                                (long)d.H * d.W * d.pitch) * 2;
-  const int nc = chunk_images(per_img, a1.N);
+  const int nc = chunk_images({a1, a2, d}, a1.N);
   int r = 0;
   for (int n0 = 0; n0 < a1.N; n0 += nc) {
     const int nn = std::min(nc, a1.N - n0);
-    auto img = [n0](const Act& t) { return (void*)((char*)t.ptr + (long)n0 * t.H * t.W * t.pitch * 2); };
-    auto nbytes = [nn](const Act& t) { return ((long)nn * t.H * t.W - 1) * t.pitch * 2 + (long)t.C * 2; };
-    void* const px1 = img(a1);
-    void* const px2 = x2 ? img(a2) : nullptr;
-    void* const pdy = img(d);
-    const long bx1 = nbytes(a1), bx2 = x2 ? nbytes(a2) : 0, bdy = nbytes(d);
+    void* const px1 = a1.image(n0);
+    void* const px2 = x2 ? a2.image(n0) : nullptr;
+    void* const pdy = d.image(n0);
+    const long bx1 = a1.span_bytes(nn), bx2 = x2 ? a2.span_bytes(nn) : 0, bdy = d.span_bytes(nn);
     const int C2 = x2 ? a2.C : 0, p2 = x2 ? a2.pitch : 0, acc = n0 > 0 ? 1 : accumulate;
     float* const slp = slab.data_ptr<float>();
     const long sln = slab.numel();
@@ -816,7 +728,7 @@ void bn_relu_apply(torch::Tensor y, torch::Tensor out, torch::Tensor coef, int r
 int conv_dgrad_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, torch::Tensor y_bn, torch::Tensor coef,
                      torch::Tensor partial) {
   Act a = act(dy, "dy"), o = act(dx, "dx"), b = act(y_bn, "y_bn");
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous() && w.dim() == 2, "w: bf16 [Cout][K]");
+  check_w(w);
   TORCH_CHECK(o.N == a.N && o.H == a.H && o.W == a.W && b.N == a.N && b.H == a.H && b.W == a.W && b.C == o.C,
               "conv_dgrad_bnred: shape mismatch");
   TORCH_CHECK(w.size(0) == o.C, "w rows != Cout");
@@ -826,11 +738,16 @@ int conv_dgrad_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, torch:
   // ring grid <= 256 blocks x 4 pixel groups (64 couts) or 2 (128): <= 1024 rows of 2*C
   TORCH_CHECK(partial.numel() >= 1024l * 2 * o.C, "partial too small");
   // batches past the 2 GiB buffer-offset reach: the caller's chunked conv_fwd + bn_relu_bwd_reduce
-  const long per_img = std::max(std::max((long)a.H * a.W * a.pitch, (long)o.H * o.W * o.pitch), (long)b.H * b.W * b.pitch) * 2;
-  if (chunk_images(per_img, a.N) < a.N) return -1;
-  return RDP_PLAN(rdp_conv_ring_ex(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, w.size(1), o.ptr, o.bytes,
-                          o.pitch, nullptr, 0, 0, o.C, o.C, partial.data_ptr<float>(), a.N, a.H, a.W, nullptr, nullptr,
-                          0, 256, b.ptr, b.pitch, coef.data_ptr<float>(), nullptr, nullptr, nullptr, 0, 0, st));
+  if (chunk_images({a, o, b}, a.N) < a.N) return -1;
+  RdpConv c;
+  conv_bind(c, kX1, a, 0, a.N);
+  conv_bind(c, kY1, o, 0, a.N);
+  conv_weights(c, w);
+  c.Cout = o.C;
+  c.stats = partial.data_ptr<float>();
+  RdpRingFuse f;
+  f.bn_y = b.ptr; f.bn_ypitch = b.pitch; f.bn_coef = coef.data_ptr<float>();
+  return RDP_PLAN(rdp_conv_ring_ex(c, 256, f, st));
 }
 
 // 3x3 dgrad into one BN + ReLU layer's activation gradient (dx, one destination) through the implicit-GEMM
@@ -842,7 +759,7 @@ int conv_dgrad_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, torch:
 int conv_dgrad_splitk_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, torch::Tensor y_bn,
                             torch::Tensor coef, torch::Tensor partial, c10::optional<torch::Tensor> ws) {
   Act a = act(dy, "dy"), o = act(dx, "dx"), b = act(y_bn, "y_bn");
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous() && w.dim() == 2, "w: bf16 [Cout][K]");
+  check_w(w);
   TORCH_CHECK(o.N == a.N && o.H == a.H && o.W == a.W && b.N == a.N && b.H == a.H && b.W == a.W && b.C == o.C,
               "conv_dgrad_splitk_bnred: shape mismatch");
   TORCH_CHECK(w.size(0) == o.C && w.size(1) >= 9l * a.C, "conv_dgrad_splitk_bnred: w must be [Cout][9 * Cin]");
@@ -851,24 +768,21 @@ int conv_dgrad_splitk_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx,
   TORCH_CHECK(coef.numel() >= 4l * o.C, "coef must hold 4*C floats");
   TORCH_CHECK(partial.numel() >= 512l * 2 * o.C, "partial too small");  // the split-K reduce: <= 512 rows
   if (ws) check_f32(*ws, "ws");
-  const long per_img = std::max(std::max((long)a.H * a.W * a.pitch, (long)o.H * o.W * o.pitch), (long)b.H * b.W * b.pitch) * 2;
-  if (chunk_images(per_img, a.N) < a.N) return -1;
-  auto rows = std::make_shared<int>(0);
-  void* const px = a.ptr;
-  void* const py = o.ptr;
-  void* const pyb = b.ptr;
-  void* const wp = w.data_ptr();
-  const long wb = w.numel() * 2, bx = a.bytes, by = o.bytes;
-  const int ldw = (int)w.size(1), C1 = a.C, p1 = a.pitch, Co = o.C, op = o.pitch, ypb = b.pitch, N = a.N, H = a.H,
-            W = a.W;
-  const float* const cf = coef.data_ptr<float>();
-  float* const pp = partial.data_ptr<float>();
+  if (chunk_images({a, o, b}, a.N) < a.N) return -1;
+  RdpConv c;
+  conv_bind(c, kX1, a, 0, a.N);
+  conv_bind(c, kY1, o, 0, a.N);
+  conv_weights(c, w);
+  c.Cout = o.C;
+  RdpConvBnBwd bn;
+  bn.bny = b.ptr; bn.bnypitch = b.pitch; bn.bncoef = coef.data_ptr<float>(); bn.bnpart = partial.data_ptr<float>();
   float* const wsp = ws ? ws->data_ptr<float>() : nullptr;
   const long wsn = ws ? (long)ws->numel() : 0L;
-  const int r = RDP_PLAN(rdp_conv_igemm(px, nullptr, bx, 0, C1, 0, p1, 0, wp, wb, ldw, py, nullptr, by, 0, Co, op, 0,
-                                        nullptr, N, H, W, Co, 9, 0, 0, nullptr, nullptr, 0, wsp, wsn, nullptr, 0,
-                                        nullptr, nullptr, 0, 0, 0, 0, 0, pyb, ypb, cf, pp, rows.get(), st));
-  TORCH_CHECK(r >= 0, "conv_dgrad_splitk_bnred: unsupported shape (Cin=", C1, ", Cout=", Co, ")");
+  // the row-count cell: owned by the launch; `rows` is named inside the closure so that a recorded launch keeps
+  // the cell it writes on every replay alive
+  auto rows = std::make_shared<int>(0);
+  const int r = RDP_PLAN(rdp_conv_igemm(c, 9, 0, 0, wsp, wsn, RdpConvFuse{}, nullptr, bn, rows.get(), st));
+  TORCH_CHECK(r >= 0, "conv_dgrad_splitk_bnred: unsupported shape (Cin=", a.C, ", Cout=", o.C, ")");
   return *rows;
 }
 
@@ -881,28 +795,29 @@ int conv_dgrad_splitk_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx,
 int conv_fwd_bnin(torch::Tensor x_pre, torch::Tensor w, torch::Tensor y, torch::Tensor stats, torch::Tensor in_coef,
                   c10::optional<torch::Tensor> a_out) {
   Act a = act(x_pre, "x_pre"), o = act(y, "y");
-  void* aptr = nullptr;
-  long abytes = 0;
-  int apitch = 0;
+  RdpRingFuse f;
   if (a_out && a_out->defined()) {
     Act q = act(*a_out, "a_out");
     TORCH_CHECK(q.N == a.N && q.H == a.H && q.W == a.W && q.C == a.C, "conv_fwd_bnin: a_out shape");
-    aptr = q.ptr; abytes = q.bytes; apitch = q.pitch;
+    f.aout = q.ptr; f.abytes = q.bytes; f.apitch = q.pitch;
   }
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous() && w.dim() == 2, "w: bf16 [Cout][K]");
+  check_w(w);
   TORCH_CHECK(o.N == a.N && o.H == a.H && o.W == a.W && w.size(0) == o.C, "conv_fwd_bnin: shape mismatch");
   check_f32(stats, "stats");
   check_f32(in_coef, "in_coef");
   TORCH_CHECK(in_coef.numel() >= 4l * a.C, "in_coef: [4 C] f32");
   // (the ring grid writes <= 256 blocks x 4 pixel-group rows of 2 * C)
   if (a.C != 64 || o.C != 64 || a.W % 64 || a.H % 2 || stats.numel() < 1024l * 2 * o.C) return -1;
-  const long per_img = std::max((long)a.H * a.W * a.pitch, (long)o.H * o.W * o.pitch) * 2;
-  if (chunk_images(per_img, a.N) < a.N) return -1;
-  const float* c = in_coef.data_ptr<float>();
-  return RDP_PLAN(rdp_conv_ring_ex(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, w.size(1), o.ptr, o.bytes,
-                                   o.pitch, nullptr, 0, 0, o.C, o.C, stats.data_ptr<float>(), a.N, a.H, a.W, nullptr,
-                                   nullptr, 0, 256, nullptr, 0, nullptr, c + 2 * a.C, c + 3 * a.C, aptr, abytes, apitch,
-                                   st));
+  if (chunk_images({a, o}, a.N) < a.N) return -1;
+  RdpConv c;
+  conv_bind(c, kX1, a, 0, a.N);
+  conv_bind(c, kY1, o, 0, a.N);
+  conv_weights(c, w);
+  c.Cout = o.C;
+  c.stats = stats.data_ptr<float>();
+  f.iscale = in_coef.data_ptr<float>() + 2 * a.C;
+  f.ishift = in_coef.data_ptr<float>() + 3 * a.C;
+  return RDP_PLAN(rdp_conv_ring_ex(c, 256, f, st));
 }
 
 int bn_relu_bwd_reduce(torch::Tensor da, torch::Tensor y, torch::Tensor coef, int relu, torch::Tensor partial) {
@@ -1047,10 +962,8 @@ int conv_upT_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor bias, torch::Te
                   w.size(1) >= a.C, "conv_upT_fwd: w must be bf16 [4C][>= Cin]");
   TORCH_CHECK(a.N == o.N && bias.numel() == o.C, "conv_upT_fwd shapes");
   TORCH_CHECK(oy >= 0 && ox >= 0 && 2 * a.H + oy <= o.H && 2 * a.W + ox <= o.W, "conv_upT_fwd placement");
-  const long xb = ((long)a.N * a.H * a.W - 1) * a.pitch * 2 + (long)a.C * 2;
-  const long ub = ((long)o.N * o.H * o.W - 1) * o.pitch * 2 + (long)o.C * 2;
-  return RDP_PLAN(rdp_conv_upT_fwd(a.ptr, xb, a.C, a.pitch, w.data_ptr(), w.numel() * 2, (int)w.size(1), o.ptr, ub,
-                                   o.pitch, bias.data_ptr<float>(), a.N, a.H, a.W, o.H, o.W, oy, ox, o.C, st));
+  return RDP_PLAN(rdp_conv_upT_fwd(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, (int)w.size(1), o.ptr,
+                                   o.bytes, o.pitch, bias.data_ptr<float>(), a.N, a.H, a.W, o.H, o.W, oy, ox, o.C, st));
 }
 
 // ConvTranspose2d(2, s2) input gradient dx [N,h,w,Cin] read straight from du (its 4 sub-pixels per
@@ -1061,10 +974,8 @@ int conv_upT_dgrad(torch::Tensor du, torch::Tensor wd, torch::Tensor dx, int oy,
   TORCH_CHECK(wd.scalar_type() == torch::kBFloat16 && wd.is_contiguous() && wd.dim() == 2 && wd.size(0) == o.C &&
                   wd.size(1) >= 4 * d.C, "conv_upT_dgrad: wd must be bf16 [Cin][>= 4C]");
   TORCH_CHECK(d.N == o.N && oy >= 0 && ox >= 0 && 2 * o.H + oy <= d.H && 2 * o.W + ox <= d.W, "conv_upT_dgrad placement");
-  const long db = ((long)d.N * d.H * d.W - 1) * d.pitch * 2 + (long)d.C * 2;
-  const long ob = ((long)o.N * o.H * o.W - 1) * o.pitch * 2 + (long)o.C * 2;
-  return RDP_PLAN(rdp_conv_upT_dgrad(d.ptr, db, d.C, d.pitch, d.H, d.W, oy, ox, wd.data_ptr(), wd.numel() * 2,
-                                     (int)wd.size(1), o.ptr, ob, o.C, o.pitch, o.N, o.H, o.W, st));
+  return RDP_PLAN(rdp_conv_upT_dgrad(d.ptr, d.bytes, d.C, d.pitch, d.H, d.W, oy, ox, wd.data_ptr(), wd.numel() * 2,
+                                     (int)wd.size(1), o.ptr, o.bytes, o.C, o.pitch, o.N, o.H, o.W, st));
 }
 
 // ConvTranspose2d(2, s2) weight gradient out [Cin][4C] (+)= from du (4 sub-pixels per pixel of x) and
@@ -1076,10 +987,9 @@ int conv_wgrad_upT(torch::Tensor du, torch::Tensor x, int oy, int ox, torch::Ten
   check_f32(out, "out");
   TORCH_CHECK(out.numel() == (long)a.C * 4 * d.C, "conv_wgrad_upT out numel");
   TORCH_CHECK(d.N == a.N && oy >= 0 && ox >= 0 && 2 * a.H + oy <= d.H && 2 * a.W + ox <= d.W, "conv_wgrad_upT placement");
-  const long db = ((long)d.N * d.H * d.W - 1) * d.pitch * 2 + (long)d.C * 2;
-  const long xb = ((long)a.N * a.H * a.W - 1) * a.pitch * 2 + (long)a.C * 2;
-  return RDP_PLAN(rdp_conv_wgrad_upT(d.ptr, db, d.C, d.pitch, d.H, d.W, oy, ox, a.ptr, xb, a.C, a.pitch, a.N, a.H, a.W,
-                                     slab.data_ptr<float>(), slab.numel(), out.data_ptr<float>(), accumulate, splits, st));
+  return RDP_PLAN(rdp_conv_wgrad_upT(d.ptr, d.bytes, d.C, d.pitch, d.H, d.W, oy, ox, a.ptr, a.bytes, a.C, a.pitch, a.N,
+                                     a.H, a.W, slab.data_ptr<float>(), slab.numel(), out.data_ptr<float>(), accumulate,
+                                     splits, st));
 }
 
 void upT_unshuffle(torch::Tensor du, torch::Tensor dyT, int oy, int ox) {
@@ -1194,7 +1104,7 @@ void head_bn_bwd_apply(torch::Tensor y, torch::Tensor w, torch::Tensor logits, t
 bool conv_head_mask(torch::Tensor x, torch::Tensor w, torch::Tensor coef, torch::Tensor hw, torch::Tensor hb,
                     double thr, torch::Tensor mask) {
   Act a = act(x, "x");
-  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous() && w.dim() == 2, "w: bf16 [Cout][K]");
+  check_w(w);
   check_f32(coef, "coef");
   check_f32(hw, "head_w");
   check_f32(hb, "head_b");
@@ -1222,19 +1132,17 @@ int conv_rowband(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tenso
   TORCH_CHECK(coef.numel() >= 4l * o.C, "coef size");
   Act po;
   if (pool) po = act(*pool, "pool");
-  const int ldw = wfrag ? 0 : (int)w.size(1);
-  void* const px2 = x2 ? a2.ptr : nullptr;
-  const long bx2 = x2 ? a2.bytes : 0;
-  const int C2 = x2 ? a2.C : 0, p2 = x2 ? a2.pitch : 0;
+  RdpConv c;
+  conv_bind(c, kX1, a1, 0, a1.N);
+  conv_bind(c, kX2, a2, 0, a1.N);
+  conv_bind(c, kY1, o, 0, a1.N);
+  c.w = w.data_ptr(); c.wbytes = w.numel() * 2; c.ldw = wfrag ? 0 : (int)w.size(1);
+  c.Cout = o.C;
+  c.escale = coef.data_ptr<float>() + 2 * o.C; c.eshift = coef.data_ptr<float>() + 3 * o.C; c.erelu = 1;
   void* const pp = pool ? po.ptr : nullptr;
   const long pb = pool ? po.bytes : 0;
   const int ppit = pool ? po.pitch : 0;
-  const float* sc = coef.data_ptr<float>() + 2 * o.C;
-  const float* sh = coef.data_ptr<float>() + 3 * o.C;
-  void* const wp = w.data_ptr();
-  const long wb = w.numel() * 2;
-  return (int)RDP_PLAN(rdp_conv_rowband_ex(a1.ptr, px2, a1.bytes, bx2, a1.C, C2, a1.pitch, p2, wp, wb, ldw, o.ptr, o.bytes,
-                                           o.pitch, a1.N, a1.H, a1.W, o.C, sc, sh, 1, pp, pb, ppit, wfrag, st));
+  return (int)RDP_PLAN(rdp_conv_rowband_ex(c, pp, pb, ppit, wfrag, st));
 }
 
 // Persistent row-band chain (csrc/conv_rowband.hip): layer 0 reads x, layer l > 0 layer l - 1's output;

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "host_pool.h"
+#include "rdp_host_api.h"
 
 namespace {
 template <class F>
@@ -228,7 +229,6 @@ void put_chunk(std::vector<uint8_t>& v, const char* type, const uint8_t* data, s
 
 extern "C" {
 
-// width, height, bit depth of a supported PNG; returns 0, -1 (not PNG / corrupt) or -2 (unsupported)
 int rdp_png_info(const uint8_t* d, long n, int* w, int* h, int* bd) {
   Hdr hd;
   const int r = parse_header(d, n, hd);
@@ -239,8 +239,6 @@ int rdp_png_info(const uint8_t* d, long n, int* w, int* h, int* bd) {
   return 0;
 }
 
-// decode into out (h * w * bd/8 bytes; 16-bit samples native-endian). 0 ok, -1 corrupt, -2 unsupported.
-// `parallel`: use an rdPs band index if the file has one.
 int rdp_png_decode(const uint8_t* d, long n, uint8_t* out, long out_bytes, int parallel) {
   Hdr hd;
   int r = parse_header(d, n, hd);
@@ -288,9 +286,6 @@ int rdp_png_decode(const uint8_t* d, long n, uint8_t* out, long out_bytes, int p
   return unfilter(raw.data(), stride, bpp, 0, hd.h, nullptr, out, nullptr) ? 0 : -1;
 }
 
-// Grayscale PNG of img (h x w, row-major; bpp 1 = u8, 2 = native-endian u16), filter type 0 per row,
-// deflated at `level` in `bands` row bands (> 1: the banded stream + rdPs index described above, the
-// bands compressed in parallel). Returns the encoded size, or -1 if cap is too small / zlib failed.
 long rdp_png_encode_gray(const uint8_t* img, int w, int h, int bpp, int level, int bands, uint8_t* out, long cap) {
   if (w <= 0 || h <= 0 || (bpp != 1 && bpp != 2)) return -1;
   const size_t stride = (size_t)w * bpp;

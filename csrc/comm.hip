@@ -9,6 +9,7 @@
 // it completes. The spin reads the constant-rate wall clock (s_memrealtime) and sleeps between reads
 // so the waves issue almost nothing.
 #include "common.h"
+#include "rdp_api.h"
 
 __global__ __launch_bounds__(256) void comm_emulate_kernel(uint64_t ticks) {
   const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
@@ -68,7 +69,6 @@ extern "C" int rdp_comm_emulate(double us, int blocks, hipStream_t s) {
   return 0;
 }
 
-// scratch: >= 2 * traffic_bytes (16-byte aligned); traffic_bytes: bytes read (and as many written)
 extern "C" int rdp_comm_emulate_traffic(double us, int blocks, void* scratch, long scratch_bytes, long traffic_bytes,
                                         hipStream_t s) {
   if (us < 0 || blocks < 1 || blocks > 4096 || traffic_bytes < 0 || (uintptr_t)scratch % 16 ||

@@ -18,6 +18,7 @@
 //     pixel segments grid-stride; BN partial sums stay in registers until the wave's last segment,
 //     then the block's 4 wave rows are summed through LDS into ONE stats row per block.
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -180,24 +181,20 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const FirstArgs a) {
   }
 }
 
-// Returns the number of stats rows written (training) / 0, or -1 if the shape is not this kernel's
-// (3-channel input stored with pitch >= 4, 64 couts, packed [64][128] weights).
-extern "C" int rdp_conv_first(const void* x, long xbytes, int pitch, const void* w, long wbytes, void* y, long ybytes,
-                              int ypitch, float* stats, int N, int H, int W, const float* escale, const float* eshift,
-                              int erelu, hipStream_t s) {
-  if (pitch < 4 || wbytes < 64l * 128 * 2 || ypitch < 64 || ypitch % 8) return -1;
-  if (xbytes >= (1l << 31) || ybytes >= (1l << 31)) return -1;
+extern "C" int rdp_conv_first(const RdpConv& c, hipStream_t s) {
+  if (c.pitch1 < 4 || c.wbytes < 64l * 128 * 2 || c.ypitch1 < 64 || c.ypitch1 % 8) return -1;
+  if (c.xbytes1 >= (1l << 31) || c.ybytes1 >= (1l << 31)) return -1;
   FirstArgs a;
-  a.x = (const u16*)x; a.xbytes = (uint32_t)xbytes; a.pitch = pitch;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes;
-  a.y = (u16*)y; a.ybytes = (uint32_t)ybytes; a.ypitch = ypitch;
-  a.stats = stats; a.escale = escale; a.eshift = eshift; a.erelu = erelu;
-  a.H = H; a.W = W; a.M = N * H * W;
+  a.x = (const u16*)c.x1; a.xbytes = (uint32_t)c.xbytes1; a.pitch = c.pitch1;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes;
+  a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
+  a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
+  a.H = c.H; a.W = c.W; a.M = c.N * c.H * c.W;
   a.nseg = (a.M + 63) / 64;
-  const FastDiv fhw = make_fastdiv((uint32_t)(H * W)), fw = make_fastdiv((uint32_t)W);
+  const FastDiv fhw = make_fastdiv((uint32_t)(c.H * c.W)), fw = make_fastdiv((uint32_t)c.W);
   a.fhw_m = fhw.m; a.fhw_s = fhw.s; a.fw_m = fw.m; a.fw_s = fw.s;
   // grid <= nseg / 4 keeps the stats rows within conv_stats_rows() (>= M / 32 rows)
   const int grid = std::max(1, std::min((a.nseg + 3) / 4, 512));
   hipLaunchKernelGGL(conv_first_kernel, dim3(grid), dim3(256), 0, s, a);
-  return stats ? grid : 0;
+  return c.stats ? grid : 0;
 }

@@ -30,6 +30,7 @@
 // s the block issues the weight slice of step s+2 (3-slot ring, counted vmcnt) and 1/8 of the NEXT
 // chunk's halo tile (spread over taps 0..7 so the L2->LDS rate stays flat).
 #include "common.h"
+#include "rdp_api.h"
 
 struct HaloArgs {
   const u16* x1;
@@ -314,7 +315,6 @@ static int halo_launch(HaloArgs a, hipStream_t s) {
   return tilesM * WM;
 }
 
-// Number of 256-pixel output tiles x cout tiles the halo kernel would use (0 = shape unsupported).
 extern "C" int rdp_conv_halo_tiles(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed) {
   if (taps != 9 || packed || C1 % 64 || C2 % 64 || C1 == 0 || Cout % 64) return 0;
   int tc, tr;
@@ -326,29 +326,25 @@ extern "C" int rdp_conv_halo_tiles(int N, int H, int W, int C1, int C2, int Cout
   return N * (H / tr) * (W / tc) * (Cout / (64 * wn));
 }
 
-// Returns stats rows written (>= 0) or -1 if unsupported.
-extern "C" int rdp_conv_halo(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2, int pitch1,
-                             int pitch2, const void* w, long wbytes, int ldw, void* y1, void* y2, long ybytes1,
-                             long ybytes2, int Cy1, int ypitch1, int ypitch2, float* stats, int N, int H, int W,
-                             int Cout, const float* escale, const float* eshift, int erelu, hipStream_t s) {
-  if (!rdp_conv_halo_tiles(N, H, W, C1, C2, Cout, 9, 0)) return -1;
-  if (ldw < 9 * (C1 + C2) || Cy1 % 4) return -1;
-  if (xbytes1 >= (1l << 31) || xbytes2 >= (1l << 31) || ybytes1 >= (1l << 31) || ybytes2 >= (1l << 31) ||
-      wbytes >= (1l << 31))
+extern "C" int rdp_conv_halo(const RdpConv& c, hipStream_t s) {
+  if (!rdp_conv_halo_tiles(c.N, c.H, c.W, c.C1, c.C2, c.Cout, 9, 0)) return -1;
+  if (c.ldw < 9 * (c.C1 + c.C2) || c.Cy1 % 4) return -1;
+  if (c.xbytes1 >= (1l << 31) || c.xbytes2 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.ybytes2 >= (1l << 31) ||
+      c.wbytes >= (1l << 31))
     return -1;
   HaloArgs a;
-  a.x1 = (const u16*)x1; a.x2 = (const u16*)x2;
-  a.xbytes1 = (uint32_t)xbytes1; a.xbytes2 = (uint32_t)xbytes2;
-  a.C1 = C1; a.C2 = C2; a.pitch1 = pitch1; a.pitch2 = pitch2;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw; a.cin = C1 + C2;
-  a.y1 = (u16*)y1; a.y2 = (u16*)y2; a.ybytes1 = (uint32_t)ybytes1; a.ybytes2 = (uint32_t)ybytes2;
-  a.Cy1 = Cy1; a.ypitch1 = ypitch1; a.ypitch2 = ypitch2;
-  a.stats = stats; a.escale = escale; a.eshift = eshift; a.erelu = erelu;
-  a.N = N; a.H = H; a.W = W; a.Cout = Cout;
-  a.nchunks = (C1 + C2) / 64;
-  const bool wide = Cout % 128 == 0;
+  a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
+  a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
+  a.C1 = c.C1; a.C2 = c.C2; a.pitch1 = c.pitch1; a.pitch2 = c.pitch2;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw; a.cin = c.C1 + c.C2;
+  a.y1 = (u16*)c.y1; a.y2 = (u16*)c.y2; a.ybytes1 = (uint32_t)c.ybytes1; a.ybytes2 = (uint32_t)c.ybytes2;
+  a.Cy1 = c.Cy1; a.ypitch1 = c.ypitch1; a.ypitch2 = c.ypitch2;
+  a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout;
+  a.nchunks = (c.C1 + c.C2) / 64;
+  const bool wide = c.Cout % 128 == 0;
   // 8 waves per block either way (2 per SIMD): BN=128 -> 4 (pixels) x 2 (couts), BN=64 -> 8 x 1
-  if (W % 64 == 0 && H % 4 == 0) return wide ? halo_launch<64, 4, 4, 2>(a, s) : halo_launch<64, 4, 8, 1>(a, s);
-  if (W % 32 == 0 && H % 8 == 0) return wide ? halo_launch<32, 8, 4, 2>(a, s) : halo_launch<32, 8, 8, 1>(a, s);
+  if (c.W % 64 == 0 && c.H % 4 == 0) return wide ? halo_launch<64, 4, 4, 2>(a, s) : halo_launch<64, 4, 8, 1>(a, s);
+  if (c.W % 32 == 0 && c.H % 8 == 0) return wide ? halo_launch<32, 8, 4, 2>(a, s) : halo_launch<32, 8, 8, 1>(a, s);
   return wide ? halo_launch<16, 16, 4, 2>(a, s) : halo_launch<16, 16, 8, 1>(a, s);
 }

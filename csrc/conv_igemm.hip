@@ -24,6 +24,7 @@
 // MFMAs and epilogue. This removes the per-tile prologue that dominated the small-K (K = 576)
 // 64-channel layers. The epilogue uses no LDS and no block barrier.
 #include "common.h"
+#include "rdp_api.h"
 #include <stdlib.h>
 
 struct ConvArgs {
@@ -774,12 +775,6 @@ static int launch_pp(ConvArgs a, hipStream_t s, int ksplit = 1, int* pooled = nu
   return grid / a.tilesN * 2;
 }
 
-// ConvTranspose2d(k=2, s=2) + bias straight into its (padded) output map u [N][H2][W2][upitch]: the
-// 1x1 GEMM yT[px][sub * C + c] = sum_ci x[px][ci] Wt[sub * C + c][ci] on the ping-pong kernel with the
-// sub-pixel scatter + bias in its epilogue (no yT round trip and no upT_shuffle pass). u's border
-// outside the 2h x 2w window at (oy, ox) is not written (the caller zeroes it once). Returns 0, or -1
-// where the ping-pong grid would not fill the chip / the shape does not fit (the caller then runs the
-// GEMM + upT_shuffle).
 extern "C" int rdp_conv_upT_fwd(const void* x, long xbytes, int Cin, int pitch, const void* w, long wbytes, int ldw,
                                 void* u, long ubytes, int upitch, const float* bias, int N, int h, int wd, int H2,
                                 int W2, int oy, int ox, int C, hipStream_t s) {
@@ -808,11 +803,6 @@ extern "C" int rdp_conv_upT_fwd(const void* x, long xbytes, int Cin, int pitch, 
   return -1;
 }
 
-// ConvTranspose2d(k=2, s=2) input gradient straight from the output gradient du [N][H2][W2][C] (the
-// window 2h x 2w at (oy, ox)): dx[px][ci] = sum_(sub, c) du[sub-pixel sub of px][c] Wd[ci][sub * C + c]
-// on the ping-pong kernel, its A operand DMA'd from the 4 sub-pixels as 4 "taps" (no unshuffled copy
-// of du). wd = the [Cin][4C] dgrad weight. Returns 0, or -1 where the ping-pong grid would not fill
-// the chip / the shape does not fit (the caller unshuffles and runs the 1x1 GEMM).
 extern "C" int rdp_conv_upT_dgrad(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
                                   const void* wd, long wbytes, int ldw, void* dx, long dxbytes, int Cin, int dxpitch,
                                   int N, int h, int wdt, hipStream_t s) {
@@ -836,21 +826,7 @@ extern "C" int rdp_conv_upT_dgrad(const void* du, long dubytes, int C, int dupit
   return -1;
 }
 
-extern "C" int rdp_conv_ring(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
-                             void* y, long ybytes, int ypitch, void* y2, long ybytes2, int ypitch2, int Cy1,
-                             int Cout, float* stats, int N, int H, int W, const float* escale, const float* eshift,
-                             int erelu, int max_blocks, hipStream_t s);
-extern "C" int rdp_conv_ring_pool(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
-                                  void* y, long ybytes, int ypitch, int Cout, int N, int H, int W,
-                                  const float* escale, const float* eshift, int erelu, void* pool, int ppitch,
-                                  hipStream_t s);
-extern "C" int rdp_conv_halo_tiles(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed);
-extern "C" int rdp_conv_rowband(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2, int pitch1,
-                                int pitch2, const void* w, long wbytes, int ldw, void* y, long ybytes, int ypitch, int N,
-                                int H, int W, int Cout, const float* escale, const float* eshift, int erelu, void* pool,
-                                long pbytes, int ppitch, hipStream_t s);
 
-extern "C" long rdp_conv_rowband_bytes(int N, int H, int W, int Cin, int Cout, int pool);
 
 // Eval convs on small maps run on the row-band kernel (csrc/conv_rowband.hip) where its operand traffic
 // model says it wins (<= 160 MB; a pool it cannot fuse would cost a separate launch): RDP_ROWBAND=0 turns
@@ -867,17 +843,6 @@ static bool rowband_auto(int N, int H, int W, int Cin, int Cout, bool pool) {
   // two calls give bitwise the same activations)
   return rdp_conv_rowband_bytes(N, H, W, Cin, Cout, 0) <= 160000000L;
 }
-extern "C" int rdp_conv_ring2(const void* x0, long xbytes0, int pitch0, const void* x1, long xbytes1, int pitch1,
-                              const void* w, long wbytes, int ldw, void* y, long ybytes, int ypitch, float* stats,
-                              int N, int H, int W, const float* escale, const float* eshift, int erelu, int max_blocks,
-                              int cout_total, int co0, hipStream_t s);
-extern "C" int rdp_conv_first(const void* x, long xbytes, int pitch, const void* w, long wbytes, void* y, long ybytes,
-                              int ypitch, float* stats, int N, int H, int W, const float* escale, const float* eshift,
-                              int erelu, hipStream_t s);
-extern "C" int rdp_conv_halo(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2, int pitch1,
-                             int pitch2, const void* w, long wbytes, int ldw, void* y1, void* y2, long ybytes1,
-                             long ybytes2, int Cy1, int ypitch1, int ypitch2, float* stats, int N, int H, int W,
-                             int Cout, const float* escale, const float* eshift, int erelu, hipStream_t s);
 
 // Split-K reduction + epilogue: y[m][n] = epi(sum_s slab[s][m][n]); optional BN-stats rows (one per
 // block). Thread = fixed 4-channel group (epilogue coefficients in registers), rows grid-strided.
@@ -1177,45 +1142,29 @@ static int launch_cfg(ConvArgs a, int max_blocks, long ws_elems, hipStream_t s, 
   return grid / a.tilesN * (BM / 64);
 }
 
-// Returns the number of stats-slab rows written, or -1 on unsupported shape.
-extern "C" int rdp_conv_igemm(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2,
-                              int pitch1, int pitch2, const void* w, long wbytes, int ldw, void* y1, void* y2,
-                              long ybytes1, long ybytes2, int Cy1, int ypitch1, int ypitch2, float* stats,
-                              int N, int H, int W, int Cout, int taps, int packed, int bm_pref,
-                              const float* escale, const float* eshift, int erelu, float* ws, long ws_elems,
-                              void* pool, int ppitch, int* pooled, void* up, int upitch, int uH, int uW,
-                              int uoy, int uox, const void* bny, int bnypitch, const float* bncoef, float* bnpart,
-                              int* bnrows, hipStream_t s) {
-  // pool (eval, optional): MaxPool2d(2) of y1 fused into the split-K reduce when that path runs;
-  // up (eval, optional, exclusive with pool): bilinear x2 upsample of y1 into up [N][uH][uW] at
-  // (uoy, uox), fused the same way; *pooled = 1 if the fused output was written (else the caller
-  // launches the pool / upsample)
-  // bny / bncoef / bnpart (training dgrad into one BN + ReLU layer's activation gradient, optional): that
-  // layer's BN-backward partial rows, written by the split-K reduce when that path runs (ConvArgs);
-  // *bnrows = the rows written, else 0 (the caller runs bn_relu_bwd_reduce)
+extern "C" int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int bm_pref, float* ws, long ws_elems,
+                              const RdpConvFuse& fuse, int* pooled, const RdpConvBnBwd& bn, int* bnrows,
+                              hipStream_t s) {
   if (pooled) *pooled = 0;
   if (bnrows) *bnrows = 0;
   // first layer (3-channel input, packed K): conv_first.hip (auto, or bm_pref 13 = force; bm_pref 256
   // runs this file's packed implicit GEMM, the tests' second opinion)
   {
     const int pref = bm_pref % 1000;
-    if (packed && (pref == 13 || pref == 0) && C1 == 8 && C2 == 0 && x2 == nullptr && taps == 9 &&
-        Cout == 64 && y2 == nullptr) {
-      const int r = rdp_conv_first(x1, xbytes1, pitch1, w, wbytes, y1, ybytes1, ypitch1, stats, N, H, W, escale, eshift,
-                                   erelu, s);
+    if (packed && (pref == 13 || pref == 0) && c.C1 == 8 && c.C2 == 0 && c.x2 == nullptr && taps == 9 &&
+        c.Cout == 64 && c.y2 == nullptr) {
+      const int r = rdp_conv_first(c, s);
       if (r >= 0 || pref == 13) return r;
     }
   }
   // eval (BN folded, one destination) on small maps: the row-band kernel, MaxPool2d fused (16 = force)
   {
     const int pref = bm_pref % 1000;
-    if (escale && eshift && !stats && !y2 && taps == 9 && !packed &&
-        (pref == 16 || (pref == 0 && rowband_auto(N, H, W, C1 + C2, Cout, pool && pooled)))) {
-      const bool wp = pool && pooled && H % 2 == 0 && W % 2 == 0;
-      const long pbytes = wp ? ((long)N * (H / 2) * (W / 2) - 1) * ppitch * 2 + (long)Cout * 2 : 0;
-      const int r = rdp_conv_rowband(x1, x2, xbytes1, xbytes2, C1, C2, pitch1, pitch2, w, wbytes, ldw, y1, ybytes1,
-                                     ypitch1, N, H, W, Cout, escale, eshift, erelu, wp ? pool : nullptr, pbytes,
-                                     ppitch, s);
+    if (c.escale && c.eshift && !c.stats && !c.y2 && taps == 9 && !packed &&
+        (pref == 16 || (pref == 0 && rowband_auto(c.N, c.H, c.W, c.C1 + c.C2, c.Cout, fuse.pool && pooled)))) {
+      const bool wp = fuse.pool && pooled && c.H % 2 == 0 && c.W % 2 == 0;
+      const long pbytes = wp ? ((long)c.N * (c.H / 2) * (c.W / 2) - 1) * fuse.ppitch * 2 + (long)c.Cout * 2 : 0;
+      const int r = rdp_conv_rowband(c, wp ? fuse.pool : nullptr, pbytes, fuse.ppitch, s);
       if (r >= 0) {
         if (r == 1) *pooled = 1;
         return 0;
@@ -1230,19 +1179,17 @@ extern "C" int rdp_conv_igemm(const void* x1, const void* x2, long xbytes1, long
     // row-ring kernel (conv_ring.hip): 64 -> 64 channels, 3x3, one source, no output split. Auto only
     // when its grid (one block per pair of 64-pixel row segments, <= 256) fills the chip: at N = 1,
     // 128^2 x 64 -> 128 the 128-block ring took 15.2 us vs 11.9 us for the implicit GEMM
-    const long ring_pairs = W % 64 == 0 ? (long)N * (W / 64) * H / 2 : 0;
-    if ((pref == 6 || (pref == 0 && ring_pairs >= 256)) && taps == 9 && !packed && C2 == 0 &&
-        x2 == nullptr) {
-      if (pool && pooled && !stats && !y2 && escale) {  // eval: MaxPool2d fused into the ring epilogue
-        const int r = rdp_conv_ring_pool(x1, xbytes1, C1, pitch1, w, wbytes, ldw, y1, ybytes1, ypitch1, Cout, N, H, W,
-                                         escale, eshift, erelu, pool, ppitch, s);
+    const long ring_pairs = c.W % 64 == 0 ? (long)c.N * (c.W / 64) * c.H / 2 : 0;
+    if ((pref == 6 || (pref == 0 && ring_pairs >= 256)) && taps == 9 && !packed && c.C2 == 0 &&
+        c.x2 == nullptr) {
+      if (fuse.pool && pooled && !c.stats && !c.y2 && c.escale) {  // eval: MaxPool2d fused into the ring epilogue
+        const int r = rdp_conv_ring_pool(c, fuse.pool, fuse.ppitch, s);
         if (r == 0) {
           *pooled = 1;
           return 0;
         }
       }
-      const int r = rdp_conv_ring(x1, xbytes1, C1, pitch1, w, wbytes, ldw, y1, ybytes1, ypitch1, y2, ybytes2,
-                                  ypitch2, Cy1, Cout, stats, N, H, W, escale, eshift, erelu, 256, s);
+      const int r = rdp_conv_ring(c, 256, s);
       if (r >= 0 || pref == 6) return r;
     }
   }
@@ -1251,20 +1198,28 @@ extern "C" int rdp_conv_igemm(const void* x1, const void* x2, long xbytes1, long
   // (auto: RING2_X2_PAIRS) 128 -> 128 as two launches over the output-channel halves (each reads the input).
   {
     const int pref = bm_pref % 1000;
-    const long ring_pairs = W % 64 == 0 ? (long)N * (W / 64) * H / 2 : 0;
-    const bool two = C1 == 64 && C2 == 64 && x2 != nullptr, one = C1 == 128 && C2 == 0 && x2 == nullptr;
-    const bool c64 = Cout == 64 && (pref == 14 || (pref == 0 && ring_pairs >= 256));
-    const bool c128 = Cout == 128 && (pref == 15 || (pref == 0 && ring_pairs >= RING2_X2_PAIRS));
-    if ((c64 || c128) && taps == 9 && !packed && (two || one) && y2 == nullptr && !(pool && pooled) &&
-        !(up && pooled)) {
-      const void* s1 = two ? x2 : (const void*)((const u16*)x1 + 64);
-      const long b1 = two ? xbytes2 : xbytes1 - 128;
+    const long ring_pairs = c.W % 64 == 0 ? (long)c.N * (c.W / 64) * c.H / 2 : 0;
+    const bool two = c.C1 == 64 && c.C2 == 64 && c.x2 != nullptr;
+    const bool one = c.C1 == 128 && c.C2 == 0 && c.x2 == nullptr;
+    const bool c64 = c.Cout == 64 && (pref == 14 || (pref == 0 && ring_pairs >= 256));
+    const bool c128 = c.Cout == 128 && (pref == 15 || (pref == 0 && ring_pairs >= RING2_X2_PAIRS));
+    if ((c64 || c128) && taps == 9 && !packed && (two || one) && c.y2 == nullptr && !(fuse.pool && pooled) &&
+        !(fuse.up && pooled)) {
+      RdpConv h = c;  // one launch per 64 output channels: a copy of the block with the slice offsets applied
+      if (one) {      // the second source = the upper half of the one 128-channel tensor
+        h.x2 = (const u16*)c.x1 + 64;
+        h.xbytes2 = c.xbytes1 - 128;
+        h.pitch2 = c.pitch1;
+      }
       int r = -1;
-      for (int co0 = 0; co0 < Cout; co0 += 64) {
-        const long yoff = (long)co0 * 2;
-        r = rdp_conv_ring2(x1, xbytes1, pitch1, s1, b1, two ? pitch2 : pitch1, (const u16*)w + (long)co0 * ldw,
-                           wbytes - (long)co0 * ldw * 2, ldw, (u16*)y1 + co0, ybytes1 - yoff, ypitch1, stats, N, H, W,
-                           escale ? escale + co0 : nullptr, eshift ? eshift + co0 : nullptr, erelu, 256, Cout, co0, s);
+      for (int co0 = 0; co0 < c.Cout; co0 += 64) {
+        h.w = (const u16*)c.w + (long)co0 * c.ldw;
+        h.wbytes = c.wbytes - (long)co0 * c.ldw * 2;
+        h.y1 = (u16*)c.y1 + co0;
+        h.ybytes1 = c.ybytes1 - (long)co0 * 2;
+        h.escale = c.escale ? c.escale + co0 : nullptr;
+        h.eshift = c.eshift ? c.eshift + co0 : nullptr;
+        r = rdp_conv_ring2(h, 256, c.Cout, co0, s);
         if (r < 0) break;
       }
       if (r >= 0 || pref == 14 || pref == 15) return r;
@@ -1272,63 +1227,66 @@ extern "C" int rdp_conv_igemm(const void* x1, const void* x2, long xbytes1, long
   }
   {
     const int pref = bm_pref % 1000;
-    const int ht = rdp_conv_halo_tiles(N, H, W, C1, C2, Cout, taps, packed);
+    const int ht = rdp_conv_halo_tiles(c.N, c.H, c.W, c.C1, c.C2, c.Cout, taps, packed);
     // auto: the halo kernel wins only where a 64-channel output reads >= 256 input channels
     // (measured, scripts/conv_microbench.py); elsewhere this kernel's 2 blocks/CU overlap better
-    const bool halo_auto = pref == 0 && ht >= 256 && Cout == 64 && C1 + C2 >= 256;
+    const bool halo_auto = pref == 0 && ht >= 256 && c.Cout == 64 && c.C1 + c.C2 >= 256;
     if (ht > 0 && (pref == 1 || halo_auto))
-      return rdp_conv_halo(x1, x2, xbytes1, xbytes2, C1, C2, pitch1, pitch2, w, wbytes, ldw, y1, y2, ybytes1,
-                           ybytes2, Cy1, ypitch1, ypitch2, stats, N, H, W, Cout, escale, eshift, erelu, s);
+      return rdp_conv_halo(c, s);
     if (pref == 1) return -1;
   }
   ConvArgs a;
-  a.escale = escale; a.eshift = eshift; a.erelu = erelu;
+  a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
   // ws = the split-K fp32 slab (rdp_conv_ws_elems)
   const bool has_ws = ws != nullptr && ws_elems > 0;
   a.kslab = has_ws ? ws : nullptr;
   a.ksplit = 1;
-  a.pool = (pool != nullptr && pooled != nullptr && stats == nullptr && y2 == nullptr && H % 2 == 0 && W % 2 == 0)
-               ? (u16*)pool : nullptr;
-  a.ppitch = ppitch;
+  a.pool = (fuse.pool != nullptr && pooled != nullptr && c.stats == nullptr && c.y2 == nullptr && c.H % 2 == 0 &&
+            c.W % 2 == 0)
+               ? (u16*)fuse.pool : nullptr;
+  a.ppitch = fuse.ppitch;
   // fused upsample needs the eval epilogue, 16-channel groups and the LDS band (<= 64 KB). Measured
   // (serving frame, N = 1): it wins only at the 16^2 bottleneck (6.9 us vs 4.8 + 4.8 us); at 32^2 /
   // 64^2 / 128^2 the banded two-phase kernel is slower than reduce + upsample (10.9 / 13.2 / 15.4 vs
   // 9.8 / 10.3 / 10.6 us; 2-row bands x 8 channels were slower still), so larger maps take the
   // separate upsample launch.
-  const bool up_ok = up != nullptr && pooled != nullptr && pool == nullptr && stats == nullptr && y2 == nullptr &&
-                     escale != nullptr && eshift != nullptr && Cout % UP_CG == 0 && upitch % 4 == 0 &&
-                     (long)(UP_TY / 2 + 2) * W * UP_CG * 2 <= 65536 && uH >= 2 * H && uW >= 2 * W &&
-                     (long)H * W <= 256;
-  a.up = up_ok ? (u16*)up : nullptr;
-  a.upitch = upitch; a.uH = uH; a.uW = uW; a.uoy = uoy; a.uox = uox;
-  a.urh = 2 * H > 1 ? (float)(H - 1) / (float)(2 * H - 1) : 0.f;  // = ac_scale (pool_up.hip)
-  a.urw = 2 * W > 1 ? (float)(W - 1) / (float)(2 * W - 1) : 0.f;
+  const bool up_ok = fuse.up != nullptr && pooled != nullptr && fuse.pool == nullptr && c.stats == nullptr &&
+                     c.y2 == nullptr &&
+                     c.escale != nullptr && c.eshift != nullptr && c.Cout % UP_CG == 0 && fuse.upitch % 4 == 0 &&
+                     (long)(UP_TY / 2 + 2) * c.W * UP_CG * 2 <= 65536 && fuse.uH >= 2 * c.H && fuse.uW >= 2 * c.W &&
+                     (long)c.H * c.W <= 256;
+  a.up = up_ok ? (u16*)fuse.up : nullptr;
+  a.upitch = fuse.upitch; a.uH = fuse.uH; a.uW = fuse.uW; a.uoy = fuse.uoy; a.uox = fuse.uox;
+  a.urh = 2 * c.H > 1 ? (float)(c.H - 1) / (float)(2 * c.H - 1) : 0.f;  // = ac_scale (pool_up.hip)
+  a.urw = 2 * c.W > 1 ? (float)(c.W - 1) / (float)(2 * c.W - 1) : 0.f;
   long wse = has_ws ? ws_elems : 0;
   wse = wse < (1L << 29) ? wse : (1L << 29);  // slab bytes < 2 GiB (buffer offsets)
-  a.x1 = (const u16*)x1; a.x2 = (const u16*)x2;
-  a.xbytes1 = (uint32_t)xbytes1; a.xbytes2 = (uint32_t)xbytes2;
-  a.C1 = C1; a.C2 = C2; a.pitch1 = pitch1; a.pitch2 = pitch2;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y1 = (u16*)y1; a.y2 = (u16*)y2; a.ybytes1 = (uint32_t)ybytes1; a.ybytes2 = (uint32_t)ybytes2;
-  a.Cy1 = Cy1; a.ypitch1 = ypitch1; a.ypitch2 = ypitch2; a.stats = stats;
-  if (bnpart && bny && bncoef && !stats && !escale && y2 == nullptr && Cy1 == Cout && bnypitch % 4 == 0 &&
-      pool == nullptr && up == nullptr) {
-    a.bny = (const u16*)bny; a.bnypitch = bnypitch; a.bncoef = bncoef; a.bnpart = bnpart; a.bnrows = bnrows;
+  a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
+  a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
+  a.C1 = c.C1; a.C2 = c.C2; a.pitch1 = c.pitch1; a.pitch2 = c.pitch2;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
+  a.y1 = (u16*)c.y1; a.y2 = (u16*)c.y2; a.ybytes1 = (uint32_t)c.ybytes1; a.ybytes2 = (uint32_t)c.ybytes2;
+  a.Cy1 = c.Cy1; a.ypitch1 = c.ypitch1; a.ypitch2 = c.ypitch2; a.stats = c.stats;
+  if (bn.bnpart && bn.bny && bn.bncoef && !c.stats && !c.escale && c.y2 == nullptr && c.Cy1 == c.Cout &&
+      bn.bnypitch % 4 == 0 && fuse.pool == nullptr && fuse.up == nullptr) {
+    a.bny = (const u16*)bn.bny; a.bnypitch = bn.bnypitch; a.bncoef = bn.bncoef; a.bnpart = bn.bnpart;
+    a.bnrows = bnrows;
   }
-  a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.M = N * H * W;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.M = c.N * c.H * c.W;
   a.taps = taps; a.packed = packed;
   if (packed) {
-    if (C1 != 8 || C2 != 0 || taps != 9 || ldw != 128) return -1;
+    if (c.C1 != 8 || c.C2 != 0 || taps != 9 || c.ldw != 128) return -1;
     a.nks = 2; a.cpt = 1;
   } else {
-    if (C1 % 64 || C2 % 64 || (taps != 9 && taps != 1)) return -1;
-    a.cpt = (C1 + C2) / 64;
+    if (c.C1 % 64 || c.C2 % 64 || (taps != 9 && taps != 1)) return -1;
+    a.cpt = (c.C1 + c.C2) / 64;
     a.nks = taps * a.cpt;
-    if (ldw < taps * (C1 + C2)) return -1;
+    if (c.ldw < taps * (c.C1 + c.C2)) return -1;
   }
-  if (Cout % 64 || Cy1 % 8) return -1;  // widened 16-B epilogue stores never straddle the split
-  if (xbytes1 >= (1l << 31) || xbytes2 >= (1l << 31) || ybytes1 >= (1l << 31) || ybytes2 >= (1l << 31)) return -1;
-  const FastDiv fhw = make_fastdiv((uint32_t)(H * W)), fw = make_fastdiv((uint32_t)W);
+  if (c.Cout % 64 || c.Cy1 % 8) return -1;  // widened 16-B epilogue stores never straddle the split
+  if (c.xbytes1 >= (1l << 31) || c.xbytes2 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.ybytes2 >= (1l << 31))
+    return -1;
+  const FastDiv fhw = make_fastdiv((uint32_t)(c.H * c.W)), fw = make_fastdiv((uint32_t)c.W);
   a.fhw_m = fhw.m; a.fhw_s = fhw.s; a.fw_m = fw.m; a.fw_s = fw.s;
   // bm_pref: 0 = auto, 128 / 256 = force the tile; +1000*k: k = blocks per CU of the persistent
   // grid (k = 0 => 2 per CU, every block resident; large k ~ one tile per block)
@@ -1345,17 +1303,17 @@ extern "C" int rdp_conv_igemm(const void* x1, const void* x2, long xbytes1, long
   // 2-4 % faster than the 128 x 128 kernel where K >= 1152 (128^2 128->128 851 -> 889, 64^2
   // 256+256->128 882 -> 907; slower at K = 576) and +1.0-1.4 % on the bs 64 step.
   if (bm_pref == 0 && !packed) {
-    const long tiles256 = (long)(a.M + 255) / 256 * (Cout / 256);
-    if (Cout % 256 == 0 && Cy1 % 32 == 0 && tiles256 >= 256 && escale == nullptr) return launch_pp<256>(a, s);
+    const long tiles256 = (long)(a.M + 255) / 256 * (c.Cout / 256);
+    if (c.Cout % 256 == 0 && c.Cy1 % 32 == 0 && tiles256 >= 256 && c.escale == nullptr) return launch_pp<256>(a, s);
     // 256 x 128 form: only where K is long enough (>= 128 input channels)
-    const long tiles128 = (long)(a.M + 255) / 256 * (Cout / 128);
-    if (Cout % 128 == 0 && Cy1 % 32 == 0 && tiles128 >= 256 && C1 + C2 >= 128 && escale == nullptr)
+    const long tiles128 = (long)(a.M + 255) / 256 * (c.Cout / 128);
+    if (c.Cout % 128 == 0 && c.Cy1 % 32 == 0 && tiles128 >= 256 && c.C1 + c.C2 >= 128 && c.escale == nullptr)
       return launch_pp<128>(a, s);
   }
   // bm_pref 7 / 8: force the split-K ping-pong 256 x 128 / 256 x 256 kernel (pp_split_plan's split)
   if (bm_pref == 7 || bm_pref == 8) {
-    const int d = pp_split_plan(a.M, Cout, bm_pref == 7 ? 128 : 256, a.nks, wse);
-    if (d < 2 || packed || Cy1 % 32) return -1;
+    const int d = pp_split_plan(a.M, c.Cout, bm_pref == 7 ? 128 : 256, a.nks, wse);
+    if (d < 2 || packed || c.Cy1 % 32) return -1;
     return bm_pref == 7 ? launch_pp<128>(a, s, d, pooled) : launch_pp<256>(a, s, d, pooled);
   }
   // auto, small M x long K (training): split-K ping-pong 256 x 128 where its plan exists and the 128 x 128
@@ -1365,9 +1323,9 @@ extern "C" int rdp_conv_igemm(const void* x1, const void* x2, long xbytes1, long
   // and at M = 1024 (16^2 512->1024: 29.5 vs 31.0 us) the 128 x 128 split does)
   // (eval too, BN fold in the shared reduce: the batched serving network at N = 4, scripts/rowband_bench.py
   // --batch 4 --variants 0,7: 32^2 1024->512 63.2 -> 52.3 us, 512->512 + pool 39.3 -> 36.4)
-  if (bm_pref == 0 && !packed && Cout % 128 == 0 && Cy1 % 32 == 0 && C1 + C2 >= 128 &&
-      a.M >= 4096 && (long)(a.M + 127) / 128 * (Cout / 128) < 192 && pp_split_enabled()) {
-    const int d = pp_split_plan(a.M, Cout, 128, a.nks, wse);
+  if (bm_pref == 0 && !packed && c.Cout % 128 == 0 && c.Cy1 % 32 == 0 && c.C1 + c.C2 >= 128 &&
+      a.M >= 4096 && (long)(a.M + 127) / 128 * (c.Cout / 128) < 192 && pp_split_enabled()) {
+    const int d = pp_split_plan(a.M, c.Cout, 128, a.nks, wse);
     if (d > 1) return launch_pp<128>(a, s, d, pooled);
   }
   const int max_blocks = 256 * per_cu;
@@ -1375,15 +1333,14 @@ extern "C" int rdp_conv_igemm(const void* x1, const void* x2, long xbytes1, long
   // barrier + DMA latency, 1.5x the LDS fragment reads per MFMA) for the 128x128 / 256x64 tiles
   // (measured dead end: 256 x 256 / 256 x 128 tiles in this 2-phase structure, one 8-wave block
   // per CU -- 49 spilled VGPRs at 256 x 256; +6 % on 32^2 x 512 -> 512 only, -5..-40 % elsewhere)
-  if (bm_pref == 2 && Cout % 128 == 0) return launch_cfg<128, 128, 8>(a, max_blocks, wse, s, pooled);
+  if (bm_pref == 2 && c.Cout % 128 == 0) return launch_cfg<128, 128, 8>(a, max_blocks, wse, s, pooled);
   if (bm_pref == 3) return launch_cfg<256, 64, 8>(a, max_blocks, wse, s, pooled);
-  if (bm_pref == 128 && Cout % 128 == 0) return launch_cfg<128, 128>(a, max_blocks, wse, s, pooled);
-  if (bm_pref == 0 && Cout % 128 == 0) return launch_cfg<128, 128, 8>(a, max_blocks, wse, s, pooled);
+  if (bm_pref == 128 && c.Cout % 128 == 0) return launch_cfg<128, 128>(a, max_blocks, wse, s, pooled);
+  if (bm_pref == 0 && c.Cout % 128 == 0) return launch_cfg<128, 128, 8>(a, max_blocks, wse, s, pooled);
   if (bm_pref == 256) return launch_cfg<256, 64>(a, max_blocks, wse, s, pooled);
   return launch_cfg<256, 64, 8>(a, max_blocks, wse, s, pooled);
 }
 
-// fp32 workspace elements the auto dispatch would use for split-K on this shape (0 = no split)
 extern "C" long rdp_conv_ws_elems(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed, int bm_pref) {
   const int pref = bm_pref % 1000;
   const int ht = rdp_conv_halo_tiles(N, H, W, C1, C2, Cout, taps, packed);

@@ -20,6 +20,7 @@
 // holds another column's row there: the zero padding row of this one). Epilogue: bf16 store (permlane16-widened, 16 B
 // per lane), optional training BN statistics (per-block partial rows) or eval BN fold + ReLU.
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -563,23 +564,10 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
 // Applicability of the ring kernel (3x3, one 64-channel source, 64 or 128 outputs -- split at a
 // multiple of 32 into two destinations --, W % 64 == 0, even H); returns the stats rows it writes,
 // or -1 when not applicable.
-extern "C" int rdp_conv_ring_ex(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
-                                void* y, long ybytes, int ypitch, void* y2, long ybytes2, int ypitch2, int Cy1,
-                                int Cout, float* stats, int N, int H, int W, const float* escale, const float* eshift,
-                                int erelu, int max_blocks, const void* bn_y_, int bn_ypitch, const float* bn_coef,
-                                const float* iscale, const float* ishift, void* aout, long abytes, int apitch,
-                                hipStream_t s);
-extern "C" int rdp_conv_ring(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
-                             void* y, long ybytes, int ypitch, void* y2, long ybytes2, int ypitch2, int Cy1,
-                             int Cout, float* stats, int N, int H, int W, const float* escale, const float* eshift,
-                             int erelu, int max_blocks, hipStream_t s) {
-  return rdp_conv_ring_ex(x, xbytes, C, pitch, w, wbytes, ldw, y, ybytes, ypitch, y2, ybytes2, ypitch2, Cy1, Cout,
-                          stats, N, H, W, escale, eshift, erelu, max_blocks, nullptr, 0, nullptr, nullptr, nullptr, nullptr,
-                          0, 0, s);
+extern "C" int rdp_conv_ring(const RdpConv& c, int max_blocks, hipStream_t s) {
+  return rdp_conv_ring_ex(c, max_blocks, RdpRingFuse{}, s);
 }
 
-// Eval conv (64 -> 64, BN folded + ReLU) fused with the serving 1x1 head: writes only the u8 mask
-// (logit > thr) of the 64-channel output. Returns 0, or -1 when the ring kernel does not apply.
 extern "C" int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
                                   int Cout, int N, int H, int W, const float* escale, const float* eshift,
                                   const float* hw, const float* hb, float hthr, void* mask, hipStream_t s) {
@@ -607,74 +595,65 @@ extern "C" int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, 
   return 0;
 }
 
-// Eval conv (64 -> 64, BN folded + ReLU) that also writes MaxPool2d(2) of its output into pool
-// [N][H/2][W/2][64] (pixel pitch ppitch). Returns 0, or -1 when the ring kernel does not apply.
-extern "C" int rdp_conv_ring_pool(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
-                                  void* y, long ybytes, int ypitch, int Cout, int N, int H, int W,
-                                  const float* escale, const float* eshift, int erelu, void* pool, int ppitch,
-                                  hipStream_t s) {
-  if (C != 64 || Cout != 64 || W % 64 || H % 2 || ldw < 576 || !escale || !eshift || !pool || ppitch % 4) return -1;
-  if (xbytes >= (1l << 31) || ybytes >= (1l << 31) || wbytes >= (1l << 31)) return -1;
+extern "C" int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipStream_t s) {
+  if (c.C1 != 64 || c.Cout != 64 || c.W % 64 || c.H % 2 || c.ldw < 576 || !c.escale || !c.eshift || !pool ||
+      ppitch % 4)
+    return -1;
+  if (c.xbytes1 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.wbytes >= (1l << 31)) return -1;
   RingArgs a;
-  a.x = (const u16*)x; a.xbytes = (uint32_t)xbytes; a.pitch = pitch;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y = (u16*)y; a.ybytes = (uint32_t)ybytes; a.ypitch = ypitch;
-  a.y2 = (u16*)y; a.ybytes2 = 0; a.ypitch2 = ypitch; a.Cy1 = 64;
-  a.stats = nullptr; a.escale = escale; a.eshift = eshift; a.erelu = erelu;
+  a.x = (const u16*)c.x1; a.xbytes = (uint32_t)c.xbytes1; a.pitch = c.pitch1;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
+  a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
+  a.y2 = (u16*)c.y1; a.ybytes2 = 0; a.ypitch2 = c.ypitch1; a.Cy1 = 64;
+  a.stats = nullptr; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
   a.bny = nullptr; a.bnypitch = 0; a.bncoef = nullptr;
   a.hw = nullptr; a.hb = nullptr; a.hthr = 0.f; a.hmask = nullptr;
   a.pool = (u16*)pool; a.ppitch = ppitch;
   a.iscale = nullptr; a.ishift = nullptr;
   a.aout = nullptr; a.abytes = 0; a.apitch = 0;
-  a.H = H; a.W = W; a.WS = W / 64;
-  a.nrows = N * a.WS * H;
+  a.H = c.H; a.W = c.W; a.WS = c.W / 64;
+  a.nrows = c.N * a.WS * c.H;
   a.npairs = a.nrows / 2;
   const int blocks = std::max(1, std::min(256, a.npairs));
   a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
   const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
-  const FastDiv fh = make_fastdiv((uint32_t)H), fs = make_fastdiv((uint32_t)a.WS);
+  const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)a.WS);
   a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
   hipLaunchKernelGGL((conv_ring_kernel<64, false, false, true>), dim3(grid), dim3(512), 0, s, a);
   return 0;
 }
 
-// Row-ring dgrad whose epilogue also produces the BN-backward partial rows of the layer that owns
-// the output (bn_y: its pre-BN activations, bn_coef: its [mean|invstd|scale|shift]; ReLU applied):
-// replaces a separate bn_relu_bwd_reduce pass over (da, y). Returns the partial rows, or -1.
-extern "C" int rdp_conv_ring_ex(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
-                                void* y, long ybytes, int ypitch, void* y2, long ybytes2, int ypitch2, int Cy1,
-                                int Cout, float* stats, int N, int H, int W, const float* escale, const float* eshift,
-                                int erelu, int max_blocks, const void* bn_y_, int bn_ypitch, const float* bn_coef,
-                                const float* iscale, const float* ishift, void* aout, long abytes, int apitch,
-                                hipStream_t s) {
-  const u16* bn_y = (const u16*)bn_y_;
-  if (aout && (!iscale || abytes >= (1l << 31) || apitch % 8)) return -1;
-  if (bn_y && (!stats || escale || y2 || bn_ypitch % 4 || Cout != 64)) return -1;
-  if (iscale && (!ishift || bn_y || escale || y2 || Cout != 64)) return -1;
-  if (C != 64 || (Cout != 64 && Cout != 128) || W % 64 || H % 2 || ldw < 576 || Cy1 % 32) return -1;
-  if (y2 == nullptr && Cy1 != Cout) return -1;
-  if (xbytes >= (1l << 31) || ybytes >= (1l << 31) || ybytes2 >= (1l << 31) || wbytes >= (1l << 31)) return -1;
+extern "C" int rdp_conv_ring_ex(const RdpConv& c, int max_blocks, const RdpRingFuse& f, hipStream_t s) {
+  const u16* bn_y = (const u16*)f.bn_y;
+  if (f.aout && (!f.iscale || f.abytes >= (1l << 31) || f.apitch % 8)) return -1;
+  if (bn_y && (!c.stats || c.escale || c.y2 || f.bn_ypitch % 4 || c.Cout != 64)) return -1;
+  if (f.iscale && (!f.ishift || bn_y || c.escale || c.y2 || c.Cout != 64)) return -1;
+  if (c.C1 != 64 || (c.Cout != 64 && c.Cout != 128) || c.W % 64 || c.H % 2 || c.ldw < 576 || c.Cy1 % 32) return -1;
+  if (c.y2 == nullptr && c.Cy1 != c.Cout) return -1;
+  if (c.xbytes1 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.ybytes2 >= (1l << 31) || c.wbytes >= (1l << 31))
+    return -1;
   RingArgs a;
-  a.x = (const u16*)x; a.xbytes = (uint32_t)xbytes; a.pitch = pitch;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y = (u16*)y; a.ybytes = (uint32_t)ybytes; a.ypitch = ypitch;
-  a.y2 = (u16*)(y2 ? y2 : y); a.ybytes2 = y2 ? (uint32_t)ybytes2 : 0u; a.ypitch2 = y2 ? ypitch2 : ypitch;
-  a.Cy1 = Cy1;
-  a.stats = stats; a.escale = escale; a.eshift = eshift; a.erelu = erelu;
-  a.bny = bn_y; a.bnypitch = bn_ypitch; a.bncoef = bn_coef;
+  a.x = (const u16*)c.x1; a.xbytes = (uint32_t)c.xbytes1; a.pitch = c.pitch1;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
+  a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
+  a.y2 = (u16*)(c.y2 ? c.y2 : c.y1); a.ybytes2 = c.y2 ? (uint32_t)c.ybytes2 : 0u;
+  a.ypitch2 = c.y2 ? c.ypitch2 : c.ypitch1;
+  a.Cy1 = c.Cy1;
+  a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
+  a.bny = bn_y; a.bnypitch = f.bn_ypitch; a.bncoef = f.bn_coef;
   a.hw = nullptr; a.hb = nullptr; a.hthr = 0.f; a.hmask = nullptr;
   a.pool = nullptr; a.ppitch = 0;
-  a.iscale = iscale; a.ishift = ishift;
-  a.aout = (u16*)aout; a.abytes = (uint32_t)abytes; a.apitch = apitch;
-  a.H = H; a.W = W; a.WS = W / 64;
-  a.nrows = N * a.WS * H;
+  a.iscale = f.iscale; a.ishift = f.ishift;
+  a.aout = (u16*)f.aout; a.abytes = (uint32_t)f.abytes; a.apitch = f.apitch;
+  a.H = c.H; a.W = c.W; a.WS = c.W / 64;
+  a.nrows = c.N * a.WS * c.H;
   a.npairs = a.nrows / 2;
   const int blocks = std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, a.npairs));
   a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
   const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
-  const FastDiv fh = make_fastdiv((uint32_t)H), fs = make_fastdiv((uint32_t)a.WS);
+  const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)a.WS);
   a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
-  if (Cout == 128) {
+  if (c.Cout == 128) {
     hipLaunchKernelGGL((conv_ring_kernel<128>), dim3(grid), dim3(512), 0, s, a);
     return grid * 2;
   }
@@ -682,7 +661,7 @@ extern "C" int rdp_conv_ring_ex(const void* x, long xbytes, int C, int pitch, co
     hipLaunchKernelGGL((conv_ring_kernel<64, true>), dim3(grid), dim3(512), 0, s, a);
     return grid * 4;
   }
-  if (iscale) {
+  if (f.iscale) {
     hipLaunchKernelGGL((conv_ring_kernel<64, false, false, false, true>), dim3(grid), dim3(512), 0, s, a);
     return grid * 4;
   }
@@ -954,33 +933,26 @@ __global__ __launch_bounds__(512, 2) void conv_ring2_kernel(const Ring2Args a) {
   }
 }
 
-// Two-source row ring (see conv_ring2_kernel): x0 / x1 = the two 64-channel sources (for one
-// 128-channel tensor: its two halves), 64 outputs, 3x3, W % 64 == 0, even H. cout_total / co0: the
-// launch computes output channels co0 .. co0 + 63 of a cout_total-channel conv (w, y, escale / eshift
-// already offset by the caller; the stats rows are [rows][2][cout_total], this launch's 64 columns
-// at co0). Returns the stats rows written (grid * 4), or -1 when not applicable.
-extern "C" int rdp_conv_ring2(const void* x0, long xbytes0, int pitch0, const void* x1, long xbytes1, int pitch1,
-                              const void* w, long wbytes, int ldw, void* y, long ybytes, int ypitch, float* stats,
-                              int N, int H, int W, const float* escale, const float* eshift, int erelu, int max_blocks,
-                              int cout_total, int co0, hipStream_t s) {
-  if (W % 64 || H % 2 || ldw < 1152 || ypitch % 8 || pitch0 % 8 || pitch1 % 8) return -1;
-  if (xbytes0 >= (1l << 31) || xbytes1 >= (1l << 31) || ybytes >= (1l << 31) || wbytes >= (1l << 31)) return -1;
-  if ((escale == nullptr) != (eshift == nullptr)) return -1;
+extern "C" int rdp_conv_ring2(const RdpConv& c, int max_blocks, int cout_total, int co0, hipStream_t s) {
+  if (c.W % 64 || c.H % 2 || c.ldw < 1152 || c.ypitch1 % 8 || c.pitch1 % 8 || c.pitch2 % 8) return -1;
+  if (c.xbytes1 >= (1l << 31) || c.xbytes2 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.wbytes >= (1l << 31))
+    return -1;
+  if ((c.escale == nullptr) != (c.eshift == nullptr)) return -1;
   Ring2Args a;
-  a.x0 = (const u16*)x0; a.x1 = (const u16*)x1;
-  a.xbytes0 = (uint32_t)xbytes0; a.xbytes1 = (uint32_t)xbytes1; a.pitch0 = pitch0; a.pitch1 = pitch1;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y = (u16*)y; a.ybytes = (uint32_t)ybytes; a.ypitch = ypitch;
-  a.stats = stats; a.escale = escale; a.eshift = eshift; a.erelu = erelu;
+  a.x0 = (const u16*)c.x1; a.x1 = (const u16*)c.x2;
+  a.xbytes0 = (uint32_t)c.xbytes1; a.xbytes1 = (uint32_t)c.xbytes2; a.pitch0 = c.pitch1; a.pitch1 = c.pitch2;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
+  a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
+  a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
   if (cout_total < 64 || co0 < 0 || co0 + 64 > cout_total) return -1;
   a.scout = cout_total; a.co0 = co0;
-  a.H = H; a.W = W; a.WS = W / 64;
-  a.nrows = N * a.WS * H;
+  a.H = c.H; a.W = c.W; a.WS = c.W / 64;
+  a.nrows = c.N * a.WS * c.H;
   a.npairs = a.nrows / 2;
   const int blocks = std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, a.npairs));
   a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
   const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
-  const FastDiv fh = make_fastdiv((uint32_t)H), fs = make_fastdiv((uint32_t)a.WS);
+  const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)a.WS);
   a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
   hipLaunchKernelGGL(conv_ring2_kernel, dim3(grid), dim3(512), 0, s, a);
   return grid * 4;

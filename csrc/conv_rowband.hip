@@ -28,6 +28,7 @@
 // The eval dispatch is rdp_conv_rowband_frag_auto (bindings conv_fwd with the executor's fragment-major
 // weights); rdp_conv_rowband_bytes is the OHWI form's traffic model used by rdp_conv_igemm.
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -512,11 +513,10 @@ __global__ __launch_bounds__(512, 4) void conv_rowband_chain_kernel(const Rowban
   }
 }
 
-// Operand bytes the kernel moves from L2 (every block re-reads its weight slice; every activation is read
-// once per tap and per 32-channel output slice). Measured (scripts/rowband_bench.py, N = 1, MI355X) the
-// kernel runs at ~8-9 TB/s of these bytes: it beats the split-K implicit GEMM + reduce pair at <= ~150 MB
-// (17-25 % faster on the 64^2 128 -> 256, 32^2 256 -> 512, 16^2 512 -> 512, 32^2 512 -> 256 and
-// 64^2 256 -> 128 layers) and loses from ~225 MB up (32^2 1024 -> 512: 64 vs 27 us).
+// Measured (scripts/rowband_bench.py, N = 1, MI355X) the kernel runs at ~8-9 TB/s of these bytes: it beats the
+// split-K implicit GEMM + reduce pair at <= ~150 MB (17-25 % faster on the 64^2 128 -> 256, 32^2 256 -> 512,
+// 16^2 512 -> 512, 32^2 512 -> 256 and 64^2 256 -> 128 layers) and loses from ~225 MB up (32^2 1024 -> 512: 64
+// vs 27 us).
 extern "C" long rdp_conv_rowband_bytes(int N, int H, int W, int Cin, int Cout, int pool) {
   const int R = pool && H % 2 == 0 && 2 * W <= 64 ? 2 : 1;
   const long wb = (long)Cout * 9 * Cin * 2, xb = (long)N * H * W * Cin * 2;
@@ -530,10 +530,6 @@ extern "C" long rdp_conv_rowband_bytes(int N, int H, int W, int Cin, int Cout, i
 // <= 64^2 layer of the U-Net but the two long-K decoder convs (32^2 1024 -> 512, 64^2 512 -> 256).
 static int ilog2_exact(long v);
 
-// C1 / C2: the two sources' channels (C2 = 0 for one source). Every shape predicate rdp_conv_rowband_ex
-// applies is checked here too, so a mode this returns is never rejected by the launch (W and Cin / 32
-// powers of two, each source a multiple of 32 channels); the Python executor asks this same function
-// (binding rowband_frag_mode) which layers need a fragment-major weight copy.
 extern "C" int rdp_conv_rowband_frag_auto(int N, int H, int W, int C1, int C2, int Cout) {
   static const int on = [] {
     const char* e = getenv("RDP_ROWBAND");
@@ -572,38 +568,27 @@ static int ilog2_exact(long v) {
   return (1L << s) == v ? s : -1;
 }
 
-// Returns 1 if it also wrote the pool, 0 if not, < 0 (nothing launched) when the shape does not fit.
-// wfrag: w is the fragment-major copy of the OHWI weights (rdp_rowband_frag_weights) instead of OHWI.
-extern "C" int rdp_conv_rowband_ex(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2,
-                                   int pitch1, int pitch2, const void* w, long wbytes, int ldw, void* y, long ybytes,
-                                   int ypitch, int N, int H, int W, int Cout, const float* escale, const float* eshift,
-                                   int erelu, void* pool, long pbytes, int ppitch, int wfrag, hipStream_t s);
-extern "C" int rdp_conv_rowband(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2, int pitch1,
-                                int pitch2, const void* w, long wbytes, int ldw, void* y, long ybytes, int ypitch, int N,
-                                int H, int W, int Cout, const float* escale, const float* eshift, int erelu, void* pool,
-                                long pbytes, int ppitch, hipStream_t s) {
-  return rdp_conv_rowband_ex(x1, x2, xbytes1, xbytes2, C1, C2, pitch1, pitch2, w, wbytes, ldw, y, ybytes, ypitch, N, H,
-                             W, Cout, escale, eshift, erelu, pool, pbytes, ppitch, 0, s);
+extern "C" int rdp_conv_rowband(const RdpConv& c, void* pool, long pbytes, int ppitch, hipStream_t s) {
+  return rdp_conv_rowband_ex(c, pool, pbytes, ppitch, 0, s);
 }
 
-extern "C" int rdp_conv_rowband_ex(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2,
-                                   int pitch1, int pitch2, const void* w, long wbytes, int ldw, void* y, long ybytes,
-                                   int ypitch, int N, int H, int W, int Cout, const float* escale, const float* eshift,
-                                   int erelu, void* pool, long pbytes, int ppitch, int wfrag, hipStream_t s) {
-  const int Cin = C1 + C2;
-  const int cs = ilog2_exact(Cin / 32), ws = ilog2_exact(W);
-  if (C1 % 32 || C2 % 32 || Cin < 64 || Cin % 32 || cs < 0 || ws < 4 || W > (wfrag == 2 ? 256 : 64) || Cout % 32)
+extern "C" int rdp_conv_rowband_ex(const RdpConv& c, void* pool, long pbytes, int ppitch, int wfrag, hipStream_t s) {
+  const int Cin = c.C1 + c.C2;
+  const int cs = ilog2_exact(Cin / 32), ws = ilog2_exact(c.W);
+  if (c.C1 % 32 || c.C2 % 32 || Cin < 64 || Cin % 32 || cs < 0 || ws < 4 || c.W > (wfrag == 2 ? 256 : 64) ||
+      c.Cout % 32)
     return -1;
-  if (!escale || !eshift || (!wfrag && ldw < 9 * Cin) || (wfrag && wbytes < (long)Cout * 9 * Cin * 2) || (C2 && !x2))
+  if (!c.escale || !c.eshift || (!wfrag && c.ldw < 9 * Cin) || (wfrag && c.wbytes < (long)c.Cout * 9 * Cin * 2) ||
+      (c.C2 && !c.x2))
     return -1;
-  if (pitch1 % 8 || (C2 && pitch2 % 8) || ypitch % 4) return -1;
-  if (xbytes1 >= (1L << 31) || xbytes2 >= (1L << 31) || wbytes >= (1L << 31) || ybytes >= (1L << 31) ||
+  if (c.pitch1 % 8 || (c.C2 && c.pitch2 % 8) || c.ypitch1 % 4) return -1;
+  if (c.xbytes1 >= (1L << 31) || c.xbytes2 >= (1L << 31) || c.wbytes >= (1L << 31) || c.ybytes1 >= (1L << 31) ||
       pbytes >= (1L << 31))
     return -1;
   if (wfrag == 2) {  // the activation-staged kernel: 32-channel chunks (a multiple of 8, or 2 / 4)
     if ((Cin / 32) % 8 && Cin != 64 && Cin != 128) return -1;
-    const int WB = W < 32 ? W : 32;
-    const bool plx = pool != nullptr && H % 2 == 0 && ppitch % 4 == 0;
+    const int WB = c.W < 32 ? c.W : 32;
+    const bool plx = pool != nullptr && c.H % 2 == 0 && ppitch % 4 == 0;
     // two-row tiles (each block's weight slice serves twice the pixels) wherever that grid still has >= 256
     // blocks: up1.conv1 22.4 -> 18.2 us, up2.conv1 24.5 -> 21.9, down3.conv1 7.8 -> 6.9 (at 128 blocks, the
     // 16^2 and 32^2 -> 256 convs, one-row tiles stay faster); RDP_ROWBAND_R2=0 keeps one-row tiles (A/B)
@@ -611,19 +596,20 @@ extern "C" int rdp_conv_rowband_ex(const void* x1, const void* x2, long xbytes1,
       const char* e = getenv("RDP_ROWBAND_R2");
       return e ? atoi(e) : 1;
     }();
-    const bool r2 = r2_on && H % 2 == 0 && (long)N * (H / 2) * (W / (W < 32 ? W : 32)) * (Cout / 32) >= 256;
+    const bool r2 =
+        r2_on && c.H % 2 == 0 && (long)c.N * (c.H / 2) * (c.W / (c.W < 32 ? c.W : 32)) * (c.Cout / 32) >= 256;
     const int Rx = plx || r2 ? 2 : 1;
     RowbandArgs a;
-    a.x1 = (const u16*)x1; a.x2 = (const u16*)x2;
-    a.xbytes1 = (uint32_t)xbytes1; a.xbytes2 = (uint32_t)xbytes2;
-    a.C1 = C1; a.C2 = C2; a.pitch1 = pitch1; a.pitch2 = pitch2;
-    a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-    a.y = (u16*)y; a.ybytes = (uint32_t)ybytes; a.ypitch = ypitch;
+    a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
+    a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
+    a.C1 = c.C1; a.C2 = c.C2; a.pitch1 = c.pitch1; a.pitch2 = c.pitch2;
+    a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
+    a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
     a.pool = plx ? (u16*)pool : nullptr; a.pbytes = plx ? (uint32_t)pbytes : 0u; a.ppitch = ppitch;
-    a.escale = escale; a.eshift = eshift; a.erelu = erelu;
-    a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.wshift = ws;
-    a.R = Rx; a.bands = H / Rx; a.cshift = cs; a.T = 9 * Cin / 32; a.wfrag = 1; a.segs = W / WB;
-    const int grid = N * a.bands * a.segs * (Cout / 32);
+    a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
+    a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.wshift = ws;
+    a.R = Rx; a.bands = c.H / Rx; a.cshift = cs; a.T = 9 * Cin / 32; a.wfrag = 1; a.segs = c.W / WB;
+    const int grid = c.N * a.bands * a.segs * (c.Cout / 32);
     const int PBx = Rx * WB;
     if (PBx == 16) hipLaunchKernelGGL((conv_rowband_x_kernel<1, 1>), dim3(grid), dim3(512), 0, s, a);
     else if (PBx == 32 && Rx == 1) hipLaunchKernelGGL((conv_rowband_x_kernel<2, 1>), dim3(grid), dim3(512), 0, s, a);
@@ -633,20 +619,20 @@ extern "C" int rdp_conv_rowband_ex(const void* x1, const void* x2, long xbytes1,
     return plx ? 1 : 0;
   }
   // the pool needs two rows per block: only where that block is <= 64 pixels (else the caller pools)
-  const bool pl = pool != nullptr && H % 2 == 0 && ppitch % 4 == 0 && 2 * W <= 64;
+  const bool pl = pool != nullptr && c.H % 2 == 0 && ppitch % 4 == 0 && 2 * c.W <= 64;
   const int R = pl ? 2 : 1;
-  const int PB = R * W;
+  const int PB = R * c.W;
   RowbandArgs a;
-  a.x1 = (const u16*)x1; a.x2 = (const u16*)x2;
-  a.xbytes1 = (uint32_t)xbytes1; a.xbytes2 = (uint32_t)xbytes2;
-  a.C1 = C1; a.C2 = C2; a.pitch1 = pitch1; a.pitch2 = pitch2;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y = (u16*)y; a.ybytes = (uint32_t)ybytes; a.ypitch = ypitch;
+  a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
+  a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
+  a.C1 = c.C1; a.C2 = c.C2; a.pitch1 = c.pitch1; a.pitch2 = c.pitch2;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
+  a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
   a.pool = pl ? (u16*)pool : nullptr; a.pbytes = pl ? (uint32_t)pbytes : 0u; a.ppitch = ppitch;
-  a.escale = escale; a.eshift = eshift; a.erelu = erelu;
-  a.N = N; a.H = H; a.W = W; a.Cout = Cout; a.wshift = ws;
-  a.R = R; a.bands = H / R; a.cshift = cs; a.T = 9 * Cin / 32; a.wfrag = wfrag;
-  const int grid = N * a.bands * (Cout / 32);
+  a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.wshift = ws;
+  a.R = R; a.bands = c.H / R; a.cshift = cs; a.T = 9 * Cin / 32; a.wfrag = wfrag;
+  const int grid = c.N * a.bands * (c.Cout / 32);
   if (PB == 16) hipLaunchKernelGGL((conv_rowband_kernel<2, 1, 4>), dim3(grid), dim3(512), 0, s, a);
   else if (PB == 32) hipLaunchKernelGGL((conv_rowband_kernel<2, 2, 2>), dim3(grid), dim3(512), 0, s, a);
   else if (PB == 64) hipLaunchKernelGGL((conv_rowband_kernel<2, 4, 1>), dim3(grid), dim3(512), 0, s, a);
@@ -654,9 +640,6 @@ extern "C" int rdp_conv_rowband_ex(const void* x1, const void* x2, long xbytes1,
   return pl ? 1 : 0;
 }
 
-// The chain launch: layer 0 reads x (C0 channels), layer l > 0 reads layer l - 1's output; every layer is
-// an eval conv (BN folded + ReLU) on the same N x H x W map. cnt: >= 1 + nl * N * H ints, err: 1 int.
-// Returns 0, or < 0 (nothing launched) when a layer does not fit the row-band kernel.
 extern "C" int rdp_conv_rowband_chain(int nl, const void* x, long xbytes, int C0, int xpitch, const void* const* w,
                                       const long* wbytes, const int* ldw, void* const* y, const long* ybytes,
                                       const int* ypitch, const int* cout, const float* const* escale,

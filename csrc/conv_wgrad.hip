@@ -24,6 +24,7 @@
 // PMC (256^2 x 64ch): ~48 % of wave cycles in s_waitcnt/barrier, i.e. latency-bound on x/dY
 // streamed from HBM with only one K step of lookahead.
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
 #include <string.h>
@@ -836,11 +837,6 @@ extern "C" int rdp_conv_wgrad(const void* x1, const void* x2, long xbytes1, long
   return a.splits;
 }
 
-// ConvTranspose2d(k=2, s=2) weight gradient straight from its output gradient du [N][H2][W2][C] (the
-// window 2h x 2w at (oy, ox)) and its input x [N][h][w][Cin]: out[ci][(sub, c)] (+)= sum_px
-// x[px][ci] du[sub-pixel sub of px][c] -- the generic kernel's role-swapped GEMM (columns = the 4
-// sub-pixels x C, "couts" = Cin) reading du at the sub-pixels instead of an unshuffled copy.
-// Returns the split count, or < 0 if the shape does not fit.
 extern "C" int rdp_conv_wgrad_upT(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
                                   const void* x, long xbytes, int Cin, int xpitch, int N, int h, int w, float* slab,
                                   long slab_elems, float* out, int accumulate, int splits, hipStream_t s) {
@@ -1042,7 +1038,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_first_bn_kernel(const FirstWgrad
   }
 }
 
-// Returns the number of splits, or < 0 (nothing launched) when the shape does not fit this kernel.
 extern "C" int rdp_wgrad_first_bn(const void* x, long xbytes, int xpitch, const void* da, long dabytes, int dapitch,
                                   const void* y, long ybytes, int ypitch, const float* coef, const float* coef2,
                                   float* slab, long slab_elems, float* out, int accumulate, int N, int H, int W,
@@ -1072,12 +1067,6 @@ extern "C" int rdp_wgrad_first_bn(const void* x, long xbytes, int xpitch, const 
   return splits;
 }
 
-// Slab size (elements) for the generic kernel's `splits` pixel splits. The halo / row-ring kernels choose
-// their own split count, capped by the slab they are given: the training step shares one slab of the
-// largest generic size, which caps the deep layers' halo wgrads at 4-15 splits (~120 blocks). That is
-// deliberate: sized for a full wave of halo blocks (rdp_conv_wgrad_halo_slab_elems) the wgrads run ~1.8x
-// faster alone but the step got slower -- bs 64 3,120-3,131 vs 3,160-3,181 img/s, bs 4 1,405-1,409 vs
-// 1,591 (same box, 2 rounds): the side-stream wgrads then take every CU from the main stream's convs.
 extern "C" long rdp_conv_wgrad_slab_elems(int N, int H, int W, int Cin, int Cout, int taps, int packed, int splits) {
   const int ncols = packed ? 72 : taps * Cin;
   const int ncols_pad = (ncols + 255) / 256 * 256;
@@ -1088,8 +1077,6 @@ extern "C" long rdp_conv_wgrad_slab_elems(int N, int H, int W, int Cin, int Cout
   return sp * Cout * ncols_pad;
 }
 
-// Slab the halo / row-ring wgrad needs for one resident wave of blocks (its own split choice
-// unconstrained); 0 where the dispatch does not pick those kernels. (conv_microbench.py sizes with it.)
 extern "C" long rdp_conv_wgrad_halo_slab_elems(int N, int H, int W, int Cin, int Cout) {
   const long M = (long)N * H * W;
   const bool halo = Cin % 64 == 0 && Cout % 64 == 0 && (W % 64 == 0 || (W >= 32 && 64 % W == 0 && (H * W) % 64 == 0));

@@ -20,6 +20,7 @@
 //   index_select + data/device_data.py:batch_to_float + UNetExecutor.set_input produce (the oracle:
 //   data/augment.py:augment_batch_reference).
 #include "common.h"
+#include "rdp_api.h"
 
 #define AREA_MAXTAP 32
 
@@ -123,7 +124,6 @@ __global__ __launch_bounds__(256) void batch_augment_kernel(const uint8_t* __res
 }
 
 extern "C" {
-// exactly one of tgt_f (one-class: fp32 mask value) / tgt_u (K-class: u8 id, 255 outside the frame) is set
 int rdp_batch_augment(const void* x, const void* y, const int* idx, const float* params, int S, int N, int H, int W,
                       void* x_out, float* tgt_f, void* tgt_u, hipStream_t s) {
   if ((tgt_f == nullptr) == (tgt_u == nullptr)) return -1;

@@ -35,6 +35,7 @@
 // [3] fp, [4] mean kappa, [5] max kappa, [6] E edge points, [7] valid points, [8..] nsamp x 3 points,
 // [8 + 3 nsamp] mask coverage count (serving form; -1 without coverage input).
 #include "common.h"
+#include "rdp_api.h"
 #include "geo_sort.h"
 #include <stdint.h>
 
@@ -896,7 +897,6 @@ __global__ __launch_bounds__(SPL_THREADS) void geo_fit_batch_kernel(const FitFra
 extern "C" {
 int rdp_geo_spline_res_len(int nsamp) { return 9 + 3 * nsamp; }
 
-// rdp_geo_spline (presorted, serving) for n <= 4 frames in one launch: per-frame arrays of its buffers
 int rdp_geo_spline_batch(int n, int nbins, int kcap, const int* const* kout, const int* const* npts,
                          double* const* sorted, double* const* u, int ecap, double s, int k, int nsamp, double eps,
                          int min_points, int min_edge, const int* const* cov, int ncov, double* const* res,
@@ -926,7 +926,6 @@ int rdp_geo_spline_batch(int n, int nbins, int kcap, const int* const* kout, con
   return 0;
 }
 
-// sort the per-bin edge points (out [nbins][kcap][4], kout) into sorted [ecap][3] and fit/evaluate.
 int rdp_geo_spline(const double* out, int nbins, int kcap, const int* kout, const int* npts, double* sorted,
                    int* gperm, double* u, int ecap, double s, int k, int nsamp, double eps, int min_points,
                    int min_edge, const int* cov, int ncov, double* res, double* dbg, int presorted,

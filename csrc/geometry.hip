@@ -18,6 +18,7 @@
 //                then writes the bin's k points (x, y, z, index) into a per-bin output slab, and
 //                (serving) x-sorts them into the packed edge array (geo_sort.h)
 #include "common.h"
+#include "rdp_api.h"
 #include "geo_sort.h"
 #include <stdint.h>
 #include <stdlib.h>
@@ -613,16 +614,8 @@ __global__ __launch_bounds__(256) void geo_select_wave_batch_kernel(const GeoFra
 extern "C" {
 int rdp_geo_nblocks(int H) { return (H + GEO_ROWS_PER_BLOCK - 1) / GEO_ROWS_PER_BLOCK; }
 
-// int32 workspace needed beyond the per-row-block counts: bin_of + bidx [cap] each + 2 x 128
 long rdp_geo_work_ints(int H, int W) { return (long)rdp_geo_nblocks(H) + 2L * H * W + 256; }
 
-// work_i: [nblk] counts | [cap] bin_of | [cap] bidx | [128] cnt | [128] cursor ; work_d: xmin/xmax
-// pts [cap][4]; out [nbins][kcap][4]
-// m256 != nullptr (serving form): `mask` is an OUTPUT, derived from the mh x mw model mask by
-// nearest upsampling, and cov[nblk] receives per-row-block coverage counts. edges == nullptr: no
-// packed edge list (the on-device spline reads the per-bin slabs directly). sorted != nullptr: the
-// x-sorted edge points [secap][3] are written too (gperm: 2*secap ints of sort scratch), so the
-// spline stage runs with presorted = 1.
 int rdp_geo_edges(const void* mask, const void* depth, int H, int W, double fx, double fy, double cx, double cy,
                   double scale, int* counts, double* xmin, double* xmax, double* pts, int cap, int* npts,
                   double* out, int kcap, int* kout, int nbins, double top, int min_points, double* edges,
@@ -659,10 +652,6 @@ int rdp_geo_edges(const void* mask, const void* depth, int H, int W, double fx, 
   return nblk;
 }
 
-// The serving form of rdp_geo_edges for n <= GEO_BATCH frames of one camera in ONE launch per stage
-// (blockIdx.y = frame): each frame's buffers as rdp_geo_edges takes them (array of n per field). The
-// stages are latency-bound small grids, so n frames cost about what one does (a batch of 4 served frames:
-// 4 x 48 us of geometry as per-frame launches, profiles/serve_batch.md).
 int rdp_geo_edges_batch(int n, const void* const* mask, const void* const* depth, int H, int W, double fx, double fy,
                         double cx, double cy, double scale, int* const* counts, double* const* xmin,
                         double* const* xmax, double* const* pts, int cap, int* const* npts, double* const* out,

@@ -11,6 +11,7 @@
 //   per-block partials of dW (64) and db.
 // 8 lanes per pixel (16 B each = 8 channels), so every access is a full 128-B line per pixel.
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 
 #define HEAD_C 64
@@ -446,8 +447,6 @@ static int blocks_for(long M) { return (int)std::max<long>(1, std::min<long>((M 
 extern "C" {
 int rdp_head_partial_blocks(long M) { return blocks_for(M); }
 
-// coef != nullptr: `a` is the last conv's pre-BN output; BN+ReLU are applied on the fly.
-// gpart/bnpart != nullptr (needs coef, dice_w == 0): also the backward partials (head_fwd_kernel GRAD).
 int rdp_head_fwd(const void* a, int apitch, const float* w, const float* b, const float* target, float* logits,
                  float* partial, float* sums, float* loss, int M, float dice_w, float dice_eps, const float* coef,
                  float* gpart, float* bnpart, float gscale, hipStream_t s) {
@@ -467,14 +466,11 @@ int rdp_head_fwd(const void* a, int apitch, const float* w, const float* b, cons
   return nb;
 }
 
-// head weight / bias gradient from the [nb][65] partials of a GRAD forward
 int rdp_head_grad_finalize(const float* gpart, int M, float* gw, float* gb, hipStream_t s) {
   hipLaunchKernelGGL(head_grad_finalize_kernel, dim3(HEAD_C + 1), dim3(256), 0, s, gpart, blocks_for(M), gw, gb);
   return 0;
 }
 
-// coef != nullptr: BN-fused variant (da unused; bnpart receives the BN backward partial rows).
-// Returns the number of partial rows.
 int rdp_head_bwd(const void* a, int apitch, const float* w, const float* logits, const float* target,
                  const float* sums, void* da, int dapitch, float* partial, float* gw, float* gb, int M, float dice_w,
                  float dice_eps, float gscale, const float* coef, float* bnpart, hipStream_t s) {

@@ -24,6 +24,7 @@
 // steps (KP = K rounded up to a power of two) lane `sub` owns logit `sub & (KP - 1)` -- 7 shuffles
 // at K = 8 where K separate butterflies would take 24.
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 
 #define HEAD_C 64
@@ -370,7 +371,6 @@ void launch_mask(int nb, hipStream_t s, const void* a, int apitch, const float* 
 extern "C" {
 int rdp_headk_partial_blocks(long M) { return blocks_for(M); }
 
-// partial: >= blocks * 2 floats. Returns the number of partial rows, < 0 if nothing was launched.
 int rdp_headk_fwd(const void* a, int apitch, const float* w, const float* b, const void* labels, float* logits,
                   float* partial, float* sums, float* loss, int M, int K, hipStream_t s) {
   if (apitch % 8 || M <= 0) return -1;
@@ -380,7 +380,6 @@ int rdp_headk_fwd(const void* a, int apitch, const float* w, const float* b, con
   return nb;
 }
 
-// partial: >= blocks * (K * 64 + K) floats; gw [K][64], gb [K]
 int rdp_headk_bwd(const void* a, int apitch, const float* w, const float* logits, const void* labels,
                   const float* sums, void* da, int dapitch, float* partial, float* gw, float* gb, int M, int K,
                   float gscale, hipStream_t s) {

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "host_pool.h"
+#include "rdp_host_api.h"
 #include "jpeg_sync.h"
 
 namespace {
@@ -500,9 +501,6 @@ bool fill_tables(const Jpeg& j, jsync::Tables& T) {
 
 extern "C" {
 
-// Header summary. info (int[24]): width, height, ncomp, hmax, vmax, mcux, mcuy, restart, segments,
-// then per component (3 x 5): h, v, bw, bh, tq. Returns the coefficient count, or -1 corrupt / -2
-// unsupported.
 long rdp_jpeg_info(const uint8_t* d, long n, int* info) {
   Jpeg j;
   const int r = parse(d, n, j);
@@ -511,9 +509,6 @@ long rdp_jpeg_info(const uint8_t* d, long n, int* info) {
   return j.total_coefs;
 }
 
-// The pixel stage's geometry block (meta int32[32]: W, H, ncomp, hmax, vmax, total blocks; per component
-// c at 8 + 8c: h, v, blocks per line, block rows, first block, plane byte offset, downsampled width,
-// height) from rdp_jpeg_info's header summary `hi`.
 void rdp_jpeg_meta(const int* hi, int* g) {
   const int W = hi[0], H = hi[1], nc = hi[2], hmax = hi[3], vmax = hi[4];
   for (int i = 0; i < 32; ++i) g[i] = 0;
@@ -531,9 +526,6 @@ void rdp_jpeg_meta(const int* hi, int* g) {
   g[5] = (int)blk;
 }
 
-// Entropy-decode into `coefs` (rdp_jpeg_info's count, int16, plane after plane, blocks row-major,
-// natural order, quantized) and the component quantisation tables into qt[3][64] (natural order).
-// Restart segments are decoded in parallel when `parallel`. 0 ok, -1 corrupt, -2 unsupported.
 int rdp_jpeg_decode(const uint8_t* d, long n, int16_t* coefs, long ncoefs, uint16_t* qt, int parallel) {
   Jpeg j;
   int r = parse(d, n, j);
@@ -584,8 +576,6 @@ long rdp_jpeg_entropy_work_words(long cap_bytes, int S) {
   return jsync::work_layout(cap_bytes, S).words;
 }
 
-// Upper bound of rdp_jpeg_scan's output for this stream (its entropy-coded bytes, rounded up to whole
-// 32-bit words), or parse()'s error.
 long rdp_jpeg_scan_bound(const uint8_t* d, long n) {
   Jpeg j;
   const int r = parse(d, n, j);
@@ -593,12 +583,6 @@ long rdp_jpeg_scan_bound(const uint8_t* d, long n) {
   return ((j.scan_end - j.scan_begin) + 3) / 4 * 4 + 4;
 }
 
-// Front end of the GPU entropy decoder: what rdp_jpeg_decode accepts, without restart markers. meta
-// (int32[224]: rdp_jpeg_meta's geometry, then the three quantisation tables), the packed Huffman tables
-// (rdp_jpeg_tables_bytes()), and the scan bytes with the 0xFF00 stuffing removed, cut at the first marker,
-// into scan[cap] (cap a multiple of 4); *nbits = 8 x the bytes written. No entropy work. 0 ok, -1 corrupt,
-// -2 unsupported here (restart markers, more than two tables of a class, a scan above `cap`): the
-// host decoder runs.
 int rdp_jpeg_scan(const uint8_t* d, long n, int* meta, uint8_t* tables, uint8_t* scan, long cap, int* nbits) {
   Jpeg j;
   const int r = parse(d, n, j);
@@ -633,10 +617,6 @@ int rdp_jpeg_scan(const uint8_t* d, long n, int* meta, uint8_t* tables, uint8_t*
   return 0;
 }
 
-// The GPU decoder's stages (jpeg_entropy.hip) as plain loops over the same per-lane code, workgroup by
-// workgroup and round by round, so results and statistics equal the kernels'. scan[cap_bytes] (a multiple
-// of 4, 4-byte aligned), S bits per subsequence (0: the default). *status: 0 ok, 1 corrupt (whenever
-// rdp_jpeg_decode returns -1); stats (optional): subsequences, rounds. Returns -1 on bad arguments.
 int rdp_jpeg_entropy_emulate(const uint8_t* scan, long cap_bytes, int nbits, const uint8_t* tables, const int* geo,
                              int16_t* coefs, long cap_coefs, int S, int* status, int* stats) {
   using namespace jsync;

@@ -22,6 +22,7 @@
 // No loop's trip count depends on how fast the data synchronises beyond those bounds; every store is
 // guarded by the block count of the frame and of the output buffer.
 #include "common.h"
+#include "rdp_api.h"
 #include "jpeg_sync.h"
 
 using namespace jsync;
@@ -235,11 +236,6 @@ __global__ __launch_bounds__(kLanes) void jpeg_dc_kernel(const Args a) {
 
 }  // namespace
 
-// scan: cap_bytes (a multiple of 4) of de-stuffed scan, of which *nbits (device) are the frame's; tables:
-// rdp_jpeg_scan's block; geo: rdp_jpeg_meta's int32[32]; coefs: cap_coefs int16 (16-byte aligned);
-// work: rdp_jpeg_entropy_work_words(cap_bytes, S) int32; status: one device-visible int32 (0 ok, 1
-// corrupt). S: bits per subsequence, a multiple of 32, >= 64, 0 = the tuned default. After the launches
-// work[stats_word] holds (subsequences, rounds); *stats_word (optional) receives that offset.
 extern "C" int rdp_jpeg_entropy_gpu(const void* scan, long cap_bytes, const int* nbits, const void* tables,
                                     const int* geo, void* coefs, long cap_coefs, int* work, long work_words,
                                     int* status, int S, long* stats_word, hipStream_t st) {

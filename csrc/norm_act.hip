@@ -9,6 +9,7 @@
 // per-channel affine (scale, shift) applied by bn_relu_apply. Backward is a two-pass
 // reduce (sum g, sum g*xhat) -> finalize (dgamma, dbeta, 3 apply coefficients) -> apply.
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -417,7 +418,6 @@ int rdp_bn_relu_apply(const void* y, int ypitch, void* out, int opitch, const fl
   return 0;
 }
 
-// returns the number of partial rows written (T for bn_bwd_finalize)
 int rdp_bn_relu_bwd_reduce(const void* da, int dapitch, const void* y, int ypitch, const float* coef, int M, int C,
                            int relu, float* partial, int max_blocks, hipStream_t s) {
   if (C % 8 || C > 2048) return -1;

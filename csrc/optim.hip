@@ -11,6 +11,7 @@
 //   kind 0: dgrad weights  Wt[cin][8-tap][cout] = W[cout][tap][cin]   (flip + transpose)
 //   kind 1: packed first layer  Wp[cout][16][8] (taps 0..8, channels 0..cin-1, zeros elsewhere)
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -162,10 +163,6 @@ __global__ __launch_bounds__(256) void wprep_kernel(const float* __restrict__ ma
 }
 
 extern "C" {
-// inc = 0: the caller advances the step counter later on this stream (rdp_wprep with step)
-// g_bf16: g is bf16 (u16) instead of fp32
-// max_blocks > 0 caps the grid (grid-stride loop): the overlapped update on the side stream leaves CUs to
-// the next forward's first layers
 int rdp_adam(float* p, const void* g, int g_bf16, float* m, float* v, void* shadow, long n, float lr, float b1,
              float b2, float eps, float wd, float gscale, int* step, int inc, int max_blocks, hipStream_t s) {
   if (n % 4) return -1;
@@ -188,9 +185,6 @@ int rdp_cast_bf16(const float* p, void* out, long n, hipStream_t s) {
   return 0;
 }
 
-// segs: device array of nseg WSeg {long src, long dst, int kind, cout, cin, taps, tile0, pad} (40 bytes
-// each; tile0 = the running sum of wseg_tiles over the earlier segments); tiles = the table's total tile
-// count (the caller's sum), blocks = grid cap (0: one block per tile, at most 4096)
 int rdp_wprep(const float* master, void* out, const void* segs, int nseg, int* step, int tiles, int blocks,
               hipStream_t s) {
   if (nseg <= 0 || tiles <= 0) {

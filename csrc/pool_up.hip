@@ -11,6 +11,7 @@
 //     (F.pad with [dx//2, dx-dx//2, dy//2, dy-dy//2]); the rest is zero. Backward is a
 //     deterministic gather (no atomics) that re-derives the forward's exact index/weight arithmetic.
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 
 RDP_DEV void unpack8f(const uint4& v, float* f) {
@@ -710,8 +711,6 @@ int rdp_bn_relu_apply_pool(const void* y, int ypitch, void* a, int apitch, void*
                      (u16*)pool, ppitch, coef, N, H, W, C);
   return 0;
 }
-// returns the number of partial rows written (T for bn_bwd_finalize), -1 if not applicable
-// x: the stored activation (pitch check only: the argmax is recomputed from y)
 int rdp_maxpool2_bwd_bn_reduce(const void* dp, int dppitch, const void* x, int xpitch, const void* dskip, int dspitch,
                                void* dx, int dxpitch, const void* y, int ypitch, const float* coef, int N, int H, int W,
                                int C, float* partial, int max_blocks, hipStream_t s) {
@@ -749,8 +748,6 @@ int rdp_upsample2_fwd(const void* x, int xpitch, void* out, int opitch, int N, i
                      xpitch, (u16*)out, opitch, g, lcg, nchunk, R, coef);
   return 0;
 }
-// y/coef/partial given: fused BN-backward reduction of dx's consumer BN; returns the partial rows
-// written (<= max_blocks). Otherwise returns 0.
 int rdp_upsample2_bwd(const void* dout, int dpitch, void* dx, int xpitch, int N, int hin, int win, int Hout, int Wout,
                       int oy, int ox, int C, const void* y, int ypitch, const float* coef, float* partial,
                       int max_blocks, hipStream_t s) {
@@ -790,7 +787,6 @@ int rdp_upT_unshuffle(const void* du, int dpitch, void* dyT, int ypitch, int N, 
                      (const u16*)du, dpitch, (u16*)dyT, ypitch, g);
   return 0;
 }
-// partial must hold >= 1024 * K + 2 * FOLD_RB * K / groups floats
 int rdp_colsum_bf16(const void* x, int pitch, long M, int K, int groups, float* partial, float* out, int accumulate,
                     hipStream_t s) {
   if (K < 8 || K > 2048 || (K & (K - 1)) || K % groups || pitch % 8) return -1;

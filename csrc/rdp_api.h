@@ -1,0 +1,372 @@
+// The GPU launchers (rdp_*) and their sizing helpers: the one declaration of each, included by the .hip file
+// that defines it and by every caller (csrc/bindings.cpp, csrc/serve_runtime.cpp, the conv dispatcher), so the
+// compiler compares definition and use. Every launcher enqueues on the given stream and returns without waiting.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include "rdp_host_api.h"
+
+// ---- the conv family's operand blocks ----------------------------------------------------------------------------
+// Activations are NHWC bf16 views: pointer, extent in bytes (the kernels size their buffer descriptors from it;
+// every extent must stay below 2 GiB), channels and pixel pitch in elements. Every field defaults to zero / null;
+// a launcher ignores the fields its kernel has no use for. The blocks hold values only: a launch that is recorded
+// for replay keeps a copy. Host cells a launch writes its result to (int*) are separate parameters.
+struct RdpConv {
+  // the sources: the conv reads cat(x1, x2) along channels (one source: x2 = nullptr, C2 = 0)
+  const void* x1 = nullptr;
+  const void* x2 = nullptr;
+  long xbytes1 = 0, xbytes2 = 0;
+  int C1 = 0, C2 = 0, pitch1 = 0, pitch2 = 0;
+  // the weights, bf16 [Cout][ldw]
+  const void* w = nullptr;
+  long wbytes = 0;
+  int ldw = 0;
+  // the destinations: output channels [0, Cy1) go to y1, [Cy1, Cout) to y2 (one destination: y2 = nullptr)
+  void* y1 = nullptr;
+  void* y2 = nullptr;
+  long ybytes1 = 0, ybytes2 = 0;
+  int Cy1 = 0, ypitch1 = 0, ypitch2 = 0;
+  float* stats = nullptr;  // training: the BN partial (sum, sum of squares) rows, [rows][2][Cout]
+  int N = 0, H = 0, W = 0, Cout = 0;
+  // the eval epilogue y = acc * escale[c] + eshift[c], then ReLU if erelu (both null: none)
+  const float* escale = nullptr;
+  const float* eshift = nullptr;
+  int erelu = 0;
+};
+// rdp_conv_igemm, eval, optional: MaxPool2d(2) of y1 into pool [N][H/2][W/2][Cout], or (exclusive) the bilinear
+// x2 upsample of y1 into up [N][uH][uW][Cout] at (uoy, uox), fused into the split-K reduce when that path runs
+struct RdpConvFuse {
+  void* pool = nullptr;
+  int ppitch = 0;
+  void* up = nullptr;
+  int upitch = 0, uH = 0, uW = 0, uoy = 0, uox = 0;
+};
+// rdp_conv_igemm, training dgrad into one BN + ReLU layer's activation gradient, optional: that layer's pre-BN
+// output bny, its coefficients bncoef [mean|invstd|scale|shift], and bnpart, which receives its BN-backward partial
+// rows from the split-K reduce when that path runs
+struct RdpConvBnBwd {
+  const void* bny = nullptr;
+  int bnypitch = 0;
+  const float* bncoef = nullptr;
+  float* bnpart = nullptr;
+};
+// rdp_conv_ring_ex, optional and exclusive: bn_y / bn_coef = the dgrad form (the BN-backward partial rows of the
+// layer that owns the output go to stats; bn_y: its pre-BN activations, bn_coef: its [mean|invstd|scale|shift],
+// ReLU applied); iscale / ishift = BN + ReLU of the producer layer applied to the staged input rows, which aout
+// (optional) also receives as an activation tensor
+struct RdpRingFuse {
+  const void* bn_y = nullptr;
+  int bn_ypitch = 0;
+  const float* bn_coef = nullptr;
+  const float* iscale = nullptr;
+  const float* ishift = nullptr;
+  void* aout = nullptr;
+  long abytes = 0;
+  int apitch = 0;
+};
+
+extern "C" {
+
+// ---- csrc/comm.hip --------------------------------------------------------------------------------------------
+int rdp_comm_emulate(double us, int blocks, hipStream_t s);
+// scratch: >= 2 * traffic_bytes (16-byte aligned); traffic_bytes: bytes read (and as many written)
+int rdp_comm_emulate_traffic(double us, int blocks, void* scratch, long scratch_bytes, long traffic_bytes,
+                             hipStream_t s);
+
+// ---- csrc/conv_first.hip --------------------------------------------------------------------------------------
+// Returns the number of stats rows written (training) / 0, or -1 if the shape is not this kernel's
+// (3-channel input stored with pitch >= 4, 64 couts, packed [64][128] weights).
+int rdp_conv_first(const RdpConv& c, hipStream_t s);
+
+// ---- csrc/conv_halo.hip ---------------------------------------------------------------------------------------
+// Number of 256-pixel output tiles x cout tiles the halo kernel would use (0 = shape unsupported).
+int rdp_conv_halo_tiles(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed);
+// Returns stats rows written (>= 0) or -1 if unsupported.
+int rdp_conv_halo(const RdpConv& c, hipStream_t s);
+
+// ---- csrc/conv_igemm.hip --------------------------------------------------------------------------------------
+// ConvTranspose2d(k=2, s=2) + bias straight into its (padded) output map u [N][H2][W2][upitch]: the
+// 1x1 GEMM yT[px][sub * C + c] = sum_ci x[px][ci] Wt[sub * C + c][ci] on the ping-pong kernel with the
+// sub-pixel scatter + bias in its epilogue (no yT round trip and no upT_shuffle pass). u's border
+// outside the 2h x 2w window at (oy, ox) is not written (the caller zeroes it once). Returns 0, or -1
+// where the ping-pong grid would not fill the chip / the shape does not fit (the caller then runs the
+// GEMM + upT_shuffle).
+int rdp_conv_upT_fwd(const void* x, long xbytes, int Cin, int pitch, const void* w, long wbytes, int ldw, void* u,
+                     long ubytes, int upitch, const float* bias, int N, int h, int wd, int H2, int W2, int oy,
+                     int ox, int C, hipStream_t s);
+// ConvTranspose2d(k=2, s=2) input gradient straight from the output gradient du [N][H2][W2][C] (the
+// window 2h x 2w at (oy, ox)): dx[px][ci] = sum_(sub, c) du[sub-pixel sub of px][c] Wd[ci][sub * C + c]
+// on the ping-pong kernel, its A operand DMA'd from the 4 sub-pixels as 4 "taps" (no unshuffled copy
+// of du). wd = the [Cin][4C] dgrad weight. Returns 0, or -1 where the ping-pong grid would not fill
+// the chip / the shape does not fit (the caller unshuffles and runs the 1x1 GEMM).
+int rdp_conv_upT_dgrad(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
+                       const void* wd, long wbytes, int ldw, void* dx, long dxbytes, int Cin, int dxpitch, int N,
+                       int h, int wdt, hipStream_t s);
+// The conv dispatcher: forwards to the first-layer, row-band, row-ring and halo launchers where they apply, else
+// runs this file's implicit GEMM. Returns the number of stats-slab rows written, or -1 on unsupported shape.
+// bm_pref % 1000: 0 = auto, else force one kernel (see the definition); bm_pref / 1000: blocks per CU of the
+// persistent grid (0 = 2). ws: the split-K fp32 slab of ws_elems elements (rdp_conv_ws_elems), or nullptr.
+// *pooled = 1 if fuse's pool / upsample was written, else 0 (the caller launches the pool / upsample; nullptr: no
+// fusion). *bnrows = the rows written to bn.bnpart, else 0 (the caller runs bn_relu_bwd_reduce).
+int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int bm_pref, float* ws, long ws_elems,
+                   const RdpConvFuse& fuse, int* pooled, const RdpConvBnBwd& bn, int* bnrows, hipStream_t s);
+// fp32 workspace elements the auto dispatch would use for split-K on this shape (0 = no split)
+long rdp_conv_ws_elems(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed, int bm_pref);
+
+// ---- csrc/conv_ring.hip ---------------------------------------------------------------------------------------
+// The ring kernel (3x3, one 64-channel source, 64 or 128 outputs -- split at a multiple of 32 into two
+// destinations --, W % 64 == 0, even H); max_blocks caps the grid (<= 0: 256). Returns the stats rows it writes,
+// or -1 when not applicable.
+int rdp_conv_ring(const RdpConv& c, int max_blocks, hipStream_t s);
+int rdp_conv_ring_ex(const RdpConv& c, int max_blocks, const RdpRingFuse& f, hipStream_t s);
+// Eval conv (64 -> 64, BN folded + ReLU) fused with the serving 1x1 head: writes only the u8 mask
+// (logit > thr) of the 64-channel output. Returns 0, or -1 when the ring kernel does not apply.
+int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw, int Cout,
+                       int N, int H, int W, const float* escale, const float* eshift, const float* hw,
+                       const float* hb, float hthr, void* mask, hipStream_t s);
+// Eval conv (64 -> 64, BN folded + ReLU) that also writes MaxPool2d(2) of its output into pool
+// [N][H/2][W/2][64] (pixel pitch ppitch). Returns 0, or -1 when the ring kernel does not apply.
+int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipStream_t s);
+// Two-source row ring (see conv_ring2_kernel): x1 / x2 = the two 64-channel sources (for one
+// 128-channel tensor: its two halves), 64 outputs into y1, 3x3, W % 64 == 0, even H. cout_total / co0: the
+// launch computes output channels co0 .. co0 + 63 of a cout_total-channel conv (w, y1, escale / eshift
+// already offset by the caller; the stats rows are [rows][2][cout_total], this launch's 64 columns
+// at co0). Returns the stats rows written (grid * 4), or -1 when not applicable.
+int rdp_conv_ring2(const RdpConv& c, int max_blocks, int cout_total, int co0, hipStream_t s);
+
+// ---- csrc/conv_rowband.hip ------------------------------------------------------------------------------------
+// Operand bytes the kernel moves from L2 (every block re-reads its weight slice; every activation is read
+// once per tap and per 32-channel output slice): the dispatcher's traffic model.
+long rdp_conv_rowband_bytes(int N, int H, int W, int Cin, int Cout, int pool);
+// C1 / C2: the two sources' channels (C2 = 0 for one source). Every shape predicate rdp_conv_rowband_ex
+// applies is checked here too, so a mode this returns is never rejected by the launch (W and Cin / 32
+// powers of two, each source a multiple of 32 channels); the Python executor asks this same function
+// (binding rowband_frag_mode) which layers need a fragment-major weight copy.
+int rdp_conv_rowband_frag_auto(int N, int H, int W, int C1, int C2, int Cout);
+// Eval conv on the row-band kernel into y1; pool (optional, pbytes / ppitch): MaxPool2d(2) of the output where the
+// kernel can fuse it. Returns 1 if it also wrote the pool, 0 if not, < 0 (nothing launched) when the shape does
+// not fit. wfrag 1: w is the fragment-major copy of the OHWI weights instead of OHWI; 2: that copy on the
+// activation-staged kernel (rdp_conv_rowband_frag_auto picks); rdp_conv_rowband = wfrag 0.
+int rdp_conv_rowband(const RdpConv& c, void* pool, long pbytes, int ppitch, hipStream_t s);
+int rdp_conv_rowband_ex(const RdpConv& c, void* pool, long pbytes, int ppitch, int wfrag, hipStream_t s);
+// The chain launch: layer 0 reads x (C0 channels), layer l > 0 reads layer l - 1's output; every layer is
+// an eval conv (BN folded + ReLU) on the same N x H x W map. cnt: >= 1 + nl * N * H ints, err: 1 int.
+// Returns 0, or < 0 (nothing launched) when a layer does not fit the row-band kernel.
+int rdp_conv_rowband_chain(int nl, const void* x, long xbytes, int C0, int xpitch, const void* const* w,
+                           const long* wbytes, const int* ldw, void* const* y, const long* ybytes,
+                           const int* ypitch, const int* cout, const float* const* escale,
+                           const float* const* eshift, int N, int H, int W, int* cnt, int* err, hipStream_t s);
+
+// ---- csrc/conv_wgrad.hip --------------------------------------------------------------------------------------
+void rdp_wgrad_reduce(float* slab, float* out, int splits, int Cout, int ncols_pad, int taps, int cin_pad,
+                      int cin_real, int accumulate, hipStream_t s);
+int rdp_conv_wgrad(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2, int pitch1,
+                   int pitch2, const void* dy, long dybytes, int dypitch, float* slab, long slab_elems, float* out,
+                   int accumulate, int N, int H, int W, int Cout, int taps, int packed, int cin_real, int splits,
+                   int variant, hipStream_t s);
+// ConvTranspose2d(k=2, s=2) weight gradient straight from its output gradient du [N][H2][W2][C] (the
+// window 2h x 2w at (oy, ox)) and its input x [N][h][w][Cin]: out[ci][(sub, c)] (+)= sum_px
+// x[px][ci] du[sub-pixel sub of px][c] -- the generic kernel's role-swapped GEMM (columns = the 4
+// sub-pixels x C, "couts" = Cin) reading du at the sub-pixels instead of an unshuffled copy.
+// Returns the split count, or < 0 if the shape does not fit.
+int rdp_conv_wgrad_upT(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
+                       const void* x, long xbytes, int Cin, int xpitch, int N, int h, int w, float* slab,
+                       long slab_elems, float* out, int accumulate, int splits, hipStream_t s);
+// Returns the number of splits, or < 0 (nothing launched) when the shape does not fit this kernel.
+int rdp_wgrad_first_bn(const void* x, long xbytes, int xpitch, const void* da, long dabytes, int dapitch,
+                       const void* y, long ybytes, int ypitch, const float* coef, const float* coef2, float* slab,
+                       long slab_elems, float* out, int accumulate, int N, int H, int W, int cin_real, int splits,
+                       hipStream_t s);
+// Slab size (elements) for the generic kernel's `splits` pixel splits. The halo / row-ring kernels choose
+// their own split count, capped by the slab they are given: the training step shares one slab of the
+// largest generic size, which caps the deep layers' halo wgrads at 4-15 splits (~120 blocks). That is
+// deliberate: sized for a full wave of halo blocks (rdp_conv_wgrad_halo_slab_elems) the wgrads run ~1.8x
+// faster alone but the step got slower -- bs 64 3,120-3,131 vs 3,160-3,181 img/s, bs 4 1,405-1,409 vs
+// 1,591 (same box, 2 rounds): the side-stream wgrads then take every CU from the main stream's convs.
+long rdp_conv_wgrad_slab_elems(int N, int H, int W, int Cin, int Cout, int taps, int packed, int splits);
+// Slab the halo / row-ring wgrad needs for one resident wave of blocks (its own split choice
+// unconstrained); 0 where the dispatch does not pick those kernels. (conv_microbench.py sizes with it.)
+long rdp_conv_wgrad_halo_slab_elems(int N, int H, int W, int Cin, int Cout);
+
+// ---- csrc/data_kernels.hip ------------------------------------------------------------------------------------
+// exactly one of tgt_f (one-class: fp32 mask value) / tgt_u (K-class: u8 id, 255 outside the frame) is set
+int rdp_batch_augment(const void* x, const void* y, const int* idx, const float* params, int S, int N, int H, int W,
+                      void* x_out, float* tgt_f, void* tgt_u, hipStream_t s);
+int rdp_area_maxtap();
+int rdp_resize_area_u8(const void* in, int h, int w, int C, const int* ys, const int* yn, const double* yw,
+                       const int* xs, const int* xn, const double* xw, int H, int W, int swap_rb, void* out,
+                       hipStream_t s);
+
+// ---- csrc/geo_spline.hip --------------------------------------------------------------------------------------
+int rdp_geo_spline_res_len(int nsamp);
+// rdp_geo_spline (presorted, serving) for n <= 4 frames in one launch: per-frame arrays of its buffers
+int rdp_geo_spline_batch(int n, int nbins, int kcap, const int* const* kout, const int* const* npts,
+                         double* const* sorted, double* const* u, int ecap, double s, int k, int nsamp, double eps,
+                         int min_points, int min_edge, const int* const* cov, int ncov, double* const* res,
+                         const void* const* mask, void* const* mask_host, long mask_bytes, hipStream_t st);
+// sort the per-bin edge points (out [nbins][kcap][4], kout) into sorted [ecap][3] and fit/evaluate.
+int rdp_geo_spline(const double* out, int nbins, int kcap, const int* kout, const int* npts, double* sorted,
+                   int* gperm, double* u, int ecap, double s, int k, int nsamp, double eps, int min_points,
+                   int min_edge, const int* cov, int ncov, double* res, double* dbg, int presorted,
+                   const void* mask, void* mask_host, long mask_bytes, hipStream_t st);
+
+// ---- csrc/geometry.hip ----------------------------------------------------------------------------------------
+int rdp_geo_nblocks(int H);
+// int32 workspace needed beyond the per-row-block counts: bin_of + bidx [cap] each + 2 x 128
+long rdp_geo_work_ints(int H, int W);
+// work_i: [nblk] counts | [cap] bin_of | [cap] bidx | [128] cnt | [128] cursor ; work_d: xmin/xmax
+// pts [cap][4]; out [nbins][kcap][4]
+// m256 != nullptr (serving form): `mask` is an OUTPUT, derived from the mh x mw model mask by
+// nearest upsampling, and cov[nblk] receives per-row-block coverage counts. edges == nullptr: no
+// packed edge list (the on-device spline reads the per-bin slabs directly). sorted != nullptr: the
+// x-sorted edge points [secap][3] are written too (gperm: 2*secap ints of sort scratch), so the
+// spline stage runs with presorted = 1.
+int rdp_geo_edges(const void* mask, const void* depth, int H, int W, double fx, double fy, double cx, double cy,
+                  double scale, int* counts, double* xmin, double* xmax, double* pts, int cap, int* npts,
+                  double* out, int kcap, int* kout, int nbins, double top, int min_points, double* edges, int ecap,
+                  int* hdr, const void* m256, int mh, int mw, int* cov, double* sorted, int* gperm, int secap,
+                  void* mask_host, hipStream_t s);
+// The serving form of rdp_geo_edges for n <= GEO_BATCH frames of one camera in ONE launch per stage
+// (blockIdx.y = frame): each frame's buffers as rdp_geo_edges takes them (array of n per field). The
+// stages are latency-bound small grids, so n frames cost about what one does (a batch of 4 served frames:
+// 4 x 48 us of geometry as per-frame launches, profiles/serve_batch.md).
+int rdp_geo_edges_batch(int n, const void* const* mask, const void* const* depth, int H, int W, double fx,
+                        double fy, double cx, double cy, double scale, int* const* counts, double* const* xmin,
+                        double* const* xmax, double* const* pts, int cap, int* const* npts, double* const* out,
+                        int kcap, int* const* kout, int nbins, double top, int min_points, const void* const* m256,
+                        int mh, int mw, int* const* cov, double* const* sorted, int* const* gperm, int secap,
+                        void* const* mask_host, hipStream_t s);
+
+// ---- csrc/head_loss.hip ---------------------------------------------------------------------------------------
+int rdp_head_partial_blocks(long M);
+// coef != nullptr: `a` is the last conv's pre-BN output; BN+ReLU are applied on the fly.
+// gpart/bnpart != nullptr (needs coef, dice_w == 0): also the backward partials (head_fwd_kernel GRAD).
+int rdp_head_fwd(const void* a, int apitch, const float* w, const float* b, const float* target, float* logits,
+                 float* partial, float* sums, float* loss, int M, float dice_w, float dice_eps, const float* coef,
+                 float* gpart, float* bnpart, float gscale, hipStream_t s);
+// head weight / bias gradient from the [nb][65] partials of a GRAD forward
+int rdp_head_grad_finalize(const float* gpart, int M, float* gw, float* gb, hipStream_t s);
+// coef != nullptr: BN-fused variant (da unused; bnpart receives the BN backward partial rows).
+// Returns the number of partial rows.
+int rdp_head_bwd(const void* a, int apitch, const float* w, const float* logits, const float* target,
+                 const float* sums, void* da, int dapitch, float* partial, float* gw, float* gb, int M,
+                 float dice_w, float dice_eps, float gscale, const float* coef, float* bnpart, hipStream_t s);
+int rdp_head_bn_bwd_apply(const void* y, int ypitch, const float* w, const float* logits, const float* target,
+                          const float* sums, const float* coef, const float* coef2, void* dy, int dypitch, int M,
+                          float dice_w, float dice_eps, float gscale, hipStream_t s);
+int rdp_head_mask(const void* a, int apitch, const float* w, const float* b, float logit_thr, void* mask, int M,
+                  hipStream_t s);
+
+// ---- csrc/head_multi.hip --------------------------------------------------------------------------------------
+int rdp_headk_partial_blocks(long M);
+// partial: >= blocks * 2 floats. Returns the number of partial rows, < 0 if nothing was launched.
+int rdp_headk_fwd(const void* a, int apitch, const float* w, const float* b, const void* labels, float* logits,
+                  float* partial, float* sums, float* loss, int M, int K, hipStream_t s);
+// partial: >= blocks * (K * 64 + K) floats; gw [K][64], gb [K]
+int rdp_headk_bwd(const void* a, int apitch, const float* w, const float* logits, const void* labels,
+                  const float* sums, void* da, int dapitch, float* partial, float* gw, float* gb, int M, int K,
+                  float gscale, hipStream_t s);
+int rdp_headk_mask(const void* a, int apitch, const float* w, const float* b, int cls, void* mask, int M, int K,
+                   hipStream_t s);
+
+// ---- csrc/jpeg_entropy.hip ------------------------------------------------------------------------------------
+// scan: cap_bytes (a multiple of 4) of de-stuffed scan, of which *nbits (device) are the frame's; tables:
+// rdp_jpeg_scan's block; geo: rdp_jpeg_meta's int32[32]; coefs: cap_coefs int16 (16-byte aligned);
+// work: rdp_jpeg_entropy_work_words(cap_bytes, S) int32; status: one device-visible int32 (0 ok, 1
+// corrupt). S: bits per subsequence, a multiple of 32, >= 64, 0 = the tuned default. After the launches
+// work[stats_word] holds (subsequences, rounds); *stats_word (optional) receives that offset.
+int rdp_jpeg_entropy_gpu(const void* scan, long cap_bytes, const int* nbits, const void* tables, const int* geo,
+                         void* coefs, long cap_coefs, int* work, long work_words, int* status, int S,
+                         long* stats_word, hipStream_t st);
+
+// ---- csrc/norm_act.hip ----------------------------------------------------------------------------------------
+int rdp_bn_finalize(const float* stats, int T, int C, long count, const float* gamma, const float* beta,
+                    float* rmean, float* rvar, long long* nbt, float momentum, float eps, float* coef, float* ws,
+                    hipStream_t s);
+int rdp_rows_fold(const float* buf, int T, int K, double* out, hipStream_t s);
+int rdp_rows_hilo(const double* in, float* buf, int K, hipStream_t s);
+int rdp_bn_eval_coef(int C, const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps,
+                     float* coef, hipStream_t s);
+int rdp_bn_relu_apply(const void* y, int ypitch, void* out, int opitch, const float* coef, int M, int C, int relu,
+                      hipStream_t s);
+// returns the number of partial rows written (T for bn_bwd_finalize)
+int rdp_bn_relu_bwd_reduce(const void* da, int dapitch, const void* y, int ypitch, const float* coef, int M, int C,
+                           int relu, float* partial, int max_blocks, hipStream_t s);
+int rdp_bn_bwd_finalize(const float* partial, int T, int C, long count, const float* gamma, const float* coef,
+                        float* dgamma, float* dbeta, float* coef2, float* ws, hipStream_t s);
+int rdp_bn_relu_bwd_apply(const void* da, int dapitch, const void* y, int ypitch, const float* coef,
+                          const float* coef2, void* dy, int dypitch, int M, int C, int relu, hipStream_t s);
+
+// ---- csrc/optim.hip -------------------------------------------------------------------------------------------
+// inc = 0: the caller advances the step counter later on this stream (rdp_wprep with step)
+// g_bf16: g is bf16 (u16) instead of fp32
+// max_blocks > 0 caps the grid (grid-stride loop): the overlapped update on the side stream leaves CUs to
+// the next forward's first layers
+int rdp_adam(float* p, const void* g, int g_bf16, float* m, float* v, void* shadow, long n, float lr, float b1,
+             float b2, float eps, float wd, float gscale, int* step, int inc, int max_blocks, hipStream_t s);
+int rdp_cast_bf16(const float* p, void* out, long n, hipStream_t s);
+// segs: device array of nseg WSeg {long src, long dst, int kind, cout, cin, taps, tile0, pad} (40 bytes
+// each; tile0 = the running sum of wseg_tiles over the earlier segments); tiles = the table's total tile
+// count (the caller's sum), blocks = grid cap (0: one block per tile, at most 4096)
+int rdp_wprep(const float* master, void* out, const void* segs, int nseg, int* step, int tiles, int blocks,
+              hipStream_t s);
+int rdp_wseg_size();
+
+// ---- csrc/pool_up.hip -----------------------------------------------------------------------------------------
+int rdp_maxpool2_fwd(const void* x, int xpitch, void* out, int opitch, int N, int H, int W, int C, hipStream_t s);
+int rdp_maxpool2_bwd(const void* dp, int dppitch, const void* x, int xpitch, const void* dskip, int dspitch,
+                     void* dx, int dxpitch, int N, int H, int W, int C, hipStream_t s);
+int rdp_bn_relu_apply_pool(const void* y, int ypitch, void* a, int apitch, void* pool, int ppitch,
+                           const float* coef, int N, int H, int W, int C, hipStream_t s);
+// returns the number of partial rows written (T for bn_bwd_finalize), -1 if not applicable
+// x: the stored activation (pitch check only: the argmax is recomputed from y)
+int rdp_maxpool2_bwd_bn_reduce(const void* dp, int dppitch, const void* x, int xpitch, const void* dskip,
+                               int dspitch, void* dx, int dxpitch, const void* y, int ypitch, const float* coef,
+                               int N, int H, int W, int C, float* partial, int max_blocks, hipStream_t s);
+int rdp_upsample2_fwd(const void* x, int xpitch, void* out, int opitch, int N, int hin, int win, int Hout, int Wout,
+                      int oy, int ox, int C, const float* coef, hipStream_t s);
+// y/coef/partial given: fused BN-backward reduction of dx's consumer BN; returns the partial rows
+// written (<= max_blocks). Otherwise returns 0.
+int rdp_upsample2_bwd(const void* dout, int dpitch, void* dx, int xpitch, int N, int hin, int win, int Hout,
+                      int Wout, int oy, int ox, int C, const void* y, int ypitch, const float* coef, float* partial,
+                      int max_blocks, hipStream_t s);
+int rdp_upT_shuffle(const void* yT, int ypitch, const float* bias, void* u, int upitch, int N, int h, int w, int H2,
+                    int W2, int oy, int ox, int C, hipStream_t s);
+int rdp_upT_unshuffle(const void* du, int dpitch, void* dyT, int ypitch, int N, int h, int w, int H2, int W2,
+                      int oy, int ox, int C, hipStream_t s);
+// partial must hold >= 1024 * K + 2 * FOLD_RB * K / groups floats
+int rdp_colsum_bf16(const void* x, int pitch, long M, int K, int groups, float* partial, float* out, int accumulate,
+                    hipStream_t s);
+
+// ---- csrc/seg_metrics.hip -------------------------------------------------------------------------------------
+// pixels of one block and pass: M above blocks * this takes more than one pass of the grid-stride loop
+int rdp_seg_confusion_block_pixels();
+// blocks of one launch over M pixels
+int rdp_seg_confusion_blocks(long M);
+// counts: int64 [KC * KC + 1], added to. max_blocks > 0 caps the grid (a test hook: a small M then
+// takes several passes of the grid-stride loop). Returns the blocks launched, < 0 if nothing was.
+int rdp_seg_confusion(const float* logits, const void* target, void* counts, long M, int K, float thr,
+                      int max_blocks, hipStream_t s);
+
+// ---- csrc/serve_kernels.hip -----------------------------------------------------------------------------------
+int rdp_preprocess(const void* bgr, int H, int W, const int* ystart, const int* ysize, const float* yw,
+                   const int* xstart, const int* xsize, const float* xw, int OH, int OW, int rgb, void* out,
+                   hipStream_t s);
+int rdp_preprocess_batch(int n, const void* const* bgr, int H, int W, const int* ystart, const int* ysize,
+                         const float* yw, const int* xstart, const int* xsize, const float* xw, int OH, int OW,
+                         int rgb, void* const* out, hipStream_t s);
+int rdp_mask_upsample(const void* m, int mh, int mw, void* out, int H, int W, unsigned* count, hipStream_t s);
+// the JPEG pixel stage of n <= 4 frames (each its coefficient / meta / planes / RGB buffers) in 2 launches
+int rdp_jpeg_gpu_batch(int n, const void* const* coefs, const int* const* geo, const int* const* qt,
+                       void* const* planes, int H, int W, int max_blocks, void* const* rgb, hipStream_t s);
+// coefficient / plane capacity for frames of H x W (any supported sampling: Y and chroma planes at most
+// MCU-padded to 16 x 16)
+long rdp_jpeg_max_coefs(int H, int W);
+long rdp_jpeg_plane_bytes(int H, int W);
+int rdp_jpeg_gpu(const void* coefs, const int* geo, const int* qt, void* planes, int H, int W, int max_blocks,
+                 void* rgb, hipStream_t s);
+int rdp_h2d_copy(const void* src, void* dst, long bytes, hipStream_t s);
+// n <= 16 segments, every src / dst 16-byte aligned (returns -1, nothing launched, otherwise)
+int rdp_h2d_copy_multi(const void* const* src, void* const* dst, const long* bytes, int n, hipStream_t s);
+
+}  // extern "C"

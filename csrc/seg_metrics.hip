@@ -24,6 +24,7 @@
 // every non-zero bin takes ONE 64-bit integer atomicAdd: the grid is small because these same-address
 // global atomics, not the loads, bounded the pass at 2048 blocks of 256 threads (3 x slower).
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 
 #define SEG_WAVES 16   // waves per block
@@ -121,16 +122,12 @@ void launch_confusion(int nb, hipStream_t s, const float* logits, const void* ta
 }  // namespace
 
 extern "C" {
-// pixels of one block and pass: M above blocks * this takes more than one pass of the grid-stride loop
 int rdp_seg_confusion_block_pixels() { return SEG_BLOCK_PX; }
 
-// blocks of one launch over M pixels
 int rdp_seg_confusion_blocks(long M) {
   return (int)std::max<long>(1, std::min<long>((M + SEG_BLOCK_PX - 1) / SEG_BLOCK_PX, SEG_MAX_BLOCKS));
 }
 
-// counts: int64 [KC * KC + 1], added to. max_blocks > 0 caps the grid (a test hook: a small M then
-// takes several passes of the grid-stride loop). Returns the blocks launched, < 0 if nothing was.
 int rdp_seg_confusion(const float* logits, const void* target, void* counts, long M, int K, float thr, int max_blocks,
                       hipStream_t s) {
   if (M <= 0) return -1;

@@ -9,6 +9,7 @@
 // mask_upsample: replaces (sigmoid(logits) > 0.5) -> cv2.resize(INTER_NEAREST) -> count_nonzero
 //   (server.py:124-125,133): u8 {0,1} mask at the camera resolution + coverage count (atomics).
 #include "common.h"
+#include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
 
@@ -306,7 +307,6 @@ __global__ __launch_bounds__(256) void jpeg_color_batch_kernel(const JpegFrames 
 }
 
 extern "C" {
-// the JPEG pixel stage of n <= 4 frames (each its coefficient / meta / planes / RGB buffers) in 2 launches
 int rdp_jpeg_gpu_batch(int n, const void* const* coefs, const int* const* geo, const int* const* qt,
                        void* const* planes, int H, int W, int max_blocks, void* const* rgb, hipStream_t s) {
   if (n < 1 || n > 4) return -1;
@@ -324,8 +324,6 @@ int rdp_jpeg_gpu_batch(int n, const void* const* coefs, const int* const* geo, c
   return 0;
 }
 
-// coefficient / plane capacity for frames of H x W (any supported sampling: Y and chroma planes at most
-// MCU-padded to 16 x 16)
 long rdp_jpeg_max_coefs(int H, int W) { return 3L * ((W + 15) / 16 * 16) * ((H + 15) / 16 * 16); }
 long rdp_jpeg_plane_bytes(int H, int W) { return rdp_jpeg_max_coefs(H, W); }
 
@@ -418,7 +416,6 @@ __global__ __launch_bounds__(256) void h2d_copy_multi_kernel(CopySegs g) {
   if (i < 16 && t < bytes) g.dst[sg][t] = g.src[sg][t];
 }
 
-// n <= 16 segments, every src / dst 16-byte aligned (returns -1, nothing launched, otherwise)
 extern "C" int rdp_h2d_copy_multi(const void* const* src, void* const* dst, const long* bytes, int n, hipStream_t s) {
   if (n <= 0) return 0;
   if (n > 16) return -1;

@@ -30,21 +30,10 @@
 #include <vector>
 
 #include "host_pool.h"
+#include "rdp_api.h"
 #include "wire_parse.h"
 
 namespace py = pybind11;
-
-extern "C" int rdp_h2d_copy(const void*, void*, long, hipStream_t);
-extern "C" int rdp_h2d_copy_multi(const void* const*, void* const*, const long*, int, hipStream_t);
-extern "C" long rdp_png_encode_gray(const uint8_t*, int, int, int, int, int, uint8_t*, long);
-extern "C" long rdp_png_encode_bound(int, int, int, int);
-extern "C" long rdp_jpeg_info(const uint8_t*, long, int*);
-extern "C" void rdp_jpeg_meta(const int*, int*);
-extern "C" int rdp_jpeg_decode(const uint8_t*, long, int16_t*, long, uint16_t*, int);
-extern "C" int rdp_jpeg_scan(const uint8_t*, long, int*, uint8_t*, uint8_t*, long, int*);
-extern "C" long rdp_jpeg_tables_bytes();
-extern "C" int rdp_png_info(const uint8_t*, long, int*, int*, int*);
-extern "C" int rdp_png_decode(const uint8_t*, long, uint8_t*, long, int);
 
 namespace {
 

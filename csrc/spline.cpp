@@ -20,6 +20,8 @@
 #include <cstring>
 #include <vector>
 
+#include "rdp_host_api.h"
+
 namespace {
 
 struct Banded {  // n x w row-major (1-based access)
@@ -171,9 +173,6 @@ void fpknot(const double* x, double* t, int& n, double* fpint, int* nrdata, int&
 
 extern "C" {
 
-// FITPACK fppara for iopt = 0, unit weights, ub = u[0], ue = u[m-1].
-//   x: m points x idim (point-major); t: >= nest knots; c: >= nest*idim coefficients (dim-major,
-//   stride nest). Returns ier (-2 polynomial, 0 ok, 1..3 FITPACK warnings, 10 invalid input).
 int rdp_parcur(int idim, int m, const double* u_in, const double* x_in, double s, int k, int nest, double* t_out,
                double* c_out, int* n_out, double* fp_out) {
   if (k < 1 || k > 5 || m <= k || s < 0.0 || idim < 1 || idim > 10 || nest < 2 * (k + 1)) return 10;
@@ -381,8 +380,6 @@ int rdp_parcur(int idim, int m, const double* u_in, const double* x_in, double s
   return ier;
 }
 
-// value / derivatives (der <= k) of a B-spline (t: n knots, c: n-k-1 coefficients) at x,
-// extrapolating outside [t_k, t_{n-k-1}] like FITPACK splev(ext=0).
 double rdp_splev1(const double* t, int n, const double* c, int k, double x, int der) {
   // derivative coefficients by repeated differencing (FITPACK splder)
   std::vector<double> cd(c, c + (n - k - 1));
@@ -414,9 +411,6 @@ double rdp_splev1(const double* t, int n, const double* c, int k, double x, int 
   return s;
 }
 
-// Full post-edge pipeline: chord-length u, parcur(s, k), 100-sample curvature + points.
-//   pts: m x 3 (sorted by x); out_pts: nsamp x 3; out: [mean_k, max_k, fp, n]; returns ier
-//   (-2/0/1/2/3 like FITPACK, 10 = invalid input -> caller returns the empty result).
 int rdp_fit_curvature(const double* pts, int m, double s, int k, int nsamp, double eps, double* out_pts,
                       double* out) {
   if (m <= k) return 10;

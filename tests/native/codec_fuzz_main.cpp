@@ -23,14 +23,8 @@
 #include <thread>
 #include <vector>
 
+#include "../../csrc/rdp_host_api.h"
 #include "../../csrc/wire_parse.h"
-
-extern "C" {
-long rdp_jpeg_info(const uint8_t* d, long n, int* info);
-int rdp_jpeg_decode(const uint8_t* d, long n, int16_t* coefs, long ncoefs, uint16_t* qt, int parallel);
-int rdp_png_info(const uint8_t* d, long n, int* w, int* h, int* bd);
-int rdp_png_decode(const uint8_t* d, long n, uint8_t* out, long out_bytes, int parallel);
-}
 
 namespace {
 

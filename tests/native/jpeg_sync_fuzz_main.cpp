@@ -19,15 +19,7 @@
 #include <cstring>
 #include <vector>
 
-extern "C" {
-long rdp_jpeg_info(const uint8_t* d, long n, int* info);
-int rdp_jpeg_decode(const uint8_t* d, long n, int16_t* coefs, long ncoefs, uint16_t* qt, int parallel);
-long rdp_jpeg_tables_bytes();
-long rdp_jpeg_scan_bound(const uint8_t* d, long n);
-int rdp_jpeg_scan(const uint8_t* d, long n, int* meta, uint8_t* tables, uint8_t* scan, long cap, int* nbits);
-int rdp_jpeg_entropy_emulate(const uint8_t* scan, long cap_bytes, int nbits, const uint8_t* tables, const int* geo,
-                             int16_t* coefs, long cap_coefs, int S, int* status, int* stats);
-}
+#include "../../csrc/rdp_host_api.h"
 
 namespace {
 

@@ -7,11 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
-extern "C" int rdp_parcur(int idim, int m, const double* u, const double* x, double s, int k, int nest, double* t,
-                          double* c, int* n, double* fp);
-extern "C" double rdp_splev1(const double* t, int n, const double* c, int k, double x, int der);
-extern "C" int rdp_fit_curvature(const double* pts, int m, double s, int k, int nsamp, double eps, double* out_pts,
-                                 double* out);
+#include "../../csrc/rdp_host_api.h"
 
 static unsigned long long g_state = 0x9e3779b97f4a7c15ull;
 static double urand() {  // xorshift64*, deterministic
