@@ -14,6 +14,7 @@
 #include <dlfcn.h>
 #include <link.h>
 #include <chrono>
+#include <cmath>
 #include <climits>
 #include <cstdlib>
 #include <cstring>
@@ -1203,10 +1204,32 @@ void check_u8(const torch::Tensor& t, long numel, const char* name) {
               ": must be a contiguous u8 GPU tensor of ", numel, " elements");
 }
 
+// The optional extended mode of the K-class head: class weights (fp32 [K] on the device; their VALUES are the
+// caller's to validate, nothing here syncs) and / or a soft Dice term. Returns the weights' pointer (null: none);
+// `ext` = the call runs the extended kernels, which need 2 + 3K floats of `sums`.
+const float* headk_ext_args(const c10::optional<torch::Tensor>& class_weights, double dice_w, double dice_eps, int K,
+                            const torch::Tensor& sums, const char* who, bool& ext) {
+  TORCH_CHECK(dice_w >= 0.0 && std::isfinite(dice_w), who, ": dice_w must be finite and >= 0, got ", dice_w);
+  TORCH_CHECK(dice_eps > 0.0 && std::isfinite(dice_eps), who, ": dice_eps must be finite and > 0, got ", dice_eps);
+  const float* cw = nullptr;
+  if (class_weights) {
+    const torch::Tensor& t = *class_weights;
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.numel() == K, who,
+                ": class_weights must be a contiguous fp32 GPU tensor of ", K, " elements");
+    cw = t.data_ptr<float>();
+  }
+  ext = cw != nullptr || (float)dice_w != 0.f;
+  TORCH_CHECK(!ext || sums.numel() >= 2 + 3 * K, who, ": class weights / Dice need 2 + 3K = ", 2 + 3 * K,
+              " floats of sums, got ", sums.numel());
+  return cw;
+}
+
 // logits [M][K] fp32, softmax cross-entropy over the labels < K (u8; 255 and every label >= K ignored):
-// loss[0] = loss[1] = mean over the kept pixels, sums[0..1] = {sum ce, kept pixels}
+// loss[0] = loss[1] = mean over the kept pixels, sums[0..1] = {sum ce, kept pixels}. With class_weights and / or
+// dice_w > 0: loss[0] = CE + dice_w * Dice, loss[1] = the weighted CE, sums[0 .. 2+3K) = {sum w*ce, W, I_k, P_k, T_k}
 void headk_fwd(torch::Tensor a, torch::Tensor w, torch::Tensor b, torch::Tensor labels, torch::Tensor logits,
-               torch::Tensor partial, torch::Tensor sums, torch::Tensor loss) {
+               torch::Tensor partial, torch::Tensor sums, torch::Tensor loss,
+               c10::optional<torch::Tensor> class_weights, double dice_w, double dice_eps) {
   Act x = act(a, "a");
   const int K = headk_classes(w, b, "headk_fwd");
   TORCH_CHECK(x.C == 64, "head expects 64 channels");
@@ -1217,17 +1240,23 @@ void headk_fwd(torch::Tensor a, torch::Tensor w, torch::Tensor b, torch::Tensor 
   check_f32(partial, "partial");
   check_f32(sums, "sums");
   check_f32(loss, "loss");
+  bool ext = false;
+  const float* cw = headk_ext_args(class_weights, dice_w, dice_eps, K, sums, "headk_fwd", ext);
   TORCH_CHECK(logits.numel() == M * K, "headk_fwd: logits must hold M * K values");
-  TORCH_CHECK(partial.numel() >= (long)rdp_headk_partial_blocks(M) * 2, "headk_fwd: partial too small");
+  TORCH_CHECK(partial.numel() >= (long)rdp_headk_partial_blocks(M) * (ext ? 2 + 3 * K : 2),
+              "headk_fwd: partial too small");
   TORCH_CHECK(sums.numel() >= 2 && loss.numel() >= 2, "headk_fwd: sums / loss need 2 values");
   TORCH_CHECK(RDP_PLAN(rdp_headk_fwd(x.ptr, x.pitch, w.data_ptr<float>(), b.data_ptr<float>(), labels.data_ptr(),
                                      logits.data_ptr<float>(), partial.data_ptr<float>(), sums.data_ptr<float>(),
-                                     loss.data_ptr<float>(), (int)M, K, st)) > 0, "headk_fwd");
+                                     loss.data_ptr<float>(), (int)M, K, cw, (float)dice_w, (float)dice_eps, st)) > 0,
+              "headk_fwd");
 }
 
-// da = d loss / d a (bf16), gw [K][64] / gb [K] = the head's gradients; partial: >= blocks * (K * 65) floats
+// da = d loss / d a (bf16), gw [K][64] / gb [K] = the head's gradients; partial: >= blocks * (K * 65) floats.
+// class_weights / dice_w / dice_eps: as given to headk_fwd, whose `sums` this reads.
 void headk_bwd(torch::Tensor a, torch::Tensor w, torch::Tensor logits, torch::Tensor labels, torch::Tensor sums,
-               torch::Tensor da, torch::Tensor partial, torch::Tensor gw, torch::Tensor gb, double gscale) {
+               torch::Tensor da, torch::Tensor partial, torch::Tensor gw, torch::Tensor gb, double gscale,
+               c10::optional<torch::Tensor> class_weights, double dice_w, double dice_eps) {
   Act x = act(a, "a"), d = act(da, "da");
   const int K = headk_classes(w, gb, "headk_bwd");
   const long M = (long)x.N * x.H * x.W;
@@ -1238,11 +1267,14 @@ void headk_bwd(torch::Tensor a, torch::Tensor w, torch::Tensor logits, torch::Te
   check_f32(partial, "partial");
   check_f32(sums, "sums");
   check_f32(gw, "gw");
+  bool ext = false;
+  const float* cw = headk_ext_args(class_weights, dice_w, dice_eps, K, sums, "headk_bwd", ext);
   TORCH_CHECK(logits.numel() == M * K && sums.numel() >= 2 && gw.numel() == K * 64, "headk_bwd: logits / sums / gw sizes");
   TORCH_CHECK(partial.numel() >= (long)rdp_headk_partial_blocks(M) * (K * 65), "headk_bwd: partial too small");
   TORCH_CHECK(RDP_PLAN(rdp_headk_bwd(x.ptr, x.pitch, w.data_ptr<float>(), logits.data_ptr<float>(), labels.data_ptr(),
                                      sums.data_ptr<float>(), d.ptr, d.pitch, partial.data_ptr<float>(),
-                                     gw.data_ptr<float>(), gb.data_ptr<float>(), (int)M, K, (float)gscale, st)) > 0,
+                                     gw.data_ptr<float>(), gb.data_ptr<float>(), (int)M, K, (float)gscale, cw,
+                                     (float)dice_w, (float)dice_eps, st)) > 0,
               "headk_bwd");
 }
 
@@ -1972,9 +2004,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("head_mask", on_device(&head_mask));
   m.def("headk_partial_blocks", &headk_partial_blocks);
   m.def("headk_fwd", on_device(&headk_fwd), py::arg("a"), py::arg("w"), py::arg("b"), py::arg("labels"),
-        py::arg("logits"), py::arg("partial"), py::arg("sums"), py::arg("loss"));
+        py::arg("logits"), py::arg("partial"), py::arg("sums"), py::arg("loss"), py::arg("class_weights") = py::none(),
+        py::arg("dice_w") = 0.0, py::arg("dice_eps") = 1.0);
   m.def("headk_bwd", on_device(&headk_bwd), py::arg("a"), py::arg("w"), py::arg("logits"), py::arg("labels"),
-        py::arg("sums"), py::arg("da"), py::arg("partial"), py::arg("gw"), py::arg("gb"), py::arg("gscale") = 1.0);
+        py::arg("sums"), py::arg("da"), py::arg("partial"), py::arg("gw"), py::arg("gb"), py::arg("gscale") = 1.0,
+        py::arg("class_weights") = py::none(), py::arg("dice_w") = 0.0, py::arg("dice_eps") = 1.0);
   m.def("headk_mask", on_device(&headk_mask), py::arg("a"), py::arg("w"), py::arg("b"), py::arg("cls"),
         py::arg("mask"));
   m.def("seg_confusion_blocks", &seg_confusion_blocks);

@@ -15,6 +15,19 @@
 //   views in the parameter's [K][64] order.
 // headk_mask: mask[p] = argmax_k(a[p].w[k] + b[k]) == cls, ties to the lowest index.
 //
+// Extended mode (EXT; class weights cw[k] >= 0 and / or a soft Dice term of weight dice_w; the plain
+// kernels above are the EXT = false instantiations and are not touched by it). s = softmax(x):
+//   W = sum_kept cw[t], CE = sum_kept cw[t] * ce / W (0 if W == 0; F.cross_entropy(weight=cw)),
+//   I_k = sum_kept s_k [t == k], P_k = sum_kept s_k, T_k = sum_kept [t == k], D_k = P_k + T_k + eps,
+//   Dice = 1 - (1/K) sum_k (2 I_k + eps) / D_k over the whole batch, loss[0] = CE + dice_w * Dice,
+//   loss[1] = CE. The weights act on CE only.
+// headk_fwd: per-block partial rows of 2 + 3K floats {sum cw*ce, sum cw, I_0.., P_0.., T_0..}; after
+//   the max / sum-exp shuffles lane `sub < K` owns s_k, so I / P / T accumulate in the owning lane.
+//   headk_loss_finalize_ext: sums[0 .. 2+3K) = {sum cw*ce, W, I_k, P_k, T_k} (fp64 sums).
+// headk_bwd: dlogit[j] = cw[t] (s_j - [j == t]) / W + s_j (G_j - sum_k G_k s_k) with
+//   G_k = B_k + [t == k] A_k, A_k = -2 dice_w / (K D_k), B_k = dice_w (2 I_k + eps) / (K D_k^2),
+//   formed once per thread from `sums`; the rest is the plain backward.
+//
 // Memory pattern of head_loss.hip: 8 lanes per pixel, one 16-B load of 8 bf16 channels per lane,
 // HPX pixels in flight per lane group, grid capped at 2048 blocks, per-block partial rows and a
 // one-launch finalize. No float atomics: results are bitwise repeatable.
@@ -80,14 +93,16 @@ RDP_DEV float lane_logit(const float* f, const float (&wl)[K][8], int sub) {
   return reduce_transpose<KP>(d, sub);
 }
 
-template <int K>
+// EXT: `cw` = class weights (null: all 1); partial rows of 2 + 3K floats instead of 2
+template <int K, bool EXT>
 __global__ __launch_bounds__(256) void headk_fwd_kernel(const u16* __restrict__ a, int apitch,
                                                         const float* __restrict__ w, const float* __restrict__ b,
                                                         const uint8_t* __restrict__ labels,
                                                         float* __restrict__ logits, float* __restrict__ partial,
-                                                        int M) {
+                                                        int M, const float* __restrict__ cw) {
   constexpr int KP = pow2_classes(K);
-  __shared__ float red[4][2];
+  constexpr int PROW = EXT ? 2 + 3 * K : 2;
+  __shared__ float red[4][PROW];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int sub = lane & 7;
   const int kk = sub & (KP - 1);  // the logit this lane ends up owning
@@ -99,6 +114,11 @@ __global__ __launch_bounds__(256) void headk_fwd_kernel(const u16* __restrict__ 
     for (int j = 0; j < 8; ++j) wl[k][j] = w[k * HEAD_C + sub * 8 + j];
   const float bias = own ? b[kk] : 0.f;
   float sce = 0.f, scnt = 0.f;
+  // EXT: the weight of the class this lane owns; softmax sums of that class over the kept pixels
+  [[maybe_unused]] float wk = 1.f, accI = 0.f, accP = 0.f, accT = 0.f;
+  if constexpr (EXT) {
+    if (cw != nullptr && sub < K) wk = cw[sub];
+  }
   const long stride = (long)gridDim.x * 32;  // 32 pixel groups per block
   for (long p0 = blockIdx.x * 32l + (threadIdx.x >> 3); p0 < M; p0 += stride * HPX) {
     uint4 v[HPX];
@@ -123,13 +143,27 @@ __global__ __launch_bounds__(256) void headk_fwd_kernel(const u16* __restrict__ 
 #pragma unroll
       for (int o = 1; o < KP; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
       float se = own ? __expf(x - mx) : 0.f;
+      [[maybe_unused]] const float ex = se;  // this lane's own exp(x - max)
 #pragma unroll
       for (int o = 1; o < KP; o <<= 1) se += __shfl_xor(se, o, 64);
       if (p < M) {
         if (sub < K) logits[(size_t)p * K + sub] = x;  // sub < K: kk == sub
-        if (lab[u] < K && sub == lab[u]) {  // kept pixel: the lane that owns x[label] finishes it
-          sce += mx + logf(se) - x;
-          scnt += 1.f;
+        if constexpr (EXT) {
+          if (lab[u] < K && sub < K) {  // kept pixel: every class lane adds its softmax value
+            const float sp = ex / se;
+            accP += sp;
+            if (sub == lab[u]) {
+              accI += sp;
+              accT += 1.f;
+              sce += wk * (mx + logf(se) - x);
+              scnt += wk;
+            }
+          }
+        } else {
+          if (lab[u] < K && sub == lab[u]) {  // kept pixel: the lane that owns x[label] finishes it
+            sce += mx + logf(se) - x;
+            scnt += 1.f;
+          }
         }
       }
     }
@@ -137,10 +171,24 @@ __global__ __launch_bounds__(256) void headk_fwd_kernel(const u16* __restrict__ 
   sce = wave_sum(sce);
   scnt = wave_sum(scnt);
   if (lane == 0) { red[wave][0] = sce; red[wave][1] = scnt; }
+  if constexpr (EXT) {
+    // the 8 pixel groups of the wave share `sub`: after three steps lanes 0..7 hold class `lane`'s totals
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1) {
+      accI += __shfl_xor(accI, o, 64);
+      accP += __shfl_xor(accP, o, 64);
+      accT += __shfl_xor(accT, o, 64);
+    }
+    if (lane < K) {
+      red[wave][2 + lane] = accI;
+      red[wave][2 + K + lane] = accP;
+      red[wave][2 + 2 * K + lane] = accT;
+    }
+  }
   __syncthreads();
-  if (threadIdx.x < 2) {
+  if (threadIdx.x < PROW) {
     const int q = threadIdx.x;
-    partial[blockIdx.x * 2 + q] = red[0][q] + red[1][q] + red[2][q] + red[3][q];
+    partial[blockIdx.x * PROW + q] = red[0][q] + red[1][q] + red[2][q] + red[3][q];
   }
 }
 
@@ -168,14 +216,51 @@ __global__ void headk_loss_finalize_kernel(const float* __restrict__ partial, in
   }
 }
 
-template <int K>
+// EXT: sums[0 .. 2+3K) = {sum cw*ce, W, I_k, P_k, T_k} from partial rows of n = 2 + 3K floats, each summed
+// in the order of the plain finalize; loss[0] = CE + dice_w * Dice, loss[1] = CE = sum cw*ce / W (0 if
+// W == 0: W may be below 1 with small weights, so there is no max(W, 1) here)
+__global__ __launch_bounds__(256) void headk_loss_finalize_ext_kernel(const float* __restrict__ partial, int T,
+                                                                      int K, float dice_w, float dice_eps,
+                                                                      float* __restrict__ sums,
+                                                                      float* __restrict__ loss) {
+  constexpr int NMAX = 2 + 3 * 8;
+  __shared__ double red[NMAX][64];
+  __shared__ double tot[NMAX];
+  const int n = 2 + 3 * K;
+  const int wave = threadIdx.x >> 6, l = threadIdx.x & 63;
+  for (int q = wave; q < n; q += 4) {
+    double s = 0.0;
+    for (int t = l; t < T; t += 64) s += (double)partial[t * n + q];
+    red[q][l] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < n) {
+    double v = 0.0;
+    for (int k = 0; k < 64; ++k) v += red[threadIdx.x][k];
+    sums[threadIdx.x] = (float)v;
+    tot[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double ce = tot[1] > 0.0 ? tot[0] / tot[1] : 0.0;
+    double ratio = 0.0;
+    for (int k = 0; k < K; ++k)
+      ratio += (2.0 * tot[2 + k] + (double)dice_eps) / (tot[2 + K + k] + tot[2 + 2 * K + k] + (double)dice_eps);
+    const double dice = 1.0 - ratio / K;
+    loss[0] = (float)(ce + (double)dice_w * dice);
+    loss[1] = (float)ce;
+  }
+}
+
+template <int K, bool EXT>
 __global__ __launch_bounds__(256) void headk_bwd_kernel(const u16* __restrict__ a, int apitch,
                                                         const float* __restrict__ w,
                                                         const float* __restrict__ logits,
                                                         const uint8_t* __restrict__ labels,
                                                         const float* __restrict__ sums, u16* __restrict__ da,
                                                         int dapitch, float* __restrict__ partial, int M,
-                                                        float gscale) {
+                                                        float gscale, const float* __restrict__ cw, float dice_w,
+                                                        float dice_eps) {
   constexpr int ROW = K * HEAD_C + K;
   __shared__ float red[4][ROW];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -193,7 +278,23 @@ __global__ __launch_bounds__(256) void headk_bwd_kernel(const u16* __restrict__ 
   // Everything accumulates the unscaled (softmax - onehot) / count; the loss scale multiplies the
   // finished values (da per pixel before its bf16 rounding, dW / db in the finalize), so it scales
   // the gradients exactly
-  const float invc = 1.f / fmaxf(sums[1], 1.f);
+  float invc;
+  // EXT: cwl[k] = cw[k] / W; the Dice term's per-class constants (all 0 at dice_w == 0)
+  [[maybe_unused]] float cwl[K], dA[K], dB[K];
+  if constexpr (EXT) {
+    const float sw = sums[1];
+    invc = sw > 0.f ? 1.f / sw : 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      cwl[k] = (cw != nullptr ? cw[k] : 1.f) * invc;
+      const float dk = sums[2 + K + k] + sums[2 + 2 * K + k] + dice_eps;
+      const float rk = dice_w / ((float)K * dk);
+      dA[k] = -2.f * rk;
+      dB[k] = rk * (2.f * sums[2 + k] + dice_eps) / dk;
+    }
+  } else {
+    invc = 1.f / fmaxf(sums[1], 1.f);
+  }
   const long stride = (long)gridDim.x * 32;
   for (long p0 = blockIdx.x * 32l + (threadIdx.x >> 3); p0 < M; p0 += stride * HPX) {
     uint4 vq[HPX];
@@ -229,9 +330,25 @@ __global__ __launch_bounds__(256) void headk_bwd_kernel(const u16* __restrict__ 
         const float inv = 1.f / se;
         float f[8];
         unpack8h(vq[u], f);
+        [[maybe_unused]] float wt = 0.f, dot = 0.f, G[K];
+        if constexpr (EXT) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            if (k == lab[u]) wt = cwl[k];
+            G[k] = dB[k] + (k == lab[u] ? dA[k] : 0.f);
+            dot = fmaf(G[k], e[k] * inv, dot);
+          }
+        }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-          const float dl = (e[k] * inv - (k == lab[u] ? 1.f : 0.f)) * invc;
+          float dl;
+          if constexpr (EXT) {
+            // the CE part rounds as the plain kernel's contracted e * inv - onehot does: with unit weights and
+            // dice_w == 0 (G = dot = 0) the two modes agree bitwise
+            dl = fmaf(e[k], inv, k == lab[u] ? -1.f : 0.f) * wt + (e[k] * inv) * (G[k] - dot);
+          } else {
+            dl = (e[k] * inv - (k == lab[u] ? 1.f : 0.f)) * invc;
+          }
           gb[k] += dl;
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
@@ -333,18 +450,31 @@ __global__ __launch_bounds__(256) void headk_mask_kernel(const u16* __restrict__
 
 int blocks_for(long M) { return (int)std::max<long>(1, std::min<long>((M + 31) / 32, 2048)); }
 
+// extended mode: class weights given, or a Dice term; otherwise the plain kernels, launched as ever
+bool headk_ext(const float* cw, float dice_w) { return cw != nullptr || dice_w != 0.f; }
+
 template <int K>
 void launch_fwd(int nb, hipStream_t s, const void* a, int apitch, const float* w, const float* b, const void* labels,
-                float* logits, float* partial, int M) {
-  hipLaunchKernelGGL(headk_fwd_kernel<K>, dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, b,
-                     (const uint8_t*)labels, logits, partial, M);
+                float* logits, float* partial, int M, bool ext, const float* cw) {
+  if (ext)
+    hipLaunchKernelGGL((headk_fwd_kernel<K, true>), dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, b,
+                       (const uint8_t*)labels, logits, partial, M, cw);
+  else
+    hipLaunchKernelGGL((headk_fwd_kernel<K, false>), dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, b,
+                       (const uint8_t*)labels, logits, partial, M, (const float*)nullptr);
 }
 
 template <int K>
 void launch_bwd(int nb, hipStream_t s, const void* a, int apitch, const float* w, const float* logits,
-                const void* labels, const float* sums, void* da, int dapitch, float* partial, int M, float gscale) {
-  hipLaunchKernelGGL(headk_bwd_kernel<K>, dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, logits,
-                     (const uint8_t*)labels, sums, (u16*)da, dapitch, partial, M, gscale);
+                const void* labels, const float* sums, void* da, int dapitch, float* partial, int M, float gscale,
+                bool ext, const float* cw, float dice_w, float dice_eps) {
+  if (ext)
+    hipLaunchKernelGGL((headk_bwd_kernel<K, true>), dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, logits,
+                       (const uint8_t*)labels, sums, (u16*)da, dapitch, partial, M, gscale, cw, dice_w, dice_eps);
+  else
+    hipLaunchKernelGGL((headk_bwd_kernel<K, false>), dim3(nb), dim3(256), 0, s, (const u16*)a, apitch, w, logits,
+                       (const uint8_t*)labels, sums, (u16*)da, dapitch, partial, M, gscale, (const float*)nullptr,
+                       0.f, 1.f);
 }
 
 template <int K>
@@ -372,20 +502,27 @@ extern "C" {
 int rdp_headk_partial_blocks(long M) { return blocks_for(M); }
 
 int rdp_headk_fwd(const void* a, int apitch, const float* w, const float* b, const void* labels, float* logits,
-                  float* partial, float* sums, float* loss, int M, int K, hipStream_t s) {
-  if (apitch % 8 || M <= 0) return -1;
+                  float* partial, float* sums, float* loss, int M, int K, const float* cw, float dice_w,
+                  float dice_eps, hipStream_t s) {
+  if (apitch % 8 || M <= 0 || !(dice_w >= 0.f) || !(dice_eps > 0.f)) return -1;
   const int nb = blocks_for(M);
-  HEADK_DISPATCH(K, launch_fwd, nb, s, a, apitch, w, b, labels, logits, partial, M)
-  hipLaunchKernelGGL(headk_loss_finalize_kernel, dim3(1), dim3(128), 0, s, partial, nb, sums, loss);
+  const bool ext = headk_ext(cw, dice_w);
+  HEADK_DISPATCH(K, launch_fwd, nb, s, a, apitch, w, b, labels, logits, partial, M, ext, cw)
+  if (ext)
+    hipLaunchKernelGGL(headk_loss_finalize_ext_kernel, dim3(1), dim3(256), 0, s, partial, nb, K, dice_w, dice_eps,
+                       sums, loss);
+  else
+    hipLaunchKernelGGL(headk_loss_finalize_kernel, dim3(1), dim3(128), 0, s, partial, nb, sums, loss);
   return nb;
 }
 
 int rdp_headk_bwd(const void* a, int apitch, const float* w, const float* logits, const void* labels,
                   const float* sums, void* da, int dapitch, float* partial, float* gw, float* gb, int M, int K,
-                  float gscale, hipStream_t s) {
-  if (apitch % 8 || dapitch % 8 || M <= 0) return -1;
+                  float gscale, const float* cw, float dice_w, float dice_eps, hipStream_t s) {
+  if (apitch % 8 || dapitch % 8 || M <= 0 || !(dice_w >= 0.f) || !(dice_eps > 0.f)) return -1;
   const int nb = blocks_for(M);
-  HEADK_DISPATCH(K, launch_bwd, nb, s, a, apitch, w, logits, labels, sums, da, dapitch, partial, M, gscale)
+  HEADK_DISPATCH(K, launch_bwd, nb, s, a, apitch, w, logits, labels, sums, da, dapitch, partial, M, gscale,
+                 headk_ext(cw, dice_w), cw, dice_w, dice_eps)
   const int row = K * HEAD_C + K;
   hipLaunchKernelGGL(headk_grad_finalize_kernel, dim3(row), dim3(256), 0, s, partial, nb, row, K * HEAD_C,
                      gscale, gw, gb);

@@ -259,13 +259,16 @@ int rdp_head_mask(const void* a, int apitch, const float* w, const float* b, flo
 
 // ---- csrc/head_multi.hip --------------------------------------------------------------------------------------
 int rdp_headk_partial_blocks(long M);
-// partial: >= blocks * 2 floats. Returns the number of partial rows, < 0 if nothing was launched.
+// Plain mode (cw == null and dice_w == 0): partial >= blocks * 2 floats, sums >= 2. Extended mode (class
+// weights cw [K] and / or a soft Dice term, dice_w >= 0, dice_eps > 0): partial >= blocks * (2 + 3K),
+// sums >= 2 + 3K = {sum cw*ce, W, I_k, P_k, T_k}. Returns the number of partial rows, < 0 if nothing was launched.
 int rdp_headk_fwd(const void* a, int apitch, const float* w, const float* b, const void* labels, float* logits,
-                  float* partial, float* sums, float* loss, int M, int K, hipStream_t s);
-// partial: >= blocks * (K * 64 + K) floats; gw [K][64], gb [K]
+                  float* partial, float* sums, float* loss, int M, int K, const float* cw, float dice_w,
+                  float dice_eps, hipStream_t s);
+// partial: >= blocks * (K * 64 + K) floats; gw [K][64], gb [K]; cw / dice_w / dice_eps as given to rdp_headk_fwd
 int rdp_headk_bwd(const void* a, int apitch, const float* w, const float* logits, const void* labels,
                   const float* sums, void* da, int dapitch, float* partial, float* gw, float* gb, int M, int K,
-                  float gscale, hipStream_t s);
+                  float gscale, const float* cw, float dice_w, float dice_eps, hipStream_t s);
 int rdp_headk_mask(const void* a, int apitch, const float* w, const float* b, int cls, void* mask, int M, int K,
                    hipStream_t s);
 

@@ -49,8 +49,9 @@ class TrainConfig:
     epochs: int = 50
     validation_split: float = 0.2
     image_size: int = 256
-    # "bce" (reference) or "bce_dice" (north star); "ce" = softmax cross-entropy, the only loss of a
-    # K-class model (``n_classes`` >= 2 switches the default "bce" to it)
+    # "bce" (reference) or "bce_dice" (north star); a K-class model (``n_classes`` >= 2) takes "ce" = softmax
+    # cross-entropy (the default "bce" switches to it) or "ce_dice" = CE + ``dice_weight`` x soft Dice over all
+    # K classes (train/losses.py)
     loss: str = "bce"
     dice_weight: float = 1.0
     seed: int = 0  # the reference split is unseeded; we seed it
@@ -87,6 +88,9 @@ class TrainConfig:
     # comma-separated gray values, the position is the class id, unlisted values are ignored) maps it.
     n_classes: int = 1
     mask_values: str = ""
+    # K-class runs only: per-class CE weights, "1,4,4" (comma-separated like ``mask_values``, one finite value
+    # >= 0 per class, at least one positive); empty = unweighted. They weight CE, not the Dice term.
+    class_weights: str = ""
     # per-epoch validation metrics (per-class IoU / Dice, mean IoU, pixel accuracy: train/metrics.py) from
     # confusion counts accumulated on the device. ``mask_threshold``: the one-class model's probability
     # threshold (applied as a logit, like serving); a K-class model predicts by arg-max.

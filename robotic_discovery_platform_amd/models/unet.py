@@ -390,17 +390,28 @@ class UNetNative(nn.Module):
         return ex.logits_nchw()
 
     def executor(self, batch: int, h: int, w: int, training: bool = True, loss: str = "bce",
-                 dice_weight: float = 1.0) -> "UNetExecutor":
+                 dice_weight: float = 1.0, class_weights=None) -> "UNetExecutor":
         """``loss``: "bce" / "bce_dice" for the one-class head; a K-class model (``n_classes > 1``) takes
-        "ce" only (softmax cross-entropy over integer labels, 255 and labels >= K ignored)."""
-        if self.n_classes > 1 and loss != "ce":
-            raise ValueError(f'a {self.n_classes}-class model trains with loss="ce" only, got {loss!r}')
-        if self.n_classes == 1 and loss == "ce":
-            raise ValueError('loss="ce" needs n_classes > 1 (the one-class head takes "bce" / "bce_dice")')
-        key = (batch, h, w, training, loss, dice_weight)
+        "ce" (softmax cross-entropy over integer labels, 255 and labels >= K ignored) or "ce_dice" (CE +
+        ``dice_weight`` x soft Dice over all K classes, train/losses.py). ``class_weights`` (K-class only):
+        K finite non-negative floats, at least one positive, weighting CE per class."""
+        if self.n_classes > 1 and loss not in ("ce", "ce_dice"):
+            raise ValueError(f'a {self.n_classes}-class model trains with loss="ce" or "ce_dice", got {loss!r}')
+        if self.n_classes == 1 and loss in ("ce", "ce_dice"):
+            raise ValueError(f'loss={loss!r} needs n_classes > 1 (the one-class head takes "bce" / "bce_dice")')
+        if self.n_classes == 1 and class_weights is not None:
+            raise ValueError("class_weights need n_classes > 1")
+        if loss == "ce_dice" and not 0.0 <= float(dice_weight) < float("inf"):
+            raise ValueError(f"dice_weight must be finite and >= 0, got {dice_weight!r}")
+        if class_weights is None:  # the key (and the executor) of every call without weights stays as it was
+            key = (batch, h, w, training, loss, dice_weight)
+        else:
+            from ..train.losses import check_class_weights
+            class_weights = check_class_weights(class_weights, self.n_classes)
+            key = (batch, h, w, training, loss, dice_weight, class_weights)
         cache = self.__dict__.setdefault("_executors", {})
         if key not in cache:
-            cache[key] = UNetExecutor(self, batch, h, w, training, loss, dice_weight)
+            cache[key] = UNetExecutor(self, batch, h, w, training, loss, dice_weight, class_weights)
         return cache[key]
 
 
@@ -533,13 +544,20 @@ def _stream_wait(waiter: "torch.cuda.Stream", waitee: "torch.cuda.Stream"):
 class UNetExecutor:
     """Static-shape forward/backward/step program for one (batch, H, W)."""
 
-    def __init__(self, model: UNetNative, N: int, H: int, W: int, training: bool, loss: str, dice_weight: float):
+    def __init__(self, model: UNetNative, N: int, H: int, W: int, training: bool, loss: str, dice_weight: float,
+                 class_weights=None):
         self.m, self.N, self.H, self.W = model, N, H, W
         self.training = training
-        self.dice_w = float(dice_weight) if loss == "bce_dice" else 0.0
+        self.loss_kind = loss
+        self.dice_w = float(dice_weight) if loss in ("bce_dice", "ce_dice") else 0.0
         self.dice_eps = 1.0
         dev = model.store.device
         self.dev = dev
+        # K-class head only: per-class CE weights (validated by UNetNative.executor) as a device fp32 [K] tensor;
+        # with them or a Dice term the head kernels run their extended mode (csrc/head_multi.hip)
+        self.class_weights = tuple(class_weights) if class_weights is not None else None
+        self.class_w = (torch.tensor(self.class_weights, dtype=torch.float32, device=dev)
+                        if class_weights is not None else None)
         # Fusions (each measured against its separate-kernel form, profiles/dead_ends.md): BN apply +
         # maxpool (forward) and maxpool backward + BN reduce (backward) in one pass each at the Down
         # boundaries, upsample backward + BN reduce at the Up boundaries; in training the 1x1 head
@@ -648,7 +666,8 @@ class UNetExecutor:
         self._head_fwd_grads = False
         self.head_gpart = (torch.zeros(C.head_partial_blocks(M) * 65, dtype=torch.float32, device=dev)
                            if self.head_grads_in_fwd else None)
-        self.loss_sums = torch.zeros(4, dtype=torch.float32, device=dev)
+        # one-class: {bce, inter, psum, tsum}; K classes: {sum w*ce, W, I_k, P_k, T_k} (plain "ce" fills the first 2)
+        self.loss_sums = torch.zeros(4 if self.K == 1 else 2 + 3 * self.K, dtype=torch.float32, device=dev)
         self.loss = torch.zeros(2, dtype=torch.float32, device=dev)
         # stats slab (reused by every conv; finalize runs right after each conv)
         max_rows = max(C.conv_stats_rows(L.x1.shape[0] * L.x1.shape[1] * L.x1.shape[2], L.spec.cout, 0) * 2 * L.spec.cout
@@ -942,8 +961,13 @@ class UNetExecutor:
             return
         if self.K > 1:
             st = self.m.store
-            C.headk_fwd(self.final, st.flat_slice("outc.conv.weight"), st.view("outc.conv.bias"), self.target,
-                        self.logits, self.head_partial, self.loss_sums, self.loss)
+            if self.class_w is None and self.dice_w == 0.0:  # plain CE: the call (and its launches) as ever
+                C.headk_fwd(self.final, st.flat_slice("outc.conv.weight"), st.view("outc.conv.bias"), self.target,
+                            self.logits, self.head_partial, self.loss_sums, self.loss)
+            else:
+                C.headk_fwd(self.final, st.flat_slice("outc.conv.weight"), st.view("outc.conv.bias"), self.target,
+                            self.logits, self.head_partial, self.loss_sums, self.loss,
+                            class_weights=self.class_w, dice_w=self.dice_w, dice_eps=self.dice_eps)
             return
         head_w = self.m.store.view("outc.conv.weight").reshape(-1)
         head_b = self.m.store.view("outc.conv.bias")
@@ -1241,8 +1265,13 @@ class UNetExecutor:
         hgw, hgb = st.flat_slice("outc.conv.weight", st.grad), st.flat_slice("outc.conv.bias", st.grad)
         head_gscale = None
         if self.K > 1:  # softmax CE head: da of the last layer + dW [K][64] / db [K] (csrc/head_multi.hip)
-            C.headk_bwd(self.final, st.flat_slice("outc.conv.weight"), self.logits, self.target, self.loss_sums,
-                        last.da, self.head_partial, hgw, hgb, gscale)
+            if self.class_w is None and self.dice_w == 0.0:
+                C.headk_bwd(self.final, st.flat_slice("outc.conv.weight"), self.logits, self.target, self.loss_sums,
+                            last.da, self.head_partial, hgw, hgb, gscale)
+            else:
+                C.headk_bwd(self.final, st.flat_slice("outc.conv.weight"), self.logits, self.target, self.loss_sums,
+                            last.da, self.head_partial, hgw, hgb, gscale, class_weights=self.class_w,
+                            dice_w=self.dice_w, dice_eps=self.dice_eps)
         elif self.fuse_head and self._head_fwd_grads and gscale == self.head_gscale:
             C.head_grad_finalize(self.head_gpart, self.M, hgw, hgb)  # partials came with the forward
             last.bwd_rows = C.head_partial_blocks(self.M)

@@ -47,6 +47,7 @@ from ..models.unet import NativeAdam, UNetNative
 from ..models.unet_ref import UNetRef
 from ..parallel.ddp import FlatBucketer, broadcast_module_state, dist_info, emulate_spec, native_comm_group
 from ..utils import trace
+from .losses import ce_dice_reference, check_class_weights
 
 
 class NativeTrainer:
@@ -56,9 +57,10 @@ class NativeTrainer:
 
     def __init__(self, model: UNetNative, batch: int, h: int, w: int, lr: float = 1e-4, loss: str = "bce",
                  dice_weight: float = 1.0, graph="auto", bucket_mb: float = 16.0, sync_bn: bool = False,
-                 grad_comm: Optional[str] = None, ddp_force: Optional[bool] = None, plan="auto"):
+                 grad_comm: Optional[str] = None, ddp_force: Optional[bool] = None, plan="auto", class_weights=None):
         self.model = model
-        self.ex = model.executor(batch, h, w, training=True, loss=loss, dice_weight=dice_weight)
+        self.ex = model.executor(batch, h, w, training=True, loss=loss, dice_weight=dice_weight,
+                                 class_weights=class_weights)
         self.opt = NativeAdam(model, lr=lr)
         self.rank, self.world = dist_info()
         self.bucketer = None
@@ -310,7 +312,11 @@ class NativeTrainer:
 
     def eval_loss(self) -> torch.Tensor:
         """Validation forward (batch statistics are NOT updated: eval-mode BN)."""
-        kw = {"loss": "ce"} if self.model.n_classes > 1 else {}  # a K-class model takes "ce" only
+        kw = {}
+        if self.model.n_classes > 1:  # the training executor's loss: "ce" / "ce_dice", its Dice and class weights
+            kw = {"loss": self.ex.loss_kind, "class_weights": self.ex.class_weights}
+            if self.ex.loss_kind == "ce_dice":
+                kw["dice_weight"] = self.ex.dice_w
         ev = self.model.executor(self.ex.N, self.ex.H, self.ex.W, training=False, **kw)
         ev.target.copy_(self.ex.target)
         ev.x_in.copy_(self.ex.x_in)
@@ -330,10 +336,13 @@ class EagerTrainer:
     """Plain-torch trainer (reference execution model) with the same flat-bucket DDP."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, loss: str = "bce", dice_weight: float = 1.0,
-                 bucket_mb: float = 16.0, amp: Optional[torch.dtype] = None):
+                 bucket_mb: float = 16.0, amp: Optional[torch.dtype] = None, class_weights=None):
         self.model = model
         self.opt = torch.optim.Adam(model.parameters(), lr=lr)
         self.loss_kind, self.dice_w = loss, dice_weight
+        if loss not in ("ce", "ce_dice") and class_weights is not None:
+            raise ValueError('class_weights need a K-class loss ("ce" / "ce_dice")')
+        self.class_weights = tuple(float(v) for v in class_weights) if class_weights is not None else None
         self.amp = amp
         self.rank, self.world = dist_info()
         self.bucketer = None
@@ -355,6 +364,9 @@ class EagerTrainer:
 
     def compute_loss(self, logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         logits = logits.float()
+        if self.loss_kind == "ce_dice" or (self.loss_kind == "ce" and self.class_weights is not None):
+            cw = check_class_weights(self.class_weights, logits.shape[1])
+            return ce_dice_reference(logits, target, cw, self.dice_w if self.loss_kind == "ce_dice" else 0.0)[0]
         if self.loss_kind == "ce":  # K-class logits [N,K,H,W], integer labels [N,H,W] or [N,1,H,W]; 255 = ignore
             labels = target.long()
             if labels.dim() == 4:

@@ -39,6 +39,7 @@ from ..data.dataset import (SegmentationDataset, SyntheticSegmentationDataset, c
 from ..data.synthetic import write_dataset
 from ..models.unet_ref import UNetRef
 from ..parallel.ddp import DistributedShardSampler, dist_info
+from .losses import check_class_weights, parse_class_weights
 
 log = logging.getLogger("rdp.train")
 
@@ -56,23 +57,32 @@ def _pick_backend(cfg: TrainConfig, dev: torch.device) -> str:
 
 
 def resolve_classes(cfg: TrainConfig) -> TrainConfig:
-    """Validate ``n_classes`` (1..8) and settle the loss of a K-class run: "ce"; the default "bce" is
-    switched to it, an explicit "bce_dice" raises as the trainers do. Returns ``cfg`` or an edited copy."""
+    """Validate ``n_classes`` (1..8) and settle the loss of a K-class run: "ce" or "ce_dice"; the default
+    "bce" is switched to "ce", an explicit "bce_dice" raises as the trainers do. ``class_weights`` ("1,4,4")
+    must list ``n_classes`` valid weights; a one-class run takes neither them nor "ce_dice". Returns ``cfg``
+    or an edited copy."""
     k = check_n_classes(cfg.n_classes)
+    weights = parse_class_weights(cfg.class_weights)
     if k == 1:
+        if cfg.loss == "ce_dice" or weights is not None:
+            raise ValueError('loss="ce_dice" and class_weights need n_classes > 1 '
+                             '(the one-class model takes "bce" / "bce_dice")')
         return cfg
+    check_class_weights(weights, k)
     if cfg.loss == "bce":
         log.info('n_classes = %d: the loss is softmax cross-entropy ("ce")', k)
         return replace(cfg, loss="ce")
-    if cfg.loss != "ce":
-        raise ValueError(f'a {k}-class model trains with loss="ce" only, got {cfg.loss!r}')
+    if cfg.loss not in ("ce", "ce_dice"):
+        raise ValueError(f'a {k}-class model trains with loss="ce" or "ce_dice", got {cfg.loss!r}')
     return cfg
 
 
-def native_eval_batch(model, x, y, loss: str, dice_weight: float = 1.0, confusion=None) -> torch.Tensor:
+def native_eval_batch(model, x, y, loss: str, dice_weight: float = 1.0, confusion=None,
+                      class_weights=None) -> torch.Tensor:
     """Eval-mode forward of one batch on the native executor; returns the device loss. ``confusion`` (a
     ``ConfusionAccumulator``) also takes the batch's counts, from the executor's own logits / target."""
-    ex = model.executor(x.shape[0], x.shape[2], x.shape[3], training=False, loss=loss, dice_weight=dice_weight)
+    ex = model.executor(x.shape[0], x.shape[2], x.shape[3], training=False, loss=loss, dice_weight=dice_weight,
+                        class_weights=class_weights)
     ex.set_input(x, y)
     ex.forward()
     if confusion is not None:
@@ -87,6 +97,7 @@ class _NativeRunner:
         from ..models.unet import NativeAdam
         from .engine import NativeTrainer
         self.model, self.cfg = model, cfg
+        self.class_weights = parse_class_weights(cfg.class_weights)
         self._trainers = {}
         self._cls = NativeTrainer
         self._shared_opt = NativeAdam(model, lr=cfg.learning_rate)
@@ -96,7 +107,7 @@ class _NativeRunner:
         if key not in self._trainers:
             tr = self._cls(self.model, n, h, w, lr=self.cfg.learning_rate, loss=self.cfg.loss,
                            dice_weight=self.cfg.dice_weight, graph=self.cfg.graph, bucket_mb=self.cfg.grad_bucket_mb,
-                           sync_bn=self.cfg.sync_bn, grad_comm=self.cfg.grad_comm)
+                           sync_bn=self.cfg.sync_bn, grad_comm=self.cfg.grad_comm, class_weights=self.class_weights)
             tr.opt = self._shared_opt
             self._trainers[key] = tr
         return self._trainers[key]
@@ -114,7 +125,8 @@ class _NativeRunner:
         return tr.step()[0]
 
     def eval_loss(self, x, y, confusion=None) -> torch.Tensor:
-        return native_eval_batch(self.model, x, y, self.cfg.loss, self.cfg.dice_weight, confusion)
+        return native_eval_batch(self.model, x, y, self.cfg.loss, self.cfg.dice_weight, confusion,
+                                 self.class_weights)
 
     def optimizer_state(self):
         return self._shared_opt.state_dict()
@@ -128,7 +140,8 @@ class _EagerRunner:
         from .engine import EagerTrainer
         amp = torch.bfloat16 if (dev.type == "cuda" and cfg.dtype == "bf16") else None
         self.tr = EagerTrainer(model, lr=cfg.learning_rate, loss=cfg.loss, dice_weight=cfg.dice_weight,
-                               bucket_mb=cfg.grad_bucket_mb, amp=amp)
+                               bucket_mb=cfg.grad_bucket_mb, amp=amp,
+                               class_weights=parse_class_weights(cfg.class_weights))
         self.model = model
 
     def train_step(self, x, y):
@@ -209,6 +222,8 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
             mlstore.log_params({k: v for k, v in asdict(cfg).items() if k.startswith("aug_")})
         if K > 1:
             mlstore.log_params({"n_classes": K, "mask_values": cfg.mask_values})
+            if cfg.class_weights.strip():
+                mlstore.log_params({"class_weights": cfg.class_weights})
 
     # ---- data ----
     # GPU: the processed dataset is built once on the device (u8 NHWC; INTER_AREA / nearest resizes
