@@ -1338,6 +1338,73 @@ void adam(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c1
                        (int*)step.data_ptr(), inc ? 1 : 0, max_blocks, st)) == 0, "adam: numel must be a multiple of 4");
 }
 
+// ---- optimizer scalars on the device: gradient norm, clip coefficient, learning-rate multiplier ----
+int grad_sqnorm_blocks(long n) {
+  TORCH_CHECK(n > 0 && n % 4 == 0, "grad_sqnorm_blocks: n must be a positive multiple of 4");
+  return rdp_grad_sqnorm_blocks(n);
+}
+
+// partial[0 .. blocks) = per-block fp64 sums of g^2 (g fp32 or bf16); returns blocks
+int grad_sqnorm(torch::Tensor g, torch::Tensor partial, int max_blocks) {
+  const bool gbf = g.scalar_type() == torch::kBFloat16;
+  if (!gbf) check_f32(g, "g");
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous(), "g: contiguous device tensor");
+  const long n = g.numel();
+  TORCH_CHECK(n > 0 && n % 4 == 0, "grad_sqnorm: numel must be a positive multiple of 4");
+  TORCH_CHECK((uintptr_t)g.data_ptr() % (gbf ? 8 : 16) == 0, "grad_sqnorm: g must be aligned to 4 elements");
+  TORCH_CHECK(max_blocks >= 0, "grad_sqnorm: max_blocks");
+  int blocks = rdp_grad_sqnorm_blocks(n);
+  if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+  TORCH_CHECK(partial.is_cuda() && partial.scalar_type() == torch::kFloat64 && partial.is_contiguous() &&
+                  partial.device() == g.device() && partial.numel() >= blocks,
+              "grad_sqnorm: partial must be a contiguous float64 tensor on g's device with at least ", blocks,
+              " elements");
+  const void* gp = g.data_ptr();
+  const int r = RDP_PLAN(rdp_grad_sqnorm(gp, gbf ? 1 : 0, n, partial.data_ptr<double>(), max_blocks, st));
+  TORCH_CHECK(r == blocks, "grad_sqnorm");
+  return r;
+}
+
+void optim_ctl(torch::Tensor partial, int nblocks, double gscale, double clip, int sched, int warmup, int total,
+               double min_ratio, torch::Tensor step, torch::Tensor ctl) {
+  TORCH_CHECK(partial.is_cuda() && partial.scalar_type() == torch::kFloat64 && partial.is_contiguous(),
+              "optim_ctl: partial must be a contiguous float64 device tensor");
+  TORCH_CHECK(nblocks >= 0 && nblocks <= partial.numel(), "optim_ctl: nblocks exceeds the partial buffer");
+  TORCH_CHECK(step.scalar_type() == torch::kInt32 && step.is_cuda() && step.numel() >= 1, "step int32");
+  check_f32(ctl, "ctl");
+  TORCH_CHECK(ctl.numel() >= 4, "optim_ctl: ctl holds 4 floats");
+  TORCH_CHECK(std::isfinite(clip) && clip >= 0.0 && std::isfinite(gscale), "optim_ctl: clip / gscale");
+  TORCH_CHECK(sched == 0 || sched == 1, "optim_ctl: sched 0 (constant) or 1 (cosine)");
+  TORCH_CHECK(warmup >= 0 && min_ratio >= 0.0 && min_ratio <= 1.0, "optim_ctl: warmup / min_ratio");
+  TORCH_CHECK(sched == 0 || total > warmup, "optim_ctl: cosine needs total > warmup");
+  TORCH_CHECK(RDP_PLAN(rdp_optim_ctl(partial.data_ptr<double>(), nblocks, gscale, clip, sched, warmup, total, min_ratio,
+                                     (const int*)step.data_ptr(), ctl.data_ptr<float>(), st)) == 0,
+              "optim_ctl: bad argument");
+}
+
+void adam_ctl(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v, c10::optional<torch::Tensor> shadow,
+              double lr, double b1, double b2, double eps, double wd, double gscale, torch::Tensor step,
+              torch::Tensor ctl, bool inc, int max_blocks) {
+  check_f32(p, "p"); check_f32(m, "m"); check_f32(v, "v");
+  const bool gbf = g.scalar_type() == torch::kBFloat16;  // bf16 gradients (the DDP bf16 all-reduce buffer)
+  if (!gbf) check_f32(g, "g");
+  TORCH_CHECK(g.is_cuda() && g.is_contiguous(), "g: contiguous device tensor");
+  TORCH_CHECK(g.numel() == p.numel() && m.numel() == p.numel() && v.numel() == p.numel(), "adam numel");
+  TORCH_CHECK(step.scalar_type() == torch::kInt32 && step.is_cuda(), "step int32");
+  check_f32(ctl, "ctl");
+  TORCH_CHECK(ctl.numel() >= 4, "adam_ctl: ctl holds 4 floats");
+  void* sh = nullptr;
+  if (shadow) {
+    TORCH_CHECK(shadow->scalar_type() == torch::kBFloat16 && shadow->numel() == p.numel(), "shadow");
+    sh = shadow->data_ptr();
+  }
+  const void* gp = g.data_ptr();
+  TORCH_CHECK(RDP_PLAN(rdp_adam_ctl(p.data_ptr<float>(), gp, gbf ? 1 : 0, m.data_ptr<float>(), v.data_ptr<float>(), sh,
+                                    p.numel(), (float)lr, (float)b1, (float)b2, (float)eps, (float)wd, (float)gscale,
+                                    (int*)step.data_ptr(), ctl.data_ptr<float>(), inc ? 1 : 0, max_blocks, st)) == 0,
+              "adam_ctl: numel must be a multiple of 4");
+}
+
 void cast_bf16(torch::Tensor p, torch::Tensor out) {
   check_f32(p, "p");
   TORCH_CHECK(out.scalar_type() == torch::kBFloat16 && out.numel() == p.numel(), "cast out");
@@ -2024,6 +2091,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adam", on_device(&adam), py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("lr"),
         py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("gscale"), py::arg("step"),
         py::arg("inc") = true, py::arg("max_blocks") = 0);
+  m.def("grad_sqnorm_blocks", &grad_sqnorm_blocks, py::arg("n"));
+  m.def("grad_sqnorm", on_device(&grad_sqnorm), py::arg("g"), py::arg("partial"), py::arg("max_blocks") = 0);
+  m.def("optim_ctl", on_device(&optim_ctl), py::arg("partial"), py::arg("nblocks"), py::arg("gscale"), py::arg("clip"),
+        py::arg("sched"), py::arg("warmup"), py::arg("total"), py::arg("min_ratio"), py::arg("step"), py::arg("ctl"));
+  m.def("adam_ctl", on_device(&adam_ctl), py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("gscale"), py::arg("step"),
+        py::arg("ctl"), py::arg("inc") = true, py::arg("max_blocks") = 0);
   m.def("cast_bf16", on_device(&cast_bf16));
   m.def("h2d_copy", &h2d_copy, py::arg("src"), py::arg("dst"));
   m.def("wprep", on_device(&wprep), py::arg("master"), py::arg("out"), py::arg("segs"), py::arg("nseg"),

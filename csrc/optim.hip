@@ -17,18 +17,80 @@
 
 // G = float (the flat fp32 gradient) or u16: bf16 gradients straight from the DDP bf16 all-reduce
 // buffer (parallel/ddp.py comm_dtype), widened here instead of by a separate pass.
+// The update of one thread's grid-stride share, written once for both kernels below. LR / GSCALE: the
+// rate and the gradient scale the thread uses (adam_kernel: its arguments; adam_ctl_kernel: their products
+// with the step's device scalars, formed once per thread before the loop).
+#define RDP_ADAM_UPDATE(LR, GSCALE)                                                                              \
+  const float lr_ = (LR), gscale_ = (GSCALE);                                                                    \
+  const int t = step[0] + 1;                                                                                     \
+  const float bc1 = 1.f - (float)pow((double)b1, (double)t);                                                     \
+  const float bc2 = 1.f - (float)pow((double)b2, (double)t);                                                     \
+  const float step_size = lr_ / bc1;                                                                             \
+  const float bc2s = sqrtf(bc2);                                                                                 \
+  const long n4 = n >> 2;                                                                                        \
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {        \
+    float4 pp = ((float4*)p)[i], gg, mm = ((float4*)m)[i], vv = ((float4*)v)[i];                                 \
+    if constexpr (sizeof(G) == 4) {                                                                              \
+      gg = ((const float4*)g)[i];                                                                                \
+    } else {                                                                                                     \
+      const uint2 gb = ((const uint2*)g)[i];                                                                     \
+      gg = make_float4(__uint_as_float(gb.x << 16), __uint_as_float(gb.x & 0xffff0000u),                         \
+                       __uint_as_float(gb.y << 16), __uint_as_float(gb.y & 0xffff0000u));                        \
+    }                                                                                                            \
+    float* pa = &pp.x; float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;                                  \
+    _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                              \
+      float gk = ga[k] * gscale_;                                                                                \
+      if (wd != 0.f) gk = fmaf(wd, pa[k], gk);                                                                   \
+      ma[k] = ma[k] + (1.f - b1) * (gk - ma[k]);                                                                 \
+      va[k] = va[k] * b2 + (1.f - b2) * gk * gk;                                                                 \
+      const float den = sqrtf(va[k]) / bc2s + eps;                                                               \
+      pa[k] = pa[k] - step_size * ma[k] / den;                                                                   \
+    }                                                                                                            \
+    ((float4*)p)[i] = pp;                                                                                        \
+    ((float4*)m)[i] = mm;                                                                                        \
+    ((float4*)v)[i] = vv;                                                                                        \
+    if (shadow) {                                                                                                \
+      uint2 o;                                                                                                   \
+      o.x = pack2bf(pp.x, pp.y);                                                                                 \
+      o.y = pack2bf(pp.z, pp.w);                                                                                 \
+      ((uint2*)shadow)[i] = o;                                                                                   \
+    }                                                                                                            \
+  }
+
 template <typename G>
 __global__ void adam_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, u16* __restrict__ shadow, long n, float lr, float b1, float b2,
                             float eps, float wd, float gscale, const int* __restrict__ step) {
-  const int t = step[0] + 1;
-  const float bc1 = 1.f - (float)pow((double)b1, (double)t);
-  const float bc2 = 1.f - (float)pow((double)b2, (double)t);
-  const float step_size = lr / bc1;
-  const float bc2s = sqrtf(bc2);
+  RDP_ADAM_UPDATE(lr, gscale)
+}
+
+// The update with the step's device scalars (optim_ctl_kernel below): ctl[0] = the clip coefficient folded
+// into gscale, ctl[1] = the learning-rate multiplier, each product formed once per thread in fp32. With
+// ctl = {1, 1} both products are exact, so the update is bitwise adam_kernel's.
+template <typename G>
+__global__ void adam_ctl_kernel(float* __restrict__ p, const G* __restrict__ g, float* __restrict__ m,
+                                float* __restrict__ v, u16* __restrict__ shadow, long n, float lr, float b1, float b2,
+                                float eps, float wd, float gscale, const int* __restrict__ step,
+                                const float* __restrict__ ctl) {
+  RDP_ADAM_UPDATE(lr * ctl[1], gscale * ctl[0])
+}
+#undef RDP_ADAM_UPDATE
+
+// Sum of squares of the flat gradient, one fp64 partial per block: squares accumulate in fp64 per thread
+// (grid-stride, 16-B / 8-B loads like adam_kernel), then a wave reduction, then the block's 4 wave sums
+// through LDS. No atomics: a given grid gives the same bits every run. A pure streaming read; the grid is
+// capped at 2048 blocks (256 CUs x 8 blocks of 256 threads) and the loop is unrolled so that each thread
+// keeps 4 independent 16-B loads in flight.
+constexpr int kSqnormMaxBlocks = 2048;
+
+template <typename G>
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const G* __restrict__ g, long n,
+                                                          double* __restrict__ partial) {
   const long n4 = n >> 2;
+  double acc = 0.0;
+#pragma unroll 4
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    float4 pp = ((float4*)p)[i], gg, mm = ((float4*)m)[i], vv = ((float4*)v)[i];
+    float4 gg;
     if constexpr (sizeof(G) == 4) {
       gg = ((const float4*)g)[i];
     } else {
@@ -36,26 +98,56 @@ __global__ void adam_kernel(float* __restrict__ p, const G* __restrict__ g, floa
       gg = make_float4(__uint_as_float(gb.x << 16), __uint_as_float(gb.x & 0xffff0000u),
                        __uint_as_float(gb.y << 16), __uint_as_float(gb.y & 0xffff0000u));
     }
-    float* pa = &pp.x; float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float gk = ga[k] * gscale;
-      if (wd != 0.f) gk = fmaf(wd, pa[k], gk);
-      ma[k] = ma[k] + (1.f - b1) * (gk - ma[k]);
-      va[k] = va[k] * b2 + (1.f - b2) * gk * gk;
-      const float den = sqrtf(va[k]) / bc2s + eps;
-      pa[k] = pa[k] - step_size * ma[k] / den;
-    }
-    ((float4*)p)[i] = pp;
-    ((float4*)m)[i] = mm;
-    ((float4*)v)[i] = vv;
-    if (shadow) {
-      uint2 o;
-      o.x = pack2bf(pp.x, pp.y);
-      o.y = pack2bf(pp.z, pp.w);
-      ((uint2*)shadow)[i] = o;
-    }
+    acc = fma((double)gg.x, (double)gg.x, acc);
+    acc = fma((double)gg.y, (double)gg.y, acc);
+    acc = fma((double)gg.z, (double)gg.z, acc);
+    acc = fma((double)gg.w, (double)gg.w, acc);
   }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  __shared__ double ws[4];
+  const int tid = threadIdx.x;
+  if ((tid & 63) == 0) ws[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) partial[blockIdx.x] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+}
+
+// One block: the step's optimizer scalars, formed in fp64 and rounded once to fp32.
+//   ctl = {coef, mult, norm, (float)t},  t = step[0] (completed updates)
+//   norm = sqrt(sum of partial[0 .. nblocks)) * gscale;  coef = min(1, clip / (norm + 1e-6)), 1 when clip == 0
+//   mult = (t + 1) / W for t < W; else 1 (sched 0) or r + (1 - r) / 2 * (1 + cos(pi q)), q = min(1, (t - W) / max(1, T - W))
+// The partials are summed in a fixed order (thread k takes k, k + 256, ...; then a fixed tree), so the
+// result does not depend on scheduling. nblocks == 0: no norm was computed (coef 1, norm 0).
+__global__ __launch_bounds__(256) void optim_ctl_kernel(const double* __restrict__ partial, int nblocks, double gscale,
+                                                        double clip, int sched, int W, int T, double r,
+                                                        const int* __restrict__ step, float* __restrict__ ctl) {
+  __shared__ double sh[256];
+  const int tid = threadIdx.x;
+  double a = 0.0;
+  for (int i = tid; i < nblocks; i += 256) a += partial[i];
+  sh[tid] = a;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) sh[tid] += sh[tid + o];
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const int t = step[0];
+  const double norm = nblocks > 0 ? sqrt(sh[0]) * gscale : 0.0;
+  double coef = 1.0;
+  if (clip > 0.0 && nblocks > 0) coef = fmin(1.0, clip / (norm + 1e-6));
+  double mult = 1.0;
+  if (t < W) {
+    mult = (double)(t + 1) / (double)W;
+  } else if (sched == 1) {
+    const int span = T - W > 1 ? T - W : 1;
+    const double q = fmin(1.0, (double)(t - W) / (double)span);
+    mult = r + (1.0 - r) * 0.5 * (1.0 + cospi(q));  // cospi: exactly 1 / -1 at q = 0 / 1
+  }
+  ctl[0] = (float)coef;
+  ctl[1] = (float)mult;
+  ctl[2] = (float)norm;
+  ctl[3] = (float)t;
 }
 
 __global__ void step_inc_kernel(int* step) { step[0] += 1; }
@@ -176,6 +268,46 @@ int rdp_adam(float* p, const void* g, int g_bf16, float* m, float* v, void* shad
     hipLaunchKernelGGL(adam_kernel<float>, dim3(grid), dim3(256), 0, s, p, (const float*)g, m, v, (u16*)shadow, n, lr,
                        b1, b2, eps, wd, gscale, step);
   if (inc) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step);
+  return 0;
+}
+
+int rdp_adam_ctl(float* p, const void* g, int g_bf16, float* m, float* v, void* shadow, long n, float lr, float b1,
+                 float b2, float eps, float wd, float gscale, int* step, const float* ctl, int inc, int max_blocks,
+                 hipStream_t s) {
+  if (n % 4) return -1;
+  const long n4 = n / 4;
+  int grid = (int)std::max<long>(1, std::min<long>((n4 + 255) / 256, 8192));
+  if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+  if (g_bf16)
+    hipLaunchKernelGGL(adam_ctl_kernel<u16>, dim3(grid), dim3(256), 0, s, p, (const u16*)g, m, v, (u16*)shadow, n, lr,
+                       b1, b2, eps, wd, gscale, step, ctl);
+  else
+    hipLaunchKernelGGL(adam_ctl_kernel<float>, dim3(grid), dim3(256), 0, s, p, (const float*)g, m, v, (u16*)shadow, n,
+                       lr, b1, b2, eps, wd, gscale, step, ctl);
+  if (inc) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, s, step);
+  return 0;
+}
+
+int rdp_grad_sqnorm_blocks(long n) {
+  return (int)std::max<long>(1, std::min<long>((n / 4 + 255) / 256, kSqnormMaxBlocks));
+}
+
+int rdp_grad_sqnorm(const void* g, int g_bf16, long n, double* partial, int max_blocks, hipStream_t s) {
+  if (n <= 0 || n % 4) return -1;
+  int grid = rdp_grad_sqnorm_blocks(n);
+  if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+  if (g_bf16)
+    hipLaunchKernelGGL(grad_sqnorm_kernel<u16>, dim3(grid), dim3(256), 0, s, (const u16*)g, n, partial);
+  else
+    hipLaunchKernelGGL(grad_sqnorm_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)g, n, partial);
+  return grid;
+}
+
+int rdp_optim_ctl(const double* partial, int nblocks, double gscale, double clip, int sched, int W, int T, double r,
+                  const int* step, float* ctl, hipStream_t s) {
+  if (nblocks < 0 || nblocks > kSqnormMaxBlocks || W < 0 || (sched != 0 && sched != 1)) return -1;
+  hipLaunchKernelGGL(optim_ctl_kernel, dim3(1), dim3(256), 0, s, partial, nblocks, gscale, clip, sched, W, T, r, step,
+                     ctl);
   return 0;
 }
 

@@ -307,6 +307,20 @@ int rdp_bn_relu_bwd_apply(const void* da, int dapitch, const void* y, int ypitch
 // the next forward's first layers
 int rdp_adam(float* p, const void* g, int g_bf16, float* m, float* v, void* shadow, long n, float lr, float b1,
              float b2, float eps, float wd, float gscale, int* step, int inc, int max_blocks, hipStream_t s);
+// rdp_adam with the step's device scalars: g is scaled by gscale * ctl[0] (the clip coefficient) and the rate
+// is lr * ctl[1] (the schedule's multiplier), both read from the 4-float block rdp_optim_ctl wrote
+int rdp_adam_ctl(float* p, const void* g, int g_bf16, float* m, float* v, void* shadow, long n, float lr, float b1,
+                 float b2, float eps, float wd, float gscale, int* step, const float* ctl, int inc, int max_blocks,
+                 hipStream_t s);
+// sum of squares of g (fp32, or bf16 with g_bf16) as one fp64 partial per block: returns the number of blocks
+// written (partial[0 .. blocks)), at most rdp_grad_sqnorm_blocks(n), or max_blocks when that is smaller and
+// > 0; -1 unless n > 0 and n % 4 == 0. No atomics: the same grid gives the same bits every run
+int rdp_grad_sqnorm(const void* g, int g_bf16, long n, double* partial, int max_blocks, hipStream_t s);
+int rdp_grad_sqnorm_blocks(long n);
+// one block: ctl = {coef, mult, norm, (float)step[0]} from the partials (nblocks == 0: no norm, coef 1) and the
+// device step counter; sched 0 = constant, 1 = cosine; formed in fp64, rounded once. -1 on a bad argument
+int rdp_optim_ctl(const double* partial, int nblocks, double gscale, double clip, int sched, int W, int T, double r,
+                  const int* step, float* ctl, hipStream_t s);
 int rdp_cast_bf16(const float* p, void* out, long n, hipStream_t s);
 // segs: device array of nseg WSeg {long src, long dst, int kind, cout, cin, taps, tile0, pad} (40 bytes
 // each; tile0 = the running sum of wseg_tiles over the earlier segments); tiles = the table's total tile

@@ -96,6 +96,14 @@ class TrainConfig:
     # threshold (applied as a logit, like serving); a K-class model predicts by arg-max.
     val_metrics: bool = False
     mask_threshold: float = 0.5
+    # Gradient-norm clipping and learning-rate schedule (train/schedule.py), off by default. ``clip_grad_norm``:
+    # the L2 threshold of torch's clip_grad_norm_ over the whole (DDP-averaged) gradient, 0 = off.
+    # ``lr_schedule``: "constant" or "cosine" (decay to ``min_lr_ratio`` x learning_rate over the run's steps,
+    # epochs x this rank's steps per epoch), after ``warmup_steps`` of linear warmup.
+    clip_grad_norm: float = 0.0
+    lr_schedule: str = "constant"
+    warmup_steps: int = 0
+    min_lr_ratio: float = 0.0
 
 
 @dataclass

@@ -1374,9 +1374,23 @@ class NativeAdam:
     gradient became final -- neutral at bs64, 3% slower at bs4 from the 18 extra launches.)"""
 
     def __init__(self, model: UNetNative, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0, clip_grad_norm: float = 0.0, lr_schedule: str = "constant",
+                 warmup_steps: int = 0, total_steps: Optional[int] = None, min_lr_ratio: float = 0.0):
+        """``clip_grad_norm`` (0 = off), ``lr_schedule`` ("constant" / "cosine"), ``warmup_steps``,
+        ``total_steps`` and ``min_lr_ratio``: train/schedule.py. With any of them on, the clip coefficient
+        and the rate multiplier are formed on the device each step (from the gradient and the step counter)
+        and the update reads them there, so the options are constants of a recorded launch plan."""
+        from ..train.schedule import OptimOptions
         self.m = model
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        self.options = OptimOptions(clip_grad_norm, lr_schedule, warmup_steps, total_steps, min_lr_ratio)
+        self._ctl = self._partial = None
+        if self.options.enabled:
+            # allocated once, next to the store's step counter: {coef, mult, norm, t} and the norm pass's
+            # per-block fp64 partials (static buffers, as a launch plan needs)
+            st = model.store
+            self._ctl = torch.tensor([1.0, 1.0, 0.0, 0.0], dtype=torch.float32, device=st.device)
+            self._partial = torch.zeros(_native().grad_sqnorm_blocks(st.numel), dtype=torch.float64, device=st.device)
 
     # Overlap the update with the next forward (RDP_ADAM_OVERLAP, default on; needs ``side`` and a model
     # whose parameter layout splits, UNetNative._adam_split)
@@ -1393,6 +1407,8 @@ class NativeAdam:
         rebuilt there, off the critical path, overlapping the next forward (which reads only the packed
         first layer and the transposed decoder's weights, rebuilt here); the next backward waits for
         them (:meth:`UNetExecutor.backward`)."""
+        if self.options.enabled:
+            return self._step_ctl(gscale, side, grad)
         C = _native()
         st = self.m.store
         m = self.m
@@ -1436,9 +1452,70 @@ class NativeAdam:
             C.wprep(st.flat, m.derived, m._segs_bwd, m._nseg_bwd, None, m._wblk_bwd)
         m.__dict__["_wprep_pending"] = side
 
+    def _step_ctl(self, gscale: float, side, grad):
+        """:meth:`step` with clipping and / or a schedule on: the same launches on the same streams, with
+        ``adam_ctl`` for ``adam``, behind the norm pass (clipping only) and the one-block ``optim_ctl`` on
+        the current stream.
+
+        Ordering of the device scalars: ``optim_ctl`` reads the step counter, which the previous step
+        advanced on ``side`` (the dgrad re-layout) -- this step's backward joined that stream before it
+        ran (``UNetExecutor.backward``; unconditionally while a plan is recorded), and the same join puts
+        the previous step's group B, the last reader of ``ctl``, before this ``optim_ctl`` overwrites it.
+        Group B reads ``ctl`` on ``side`` after ``_stream_wait(side, main)``, i.e. after ``optim_ctl``."""
+        C = _native()
+        st = self.m.store
+        m = self.m
+        o = self.options
+        g = st.grad if grad is None else grad
+        nblk = C.grad_sqnorm(g, self._partial) if o.clip_grad_norm > 0 else 0
+        C.optim_ctl(self._partial, nblk, gscale, o.clip_grad_norm, 1 if o.lr_schedule == "cosine" else 0,
+                    int(o.warmup_steps), int(o.total_steps or 0), o.min_lr_ratio, st.step, self._ctl)
+        ctl = self._ctl
+        split = m._adam_split
+        if side is not None and self.OVERLAP and 0 < split < st.numel and m._nseg_bwd > 0:
+            a, b = slice(0, split), slice(split, st.numel)
+            C.adam_ctl(st.flat[a], g[a], st.exp_avg[a], st.exp_avg_sq[a], st.shadow[a], self.lr, self.betas[0],
+                       self.betas[1], self.eps, self.wd, gscale, st.step, ctl, False)
+            if m._nseg_fwd_a:
+                C.wprep(st.flat, m.derived, m._segs_fwd_a, m._nseg_fwd_a, None, m._wblk_fwd_a)
+            if m.__dict__.get("_adam_ev") is None:
+                m.__dict__["_adam_ev"] = C.event_create()
+            _stream_wait(side, torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                C.adam_ctl(st.flat[b], g[b], st.exp_avg[b], st.exp_avg_sq[b], st.shadow[b], self.lr, self.betas[0],
+                           self.betas[1], self.eps, self.wd, gscale, st.step, ctl, False, self.SIDE_BLOCKS)
+                if m._nseg_fwd_b:
+                    C.wprep(st.flat, m.derived, m._segs_fwd_b, m._nseg_fwd_b, None, m._wblk_fwd_b)
+                C.event_record(m._adam_ev, side.cuda_stream)
+                C.wprep(st.flat, m.derived, m._segs_bwd, m._nseg_bwd, st.step, m._wblk_bwd)
+            m.__dict__["_wprep_pending"] = side
+            m.__dict__["_adam_ev_pending"] = True
+            return
+        C.adam_ctl(st.flat, g, st.exp_avg, st.exp_avg_sq, st.shadow, self.lr, self.betas[0], self.betas[1], self.eps,
+                   self.wd, gscale, st.step, ctl, False)
+        if side is None or m._nseg_bwd == 0:
+            C.wprep(st.flat, m.derived, m._segs, m._nseg, st.step, m._wblk)
+            return
+        C.wprep(st.flat, m.derived, m._segs_fwd, m._nseg_fwd, st.step, m._wblk_fwd)
+        _stream_wait(side, torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            C.wprep(st.flat, m.derived, m._segs_bwd, m._nseg_bwd, None, m._wblk_bwd)
+        m.__dict__["_wprep_pending"] = side
+
+    def last_ctl(self) -> Optional[dict]:
+        """The last step's device scalars, ``{"coef", "mult", "norm", "t"}`` (``None`` with the options
+        off). A host read that waits for the device: call it per epoch, never per step."""
+        if self._ctl is None:
+            return None
+        c = self._ctl.tolist()  # written on the stepping (current) stream: the copy is ordered behind it
+        return {"coef": c[0], "mult": c[1], "norm": c[2], "t": int(c[3])}
+
     def hyper_key(self) -> tuple:
-        """The hyper-parameters a recorded launch plan bakes in (NativeTrainer re-records on change)."""
-        return (float(self.lr), tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
+        """The hyper-parameters a recorded launch plan bakes in (NativeTrainer re-records on change). The
+        clip / schedule options are constants of a run: the rate a step uses is formed on the device, so a
+        schedule does not change the key."""
+        key = (float(self.lr), tuple(float(b) for b in self.betas), float(self.eps), float(self.wd))
+        return key + self.options.key() if self.options.enabled else key
 
     def state_dict(self):
         st = self.m.store

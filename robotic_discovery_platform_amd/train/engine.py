@@ -21,8 +21,10 @@ the step, with its validated raw arguments and stream) and every later step is O
 call that re-issues the same launches on the same two streams from C++. The executor's Python
 (~8 us of host time per launch) then runs once instead of every step; at small batch the host no
 longer falls behind the GPU. Requirements, all true of the training step: static buffers, no
-host-side decisions that change between steps, a constant learning rate and the same current stream
-at every call. ``RDP_PLAN=0`` disables it. Under DDP the bucket all-reduces (and ``finish``'s waits / bf16 widening)
+host-side decisions that change between steps, a constant base learning rate (a warmup / cosine
+schedule's per-step factor and the gradient-clip coefficient are formed on the device, train/schedule.py,
+so they keep the one plan) and the same current stream at every call. ``RDP_PLAN=0`` disables it.
+Under DDP the bucket all-reduces (and ``finish``'s waits / bf16 widening)
 are torch.distributed calls the runtime cannot replay: each is recorded as a host call point of the
 plan (``plan_mark``), run with recording paused, and replay calls back into Python at that point, so
 every collective keeps its place between the recorded kernels. Measured (one MI355X, interleaved): host enqueue per bs-4
@@ -48,6 +50,7 @@ from ..models.unet_ref import UNetRef
 from ..parallel.ddp import FlatBucketer, broadcast_module_state, dist_info, emulate_spec, native_comm_group
 from ..utils import trace
 from .losses import ce_dice_reference, check_class_weights
+from .schedule import OptimOptions
 
 
 class NativeTrainer:
@@ -57,11 +60,18 @@ class NativeTrainer:
 
     def __init__(self, model: UNetNative, batch: int, h: int, w: int, lr: float = 1e-4, loss: str = "bce",
                  dice_weight: float = 1.0, graph="auto", bucket_mb: float = 16.0, sync_bn: bool = False,
-                 grad_comm: Optional[str] = None, ddp_force: Optional[bool] = None, plan="auto", class_weights=None):
+                 grad_comm: Optional[str] = None, ddp_force: Optional[bool] = None, plan="auto", class_weights=None,
+                 clip_grad_norm: float = 0.0, lr_schedule: str = "constant", warmup_steps: int = 0,
+                 total_steps: Optional[int] = None, min_lr_ratio: float = 0.0):
+        """``clip_grad_norm`` / ``lr_schedule`` / ``warmup_steps`` / ``total_steps`` / ``min_lr_ratio``
+        (train/schedule.py; all off by default) go to the trainer's :class:`NativeAdam`: the clip coefficient
+        and the rate multiplier are formed on the device inside the step, so eager, plan and hipGraph steps
+        and DDP all take them, and a schedule keeps the one recorded plan."""
         self.model = model
         self.ex = model.executor(batch, h, w, training=True, loss=loss, dice_weight=dice_weight,
                                  class_weights=class_weights)
-        self.opt = NativeAdam(model, lr=lr)
+        self.opt = NativeAdam(model, lr=lr, clip_grad_norm=clip_grad_norm, lr_schedule=lr_schedule,
+                              warmup_steps=warmup_steps, total_steps=total_steps, min_lr_ratio=min_lr_ratio)
         self.rank, self.world = dist_info()
         self.bucketer = None
         self.watchdog = None
@@ -264,8 +274,10 @@ class NativeTrainer:
             C = native(build_if_missing=False)
             version = (self.model.__dict__.get("_layout_version"), self.opt.hyper_key())
             if self.plan_id is not None and self._plan_version != version:
-                # buffers re-laid out or optimizer hyper-parameters changed (lr schedule, Adam
-                # load_state_dict): the recorded launches bake those in, so record again
+                # buffers re-laid out or optimizer hyper-parameters changed (a new base lr, Adam
+                # load_state_dict): the recorded launches bake those in, so record again. A warmup /
+                # cosine schedule or gradient clipping does NOT come here: their per-step values are
+                # formed on the device (NativeAdam options), and the options are constants of the key
                 C.plan_free(self.plan_id)
                 self.plan_id = None
             if self.plan_id is not None:
@@ -336,9 +348,17 @@ class EagerTrainer:
     """Plain-torch trainer (reference execution model) with the same flat-bucket DDP."""
 
     def __init__(self, model: nn.Module, lr: float = 1e-4, loss: str = "bce", dice_weight: float = 1.0,
-                 bucket_mb: float = 16.0, amp: Optional[torch.dtype] = None, class_weights=None):
+                 bucket_mb: float = 16.0, amp: Optional[torch.dtype] = None, class_weights=None,
+                 clip_grad_norm: float = 0.0, lr_schedule: str = "constant", warmup_steps: int = 0,
+                 total_steps: Optional[int] = None, min_lr_ratio: float = 0.0):
         self.model = model
         self.opt = torch.optim.Adam(model.parameters(), lr=lr)
+        # gradient clipping / learning-rate schedule (train/schedule.py; off by default: the step is then
+        # exactly the reference's). ``last_lr`` / ``last_grad_norm``: the last step's, for per-epoch logging
+        self.base_lr = lr
+        self.options = OptimOptions(clip_grad_norm, lr_schedule, warmup_steps, total_steps, min_lr_ratio)
+        self.last_lr: Optional[float] = None
+        self.last_grad_norm: Optional[torch.Tensor] = None
         self.loss_kind, self.dice_w = loss, dice_weight
         if loss not in ("ce", "ce_dice") and class_weights is not None:
             raise ValueError('class_weights need a K-class loss ("ce" / "ce_dice")')
@@ -393,8 +413,23 @@ class EagerTrainer:
         if self.bucketer is not None:
             self.bucketer.finish()
             self.flat_grad /= self.world
+        if self.options.enabled:
+            if self.options.clip_grad_norm > 0:  # the pre-clip total norm stays on the device
+                self.last_grad_norm = torch.nn.utils.clip_grad_norm_(list(self.model.parameters()),
+                                                                     self.options.clip_grad_norm)
+            self.last_lr = self.base_lr * self.options.multiplier(self.completed_steps())
+            for group in self.opt.param_groups:
+                group["lr"] = self.last_lr
         self.opt.step()
         return loss.detach()
+
+    def completed_steps(self) -> int:
+        """Completed optimizer updates, from the optimizer's own state (so a resumed run, after
+        ``opt.load_state_dict``, continues the schedule with nothing extra in the checkpoint)."""
+        for st in self.opt.state.values():
+            if "step" in st:
+                return int(st["step"])
+        return 0
 
 
 def build_bench_step(batch: int, size: int, decoder: str, device: torch.device, world: int, graph: bool,

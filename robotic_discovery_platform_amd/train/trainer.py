@@ -19,6 +19,9 @@ contrast / brightness jitter, fused into the batch gather on the native backend 
 K-class training (``n_classes`` 2..8; the reference is binary): UNet(3, K), softmax cross-entropy over
 integer class ids (255 = ignore). ``val_metrics``: per-epoch IoU / Dice / pixel accuracy from confusion
 counts accumulated on the device (train/metrics.py, csrc/seg_metrics.hip). Both are off by default.
+``clip_grad_norm`` / ``lr_schedule`` / ``warmup_steps`` / ``min_lr_ratio`` (off by default; the reference has
+neither): gradient-norm clipping and a warmup / cosine learning-rate schedule over the run's steps, on both
+backends (train/schedule.py); ``lr`` and ``grad_norm`` of each epoch's last step are then logged.
 """
 from __future__ import annotations
 
@@ -40,6 +43,7 @@ from ..data.synthetic import write_dataset
 from ..models.unet_ref import UNetRef
 from ..parallel.ddp import DistributedShardSampler, dist_info
 from .losses import check_class_weights, parse_class_weights
+from .schedule import OptimOptions
 
 log = logging.getLogger("rdp.train")
 
@@ -93,21 +97,25 @@ def native_eval_batch(model, x, y, loss: str, dice_weight: float = 1.0, confusio
 class _NativeRunner:
     """Per-batch-shape native executors (+ hipGraphs) over one model / one Adam state."""
 
-    def __init__(self, model, cfg: TrainConfig):
+    def __init__(self, model, cfg: TrainConfig, options: Optional[OptimOptions] = None):
         from ..models.unet import NativeAdam
         from .engine import NativeTrainer
         self.model, self.cfg = model, cfg
         self.class_weights = parse_class_weights(cfg.class_weights)
         self._trainers = {}
         self._cls = NativeTrainer
-        self._shared_opt = NativeAdam(model, lr=cfg.learning_rate)
+        # one Adam (state, step counter, clip / schedule options) for every batch shape: a ragged last
+        # batch's trainer follows the same device step counter, hence the same schedule
+        self._opt_kw = _optim_kwargs(options)
+        self._shared_opt = NativeAdam(model, lr=cfg.learning_rate, **self._opt_kw)
 
     def _get(self, n, h, w):
         key = (n, h, w)
         if key not in self._trainers:
             tr = self._cls(self.model, n, h, w, lr=self.cfg.learning_rate, loss=self.cfg.loss,
                            dice_weight=self.cfg.dice_weight, graph=self.cfg.graph, bucket_mb=self.cfg.grad_bucket_mb,
-                           sync_bn=self.cfg.sync_bn, grad_comm=self.cfg.grad_comm, class_weights=self.class_weights)
+                           sync_bn=self.cfg.sync_bn, grad_comm=self.cfg.grad_comm, class_weights=self.class_weights,
+                           **self._opt_kw)
             tr.opt = self._shared_opt
             self._trainers[key] = tr
         return self._trainers[key]
@@ -134,14 +142,28 @@ class _NativeRunner:
     def load_optimizer_state(self, sd):
         self._shared_opt.load_state_dict(sd)
 
+    def last_optim(self):
+        """(lr, grad_norm or None) of the last step: one host read of the device scalars, per epoch."""
+        ctl = self._shared_opt.last_ctl()
+        clip = self._shared_opt.options.clip_grad_norm > 0
+        return self._shared_opt.lr * ctl["mult"], (ctl["norm"] if clip else None)
+
+
+def _optim_kwargs(options: Optional[OptimOptions]) -> dict:
+    if options is None:
+        return {}
+    return {"clip_grad_norm": options.clip_grad_norm, "lr_schedule": options.lr_schedule,
+            "warmup_steps": options.warmup_steps, "total_steps": options.total_steps,
+            "min_lr_ratio": options.min_lr_ratio}
+
 
 class _EagerRunner:
-    def __init__(self, model, cfg: TrainConfig, dev):
+    def __init__(self, model, cfg: TrainConfig, dev, options: Optional[OptimOptions] = None):
         from .engine import EagerTrainer
         amp = torch.bfloat16 if (dev.type == "cuda" and cfg.dtype == "bf16") else None
         self.tr = EagerTrainer(model, lr=cfg.learning_rate, loss=cfg.loss, dice_weight=cfg.dice_weight,
                                bucket_mb=cfg.grad_bucket_mb, amp=amp,
-                               class_weights=parse_class_weights(cfg.class_weights))
+                               class_weights=parse_class_weights(cfg.class_weights), **_optim_kwargs(options))
         self.model = model
 
     def train_step(self, x, y):
@@ -161,6 +183,10 @@ class _EagerRunner:
 
     def load_optimizer_state(self, sd):
         self.tr.opt.load_state_dict(sd)
+
+    def last_optim(self):
+        gn = self.tr.last_grad_norm
+        return self.tr.last_lr, (float(gn.item()) if gn is not None else None)
 
 
 def _batches(x: torch.Tensor, y: torch.Tensor, order, bs: int, dev, n_classes: int = 1):
@@ -244,17 +270,29 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
              "device-resident u8" if device_data else "host")
     sampler = DistributedShardSampler(len(train_set), rank, world, shuffle=True, seed=cfg.seed)
 
+    # gradient clipping / learning-rate schedule (off by default: nothing below changes then). The schedule
+    # spans the whole run: epochs x this rank's steps per epoch, the same total when the run is resumed.
+    steps_per_epoch = (len(sampler) + cfg.batch_size - 1) // cfg.batch_size
+    options = OptimOptions(cfg.clip_grad_norm, cfg.lr_schedule, cfg.warmup_steps, cfg.epochs * steps_per_epoch,
+                           cfg.min_lr_ratio)
+    if not options.enabled:
+        options = None
+    elif is_main:
+        mlstore.log_params({"clip_grad_norm": options.clip_grad_norm, "lr_schedule": options.lr_schedule,
+                            "warmup_steps": options.warmup_steps, "min_lr_ratio": options.min_lr_ratio,
+                            "total_steps": options.total_steps})
+
     # ---- model / engine ----
     ref = UNetRef(3, K, bilinear=cfg.bilinear, depth=cfg.model_depth)
     if backend == "native":
         from ..models.unet import UNetNative
         model = UNetNative(3, K, bilinear=cfg.bilinear, depth=cfg.model_depth, device=dev, init_from=ref)
-        runner = _NativeRunner(model, cfg)
+        runner = _NativeRunner(model, cfg, options)
     else:
         model = ref.to(dev)
         if cfg.sync_bn and dev.type == "cuda" and dist_info()[1] > 1:  # torch's SyncBatchNorm is GPU-only
             model = torch.nn.SyncBatchNorm.convert_sync_batchnorm(model)
-        runner = _EagerRunner(model, cfg, dev)
+        runner = _EagerRunner(model, cfg, dev, options)
 
     # validation metrics (off by default: nothing below changes then): the epoch's confusion counts, added
     # up on the device by seg_confusion after each eval forward (native) or by the torch reference (eager)
@@ -345,6 +383,16 @@ def train_model(cfg: Optional[TrainConfig] = None, resume: Optional[str] = None)
                         "train_s": t_train, "train_imgs_per_s": len(order) * world / max(t_train, 1e-9)})
         if vm is not None:
             history[-1].update(val_metrics=vm, val_confusion=confusion_matrix(counts, K))
+        if options is not None and nb:
+            # the epoch's last step: the rate it used and (clipping on) its pre-clip gradient norm
+            lr_last, gnorm_last = runner.last_optim()
+            history[-1]["lr"] = lr_last
+            if gnorm_last is not None:
+                history[-1]["grad_norm"] = gnorm_last
+            if is_main:
+                mlstore.log_metric("lr", lr_last, step=epoch)
+                if gnorm_last is not None:
+                    mlstore.log_metric("grad_norm", gnorm_last, step=epoch)
         if is_main:
             mlstore.log_metric("train_loss", avg_train, step=epoch)
             mlstore.log_metric("val_loss", avg_val, step=epoch)
