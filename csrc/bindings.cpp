@@ -1291,6 +1291,28 @@ void headk_mask(torch::Tensor a, torch::Tensor w, torch::Tensor b, int cls, torc
                                       (int)M, K, st)) == 0, "headk_mask");
 }
 
+// conv_head_mask with the K-class head (head_w [K*64], head_b [K], 2 <= K <= 8): mask = (arg-max class == cls, ties to
+// the lowest class), bit for bit conv_fwd + headk_mask; returns false (nothing launched) where the ring kernel
+// does not apply
+bool conv_headk_mask(torch::Tensor x, torch::Tensor w, torch::Tensor coef, torch::Tensor hw, torch::Tensor hb, int cls,
+                     torch::Tensor mask) {
+  Act a = act(x, "x");
+  check_w(w);
+  check_f32(coef, "coef");
+  const int K = headk_classes(hw, hb, "conv_headk_mask");
+  TORCH_CHECK(coef.numel() >= 4l * w.size(0), "coef size");
+  TORCH_CHECK(cls >= 0 && cls < K, "conv_headk_mask: class ", cls, " outside 0..", K - 1);
+  const long M = (long)a.N * a.H * a.W;
+  TORCH_CHECK(M > 0 && M < (1L << 31), "conv_headk_mask: pixel count");
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kUInt8 && mask.is_contiguous() && mask.numel() >= M,
+              "mask: u8 [N*H*W]");
+  const int Co = (int)w.size(0);
+  const int r = RDP_PLAN(rdp_conv_ring_headk(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, w.size(1), Co, a.N,
+                                             a.H, a.W, coef.data_ptr<float>() + 2 * Co, coef.data_ptr<float>() + 3 * Co,
+                                             hw.data_ptr<float>(), hb.data_ptr<float>(), K, cls, mask.data_ptr(), st));
+  return r == 0;
+}
+
 // ---- validation metrics (csrc/seg_metrics.hip) ----
 int seg_confusion_blocks(long M) { return rdp_seg_confusion_blocks(M); }
 int seg_confusion_block_pixels() { return rdp_seg_confusion_block_pixels(); }
@@ -2083,6 +2105,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("seg_confusion", on_device(&seg_confusion), py::arg("logits"), py::arg("target"), py::arg("K"),
         py::arg("counts"), py::arg("thr") = 0.0, py::arg("max_blocks") = 0);
   m.def("conv_head_mask", on_device(&conv_head_mask));
+  m.def("conv_headk_mask", on_device(&conv_headk_mask), py::arg("x"), py::arg("w"), py::arg("coef"), py::arg("head_w"),
+        py::arg("head_b"), py::arg("cls"), py::arg("mask"));
   m.def("conv_rowband_chain", on_device(&conv_rowband_chain));
   m.def("conv_rowband", on_device(&conv_rowband));
   // host-only: the eval conv's row-band mode for a shape (0 = implicit GEMM), the same decision conv_fwd takes

@@ -20,6 +20,7 @@
 // holds another column's row there: the zero padding row of this one). Epilogue: bf16 store (permlane16-widened, 16 B
 // per lane), optional training BN statistics (per-block partial rows) or eval BN fold + ReLU.
 #include "common.h"
+#include "head_multi_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
@@ -52,6 +53,8 @@ struct RingArgs {
   const float* hb;
   float hthr;
   uint8_t* hmask;
+  // K-class serving head (HK variant): hw [K][64], hb [K]; hmask[m] = (argmax_k(a[m] . hw[k] + hb[k]) == hcls)
+  int hcls;
   // eval MaxPool2d(2) of the output (POOL variant): pool [N][H/2][W/2][64] with pixel pitch ppitch
   u16* pool;
   int ppitch;
@@ -81,6 +84,13 @@ RDP_DEV uint32_t rdiv(uint32_t n, uint32_t m, uint32_t s) { return (__umulhi(n, 
 // each reduces its 32 over the lane groups, cg = 1 leaves its partial in LDS (double-buffered by step
 // parity), and cg = 0 finishes the pixel after the next step's barrier (the last step after a final
 // barrier) and stores the u8 mask.
+// HK = K (COUT = 64, eval, 2 <= K <= 8): the K-class serving head, mask = (arg-max class == hcls), bit for bit
+// what headk_mask_kernel (head_multi.hip) writes from the stored activation. The accumulator layout is not
+// the 8 contiguous channels a headk_mask lane sums, so the step's bf16 activations (the very values the plain
+// epilogue stores) go to an LDS tile [128 px][64 ch] (16-B chunks XOR-swizzled by the pixel, double-buffered by
+// step parity) instead of memory; after the next step's barrier (the last step after a final barrier) all 512
+// threads read it back in headk_mask's layout -- 8 lanes per pixel, 64 pixels per pass, one pass per output
+// row -- and run the shared head code (head_multi_dev.h) with the [K][64] head weights kept in LDS.
 // POOL (COUT = 64, eval): MaxPool2d(2) of the output in the epilogue. A step's two output rows are
 // one row of 2x2 windows (rows 2P, 2P + 1 with H even): horizontal pairs are neighbouring lanes (DPP
 // swap), vertical pairs are the orow = 0 / 1 waves of a pixel group, exchanged through LDS (step-parity
@@ -92,7 +102,7 @@ RDP_DEV uint32_t rdiv(uint32_t n, uint32_t m, uint32_t s) { return (__umulhi(n, 
 // (padding chunks stay zero: the conv pads the post-ReLU activation). With aout, the interior chunks of
 // the rows the block owns (2 P0 .. 2 (P0 + nks) - 1) are also stored there; every staged chunk issues
 // its store (the others at an out-of-range offset) so the per-wave vmcnt counts below stay fixed.
-template <int COUT, bool BNR = false, bool HEAD = false, bool POOL = false, bool BNIN = false>
+template <int COUT, bool BNR = false, bool HEAD = false, bool POOL = false, bool BNIN = false, int HK = 0>
 __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
   constexpr int NCG = COUT / 32, NPG = 8 / NCG;  // waves per channel group / per pixel group
   constexpr int PXW = 128 / NPG, NI = PXW / 16;  // pixels per wave (one output row half or whole)
@@ -103,10 +113,14 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
   constexpr int HPART = HEAD ? 2 * NPG * PXW * 4 : 0;  // head partials [parity][pixel group][pixel]
   // pool halves [parity][wave][i][pixel pair][lane group] x 16 B (4 packed bf16 pairs)
   constexpr int PPART = POOL ? 2 * 8 * NI * 8 * 4 * 16 : 0;
-  __shared__ __attribute__((aligned(16))) char ring[(NX + 1) * XREG + 4 * COUT * 4 + HPART + PPART];  // + zero slot, BN fold / BN-bwd coefs
+  constexpr int HTILE = HK ? 2 * 128 * 128 : 0;     // K-class head: activation tiles [parity][128 px][64 ch] bf16
+  constexpr int HKW = HK ? (HK * 64 + 8) * 4 : 0;   // and the head weights [K][64] + bias [8] (fp32)
+  __shared__ __attribute__((aligned(16))) char ring[(NX + 1) * XREG + 4 * COUT * 4 + HPART + PPART + HTILE + HKW];  // + zero slot, BN fold / BN-bwd coefs
   float* const efold = (float*)(ring + (NX + 1) * XREG);  // eval BN fold [scale | shift] (LDS, not VGPRs)
   float* const hpart = (float*)(ring + (NX + 1) * XREG + 4 * COUT * 4);
   uint4* const ppart = (uint4*)(ring + (NX + 1) * XREG + 4 * COUT * 4 + HPART);
+  char* const htile = ring + (NX + 1) * XREG + 4 * COUT * 4 + HPART + PPART;
+  float* const hkw = (float*)(htile + HTILE);
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -202,6 +216,9 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
   }
   if constexpr (BNR) {
     for (int c = threadIdx.x; c < 4 * COUT; c += 512) efold[c] = a.bncoef[c];
+  }
+  if constexpr (HK > 0) {  // visible after the first step's barrier, long before the first finish
+    for (int c = threadIdx.x; c < HK * 64 + 8; c += 512) hkw[c] = c < HK * 64 ? a.hw[c] : (c - HK * 64 < HK ? a.hb[c - HK * 64] : 0.f);
   }
   if constexpr (BNIN) {  // input BN [scale | shift] (64 input channels), visible before the first transform
     for (int c = threadIdx.x; c < 64; c += 512) { efold[c] = a.iscale[c]; efold[64 + c] = a.ishift[c]; }
@@ -321,16 +338,51 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
     }
   };
 
+  // K-class head: all threads finish the step P = hk_prev whose activation tile (parity par) is in LDS:
+  // pass q = output row 2 P + q, pixel threadIdx.x >> 3 of its 64, channels 8 sub .. 8 sub + 7
+  int hk_prev = -1;
+  auto headk_finish = [&](int par) {
+    if constexpr (HK > 0) {
+      if (hk_prev < 0) return;
+      constexpr int KP = rdp_headk::pow2_classes(HK);
+      const int sub = lane & 7, kk = sub & (KP - 1);
+      const int px = threadIdx.x >> 3;
+      // class by class, the weights from LDS: K x 8 weights per lane at once do not fit beside the conv's
+      // 144 weight registers (the scheduling barriers keep the compiler from gathering the reads up front)
+      const float bias = kk < HK ? hkw[HK * 64 + kk] : 0.f;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int t = q * 64 + px;
+        float f[8], d[KP];
+        rdp_headk::unpack8h(*(const uint4*)(htile + par * (128 * 128) + t * 128 + 16 * (sub ^ (t & 7))), f);
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          d[k] = 0.f;
+          if (k < HK) {
+            const float4 w0 = *(const float4*)(hkw + k * 64 + sub * 8), w1 = *(const float4*)(hkw + k * 64 + sub * 8 + 4);
+            const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+            d[k] = rdp_headk::class_dot(f, w);
+            if (k & 1) __builtin_amdgcn_sched_barrier(0);  // two classes' reads in flight at a time
+          }
+        }
+        const int idx = rdp_headk::argmax_lowest<HK>(rdp_headk::reduce_transpose<KP>(d, sub) + bias, sub);
+        int hm0, hw0;
+        row_base(2 * hk_prev + q, hm0, hw0);
+        if (sub == 0) a.hmask[hm0 + px] = idx == a.hcls ? 1 : 0;
+      }
+    }
+  };
+
   for (int ks = 0; ks < nks; ++ks) {
     const int P = P0 + ks;
     // Stage P must have landed. vmcnt also counts the NI output stores every wave issues at the end
     // of a step, in issue order: younger than stage P are the stores of steps ks-2 and ks-1 and
     // (unless this is the last step) stage P+1 -- leave exactly those in flight.
-    // (HEAD: no activation stores; the mask stores of cg = 0 are not counted, which only makes the
-    // wait stricter)
+    // (HEAD / HK: no activation stores; the mask stores are not counted, which only makes the wait
+    // stricter)
     // BNIN: also the activation stores of step ks - 1's transform, younger than stage P's DMAs: at
     // least AS per wave per stage (2 or 3 pieces) and AS0 at step 0 (+ the 1-2 pieces of each prologue row)
-    constexpr int NS = HEAD ? 0 : NI;  // counted output stores per step
+    constexpr int NS = (HEAD || HK > 0) ? 0 : NI;  // counted output stores per step
     constexpr int AS = BNIN ? 2 : 0, AS0 = BNIN ? 4 : 0;
     if (ks + 1 < nks) {
       if (ks >= 2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(MINPW + 2 * NS + AS) : "memory");
@@ -351,6 +403,7 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
     }
     raw_barrier();
     if constexpr (HEAD) head_finish((ks - 1) & 1);
+    if constexpr (HK > 0) headk_finish((ks - 1) & 1);
     if constexpr (POOL) pool_finish((ks - 1) & 1);
     // BN-backward fusion: the owner layer's pre-BN activations at this step's outputs, loaded before
     // the stage P + 2 DMAs so their latency hides under the taps. (hipcc cannot see the DMAs, so its
@@ -488,7 +541,7 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
         }
         v[j].x = pack2bf(o[0], o[1]);
         v[j].y = pack2bf(o[2], o[3]);
-        if (a.stats) {
+        if (HK == 0 && a.stats) {
           const float q0 = __uint_as_float(v[j].x << 16), q1 = __uint_as_float(v[j].x & 0xffff0000u);
           const float q2 = __uint_as_float(v[j].y << 16), q3 = __uint_as_float(v[j].y & 0xffff0000u);
           if constexpr (BNR) {
@@ -526,15 +579,27 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
       }
       const auto rxs = __builtin_amdgcn_permlane16_swap(v[0].x, v[1].x, false, false);
       const auto rys = __builtin_amdgcn_permlane16_swap(v[0].y, v[1].y, false, false);
+      if constexpr (HK > 0) {  // the 16 B the plain epilogue stores at channel 32 cg + coff, into the LDS tile
+        const int t = 64 * orow + px0 + 16 * i + (lane & 15);
+        *(uint4*)(htile + (ks & 1) * (128 * 128) + t * 128 + 16 * ((4 * cg + (coff >> 3)) ^ (t & 7))) =
+            make_uint4(rxs[0], rys[0], rxs[1], rys[1]);
+        continue;
+      }
       const int m = m0 + px0 + 16 * i + (lane & 15);
       const uint32_t off = (uint32_t)(m * ypitch + cbase + coff) * 2u;
       bstore16(ry, off, make_uint4(rxs[0], rys[0], rxs[1], rys[1]));
     }
+    if constexpr (HK > 0) hk_prev = P;
   }
 
   if constexpr (HEAD) {
     __syncthreads();
     head_finish((nks - 1) & 1);
+    return;
+  }
+  if constexpr (HK > 0) {
+    __syncthreads();
+    headk_finish((nks - 1) & 1);
     return;
   }
   if constexpr (POOL) {
@@ -579,7 +644,7 @@ extern "C" int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, 
   a.y = nullptr; a.ybytes = 0; a.ypitch = 64; a.y2 = nullptr; a.ybytes2 = 0; a.ypitch2 = 64; a.Cy1 = 64;
   a.stats = nullptr; a.escale = escale; a.eshift = eshift; a.erelu = 1;
   a.bny = nullptr; a.bnypitch = 0; a.bncoef = nullptr;
-  a.hw = hw; a.hb = hb; a.hthr = hthr; a.hmask = (uint8_t*)mask;
+  a.hw = hw; a.hb = hb; a.hthr = hthr; a.hmask = (uint8_t*)mask; a.hcls = 0;
   a.pool = nullptr; a.ppitch = 0;
   a.iscale = nullptr; a.ishift = nullptr;
   a.aout = nullptr; a.abytes = 0; a.apitch = 0;
@@ -595,6 +660,49 @@ extern "C" int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, 
   return 0;
 }
 
+template <int K>
+static void launch_ring_headk(int grid, hipStream_t s, const RingArgs& a) {
+  hipLaunchKernelGGL((conv_ring_kernel<64, false, false, false, false, K>), dim3(grid), dim3(512), 0, s, a);
+}
+
+extern "C" int rdp_conv_ring_headk(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
+                                   int Cout, int N, int H, int W, const float* escale, const float* eshift,
+                                   const float* hw, const float* hb, int K, int cls, void* mask, hipStream_t s) {
+  if (C != 64 || Cout != 64 || W % 64 || H % 2 || ldw < 576 || !escale || !eshift || !hw || !hb || !mask) return -1;
+  if (xbytes >= (1l << 31) || wbytes >= (1l << 31)) return -1;
+  // (a channel-sliced view of a wider tensor, pitch != 64, keeps the separate launches)
+  if (pitch != 64 || K < 2 || K > 8 || cls < 0 || cls >= K || N <= 0 || H <= 0 || (long)N * H * W >= (1l << 31))
+    return -1;
+  RingArgs a;
+  a.x = (const u16*)x; a.xbytes = (uint32_t)xbytes; a.pitch = pitch;
+  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
+  a.y = nullptr; a.ybytes = 0; a.ypitch = 64; a.y2 = nullptr; a.ybytes2 = 0; a.ypitch2 = 64; a.Cy1 = 64;
+  a.stats = nullptr; a.escale = escale; a.eshift = eshift; a.erelu = 1;
+  a.bny = nullptr; a.bnypitch = 0; a.bncoef = nullptr;
+  a.hw = hw; a.hb = hb; a.hthr = 0.f; a.hmask = (uint8_t*)mask; a.hcls = cls;
+  a.pool = nullptr; a.ppitch = 0;
+  a.iscale = nullptr; a.ishift = nullptr;
+  a.aout = nullptr; a.abytes = 0; a.apitch = 0;
+  a.H = H; a.W = W; a.WS = W / 64;
+  a.nrows = N * a.WS * H;
+  a.npairs = a.nrows / 2;
+  const int blocks = std::max(1, std::min(256, a.npairs));
+  a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
+  const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
+  const FastDiv fh = make_fastdiv((uint32_t)H), fs = make_fastdiv((uint32_t)a.WS);
+  a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
+  switch (K) {
+    case 2: launch_ring_headk<2>(grid, s, a); break;
+    case 3: launch_ring_headk<3>(grid, s, a); break;
+    case 4: launch_ring_headk<4>(grid, s, a); break;
+    case 5: launch_ring_headk<5>(grid, s, a); break;
+    case 6: launch_ring_headk<6>(grid, s, a); break;
+    case 7: launch_ring_headk<7>(grid, s, a); break;
+    default: launch_ring_headk<8>(grid, s, a); break;
+  }
+  return 0;
+}
+
 extern "C" int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipStream_t s) {
   if (c.C1 != 64 || c.Cout != 64 || c.W % 64 || c.H % 2 || c.ldw < 576 || !c.escale || !c.eshift || !pool ||
       ppitch % 4)
@@ -607,7 +715,7 @@ extern "C" int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipS
   a.y2 = (u16*)c.y1; a.ybytes2 = 0; a.ypitch2 = c.ypitch1; a.Cy1 = 64;
   a.stats = nullptr; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
   a.bny = nullptr; a.bnypitch = 0; a.bncoef = nullptr;
-  a.hw = nullptr; a.hb = nullptr; a.hthr = 0.f; a.hmask = nullptr;
+  a.hw = nullptr; a.hb = nullptr; a.hthr = 0.f; a.hmask = nullptr; a.hcls = 0;
   a.pool = (u16*)pool; a.ppitch = ppitch;
   a.iscale = nullptr; a.ishift = nullptr;
   a.aout = nullptr; a.abytes = 0; a.apitch = 0;
@@ -641,7 +749,7 @@ extern "C" int rdp_conv_ring_ex(const RdpConv& c, int max_blocks, const RdpRingF
   a.Cy1 = c.Cy1;
   a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
   a.bny = bn_y; a.bnypitch = f.bn_ypitch; a.bncoef = f.bn_coef;
-  a.hw = nullptr; a.hb = nullptr; a.hthr = 0.f; a.hmask = nullptr;
+  a.hw = nullptr; a.hb = nullptr; a.hthr = 0.f; a.hmask = nullptr; a.hcls = 0;
   a.pool = nullptr; a.ppitch = 0;
   a.iscale = f.iscale; a.ishift = f.ishift;
   a.aout = (u16*)f.aout; a.abytes = (uint32_t)f.abytes; a.apitch = f.apitch;

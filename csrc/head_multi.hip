@@ -37,6 +37,7 @@
 // steps (KP = K rounded up to a power of two) lane `sub` owns logit `sub & (KP - 1)` -- 7 shuffles
 // at K = 8 where K separate butterflies would take 24.
 #include "common.h"
+#include "head_multi_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
 
@@ -45,53 +46,9 @@
 
 namespace {
 
-RDP_DEV void unpack8h(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
-
-constexpr int pow2_classes(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : 8; }
-
-// v[k] = this lane's partial of logit k (0 for the padding k >= K). Returns the full sum over the
-// pixel's 8 lanes of logit (sub & (KP - 1)).
-template <int KP>
-RDP_DEV float reduce_transpose(float (&v)[KP], int sub) {
-#pragma unroll
-  for (int h = KP / 2; h >= 1; h >>= 1) {
-    const bool up = (sub & h) != 0;
-#pragma unroll
-    for (int j = 0; j < h; ++j) {
-      const float send = up ? v[j] : v[j + h];
-      const float keep = up ? v[j + h] : v[j];
-      v[j] = keep + __shfl_xor(send, h, 64);
-    }
-  }
-  float r = v[0];
-#pragma unroll
-  for (int o = KP; o < 8; o <<= 1) r += __shfl_xor(r, o, 64);
-  return r;
-}
-
-// the logit this lane owns for the pixel whose 8 channels it holds in `f` (bias not added)
-template <int K>
-RDP_DEV float lane_logit(const float* f, const float (&wl)[K][8], int sub) {
-  constexpr int KP = pow2_classes(K);
-  float d[KP];
-#pragma unroll
-  for (int k = 0; k < KP; ++k) {
-    float s = 0.f;
-    if (k < K) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s = fmaf(f[j], wl[k][j], s);
-    }
-    d[k] = s;
-  }
-  return reduce_transpose<KP>(d, sub);
-}
+// unpack8h, pow2_classes, reduce_transpose, lane_logit, argmax_lowest: shared with the row-ring conv's fused
+// K-class head, which must reproduce headk_mask_kernel's bits (head_multi_dev.h)
+using namespace rdp_headk;
 
 // EXT: `cw` = class weights (null: all 1); partial rows of 2 + 3K floats instead of 2
 template <int K, bool EXT>
@@ -435,15 +392,7 @@ __global__ __launch_bounds__(256) void headk_mask_kernel(const u16* __restrict__
     const uint4 v = *(const uint4*)(a + (size_t)p * apitch + sub * 8);
     float f[8];
     unpack8h(v, f);
-    float x = lane_logit<K>(f, wl, sub) + bias;
-    if (!own) x = -INFINITY;
-    int idx = kk;
-#pragma unroll
-    for (int o = 1; o < KP; o <<= 1) {
-      const float ox = __shfl_xor(x, o, 64);
-      const int oi = __shfl_xor(idx, o, 64);
-      if (ox > x || (ox == x && oi < idx)) { x = ox; idx = oi; }
-    }
+    const int idx = argmax_lowest<K>(lane_logit<K>(f, wl, sub) + bias, sub);
     if (sub == 0) mask[p] = idx == cls ? 1 : 0;
   }
 }

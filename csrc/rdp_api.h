@@ -124,6 +124,13 @@ int rdp_conv_ring_ex(const RdpConv& c, int max_blocks, const RdpRingFuse& f, hip
 int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw, int Cout,
                        int N, int H, int W, const float* escale, const float* eshift, const float* hw,
                        const float* hb, float hthr, void* mask, hipStream_t s);
+// The same conv fused with the K-class serving head (hw [K*64], hb [K], 2 <= K <= 8): writes only the u8 mask
+// (arg-max class == cls, ties to the lowest class), bit for bit the mask rdp_headk_mask writes from the stored
+// output. Returns 0, or -1 (nothing launched) where the ring kernel does not apply, the input is a strided view
+// (pitch != 64) or K / cls are out of range.
+int rdp_conv_ring_headk(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw, int Cout,
+                        int N, int H, int W, const float* escale, const float* eshift, const float* hw,
+                        const float* hb, int K, int cls, void* mask, hipStream_t s);
 // Eval conv (64 -> 64, BN folded + ReLU) that also writes MaxPool2d(2) of its output into pool
 // [N][H/2][W/2][64] (pixel pitch ppitch). Returns 0, or -1 when the ring kernel does not apply.
 int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipStream_t s);

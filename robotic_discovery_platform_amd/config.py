@@ -122,6 +122,10 @@ class ServeConfig:
     # and into the response (class 0 is background by convention). Ignored by a one-class model.
     # RDP_SERVE_MASK_CLASS overrides.
     mask_class: int = 1
+    # K-class models: batch concurrent streams into one device program (serve/engine.py BatchEngine), as one-class
+    # models always are. Off until the 4-stream gain is settled for K classes (profiles/serve_multiclass.md).
+    # RDP_SERVE_BATCH_MULTICLASS overrides.
+    batch_multiclass: bool = False
     backend: str = "auto"
     graph: bool = True
     devices: str = ""  # comma-separated GPU indices for per-GPU replicas ("" = current device only; "all")

@@ -567,6 +567,7 @@ class UNetExecutor:
         # ``final``, headk_bwd writes the last layer's da and the ordinary BN backward passes follow.
         self.K = model.n_classes
         self.fuse_head = training and self.K == 1
+        self._mask_head_fused = False
         C = _native()
         D = model.depth
         bf = torch.bfloat16
@@ -891,6 +892,12 @@ class UNetExecutor:
         c2 = L.x2.shape[3] if L.x2 is not None else 0
         return C.rowband_frag_mode(n, h, w, c1, c2, sp.cout) > 0
 
+    @property
+    def mask_head_fused(self) -> bool:
+        """Whether the last ``forward`` formed its ``mask_head`` mask in the last conv's launch (the row-ring
+        fused head) rather than by a separate ``head_mask`` / ``headk_mask`` launch on ``final``."""
+        return self._mask_head_fused
+
     def forward(self, head: bool = True, refresh_eval: bool = True, mask_head: Optional[tuple] = None):
         """Run the network; ``head=False`` stops after up4 (serving applies ``head_mask`` instead).
 
@@ -901,9 +908,13 @@ class UNetExecutor:
         ``head(a_final) > logit_thr``; where the row-ring kernel runs the last conv, the head is fused
         into its epilogue and ``final`` is not materialised (elsewhere the separate ``head_mask`` launch).
         K-class model: ``mask_head=(head_w [K*64], head_b [K], cls, mask_u8)``, the mask of the pixels
-        whose arg-max class is ``cls``; always the separate ``headk_mask`` launch."""
+        whose arg-max class is ``cls``, ties to the lowest class. Where the row-ring kernel runs the last conv
+        the arg-max is fused into its epilogue too (``conv_headk_mask``; ``final`` is not materialised) and the
+        mask is bit for bit the one the separate ``headk_mask`` launch writes; ``RDP_SERVE_FUSED_HEADK=0``
+        keeps the separate launch (A/B measurement). ``mask_head_fused`` tells which of the two ran."""
         C = _native()
         D = self.m.depth
+        self._mask_head_fused = False
         if not self.training and refresh_eval:
             self.prepare_eval()
         l0, l1 = self.down_layers[0]
@@ -948,6 +959,7 @@ class UNetExecutor:
             self._conv_bn_relu(C, la)
             last = i == D
             if last and mask_head is not None and not head and self._conv_head_mask(C, lb, mask_head):
+                self._mask_head_fused = True
                 return
             if not last and eval_up:
                 upsampled = self._conv_bn_relu(C, lb, up=self.ups[i])
@@ -988,10 +1000,17 @@ class UNetExecutor:
     def _conv_head_mask(self, C, L: _Layer, mask_head: tuple) -> bool:
         """Eval: the last conv + BN fold + ReLU + 1x1 head + threshold in one row-ring launch."""
         sp = L.spec
-        if self.K > 1:  # the row-ring fused head is one-class: K classes take the separate headk_mask launch
-            return False
         if self.training or L.x2 is not None or sp.taps != 9 or sp.packed:
             return False
+        if self.K > 1:  # arg-max class == cls, bitwise the separate headk_mask launch's mask
+            if os.environ.get("RDP_SERVE_FUSED_HEADK", "1") == "0":
+                return False
+            # the one measured case where the fused launch lost to the pair (profiles/serve_multiclass.md):
+            # K = 5 at batch 4, +0.3 .. 1.6 us per call; larger batches are unmeasured and take that side too
+            if self.K == 5 and L.x1.shape[0] >= 4:
+                return False
+            hw, hb, cls, mask = mask_head
+            return bool(C.conv_headk_mask(L.x1, self.m.fwd_weight(sp), L.coef, hw, hb, int(cls), mask))
         hw, hb, thr, mask = mask_head
         return bool(C.conv_head_mask(L.x1, self.m.fwd_weight(sp), L.coef, hw, hb, float(thr), mask))
 

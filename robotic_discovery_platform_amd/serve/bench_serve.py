@@ -50,20 +50,27 @@ def slow_frames(lat, parts: dict) -> dict:
     return out
 
 
-def prepare_model(dev, train_steps: int = 200, batch: int = 16, n_scenes: int = 48, seed: int = 0):
+def prepare_model(dev, train_steps: int = 200, batch: int = 16, n_scenes: int = 48, seed: int = 0,
+                  n_classes: int = 1):
+    """A briefly trained model and its scenes. ``n_classes`` >= 2: the K-class scenes (``make_scene(n_classes=K)``)
+    and a K-class model trained with softmax cross-entropy on their class ids."""
     from ..data.image_io import bgr2rgb, resize_area, resize_nearest
     from ..data.synthetic import make_scene
     from ..models.unet import UNetNative
     from ..train.engine import NativeTrainer
     torch.manual_seed(seed)
-    scenes = [make_scene(seed + i) for i in range(n_scenes)]
-    model = UNetNative(3, 1, device=dev)
+    scenes = [make_scene(seed + i, n_classes=n_classes) for i in range(n_scenes)]
+    model = UNetNative(3, n_classes, device=dev)
     if train_steps > 0:
         x = np.stack([resize_area(bgr2rgb(s.color), (256, 256)) for s in scenes]).astype(np.float32) / 255
-        y = np.stack([resize_nearest(s.mask, (256, 256)) for s in scenes]).astype(np.float32) / 255
         X = torch.from_numpy(x).permute(0, 3, 1, 2).contiguous().to(dev)
-        Y = torch.from_numpy(y)[:, None].contiguous().to(dev)
-        tr = NativeTrainer(model, batch, 256, 256, lr=1e-3, graph=True)
+        if n_classes > 1:
+            Y = torch.from_numpy(np.stack([resize_nearest(s.mask, (256, 256)) for s in scenes])).contiguous().to(dev)
+            tr = NativeTrainer(model, batch, 256, 256, lr=1e-3, loss="ce", graph=True)
+        else:
+            y = np.stack([resize_nearest(s.mask, (256, 256)) for s in scenes]).astype(np.float32) / 255
+            Y = torch.from_numpy(y)[:, None].contiguous().to(dev)
+            tr = NativeTrainer(model, batch, 256, 256, lr=1e-3, graph=True)
         g = torch.Generator(device="cpu").manual_seed(seed)
         for _ in range(train_steps):
             idx = torch.randint(0, n_scenes, (batch,), generator=g).to(dev)

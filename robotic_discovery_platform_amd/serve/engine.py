@@ -140,6 +140,15 @@ def _logit(p: float) -> float:
 RESP_PNG_LEVEL, RESP_PNG_BANDS = 1, 8
 
 
+def batch_multiclass_policy(value: Optional[bool] = None) -> bool:
+    """Whether the streams of a K-class model are batched across streams (:class:`BatchEngine`). None:
+    RDP_SERVE_BATCH_MULTICLASS (1 / true / yes / on), else ServeConfig's default (off)."""
+    if value is None:
+        from ..config import ServeConfig, apply_env
+        return bool(apply_env(ServeConfig(), "serve").batch_multiclass)
+    return bool(value)
+
+
 def _check_mask_class(n_classes: int, mask_class: int):
     """A K-class model serves the mask of one class: it must be one of 0..K-1 (one-class models ignore it)."""
     if n_classes > 1 and not 0 <= int(mask_class) < n_classes:
@@ -290,7 +299,7 @@ class FramePipeline:
                                self.scan_status, self.subseq_bits)
             C.jpeg_to_rgb(self.d_coef, self.d_smeta[:32], self.d_smeta[32:], self.d_planes, self.d_color)
         C.preprocess(self.d_color, *self.tab, ex.x_in, int(src != SRC_BGR))
-        if m.n_classes > 1:  # K-class model: arg-max class == mask_class (the separate headk_mask launch)
+        if m.n_classes > 1:  # K-class model: arg-max class == mask_class (fused into the last conv's launch too)
             ex.forward(head=False, refresh_eval=False,
                        mask_head=(m.store.flat_slice("outc.conv.weight"), m.store.view("outc.conv.bias"),
                                   self.mask_class, self.m256))
@@ -537,9 +546,11 @@ class BatchEngine:
     def __init__(self, model, K, depth_scale, H: int = 480, W: int = 640, size: int = 256, threshold: float = 0.5,
                  geo_cfg: Optional[GeometryConfig] = None, device: Optional[torch.device] = None, src: int = SRC_JPEG,
                  frames: Optional[int] = None, positions: int = 4, window_us: float = 300.0,
-                 lanes: Optional[int] = None):
-        if model.n_classes != 1:
-            raise NotImplementedError("BatchEngine serves one-class models (a K-class model keeps per-stream pipelines)")
+                 lanes: Optional[int] = None, mask_class: int = 1):
+        """``mask_class``: K-class models (``n_classes > 1``): the mask is the pixels whose arg-max class it is,
+        as in :class:`FramePipeline`; ``threshold`` is not used then."""
+        _check_mask_class(model.n_classes, mask_class)
+        self.mask_class = int(mask_class)
         dev = _norm_device(device if device is not None else model.store.device)
         if lanes is None:
             lanes = int(os.environ.get("RDP_BATCH_LANES", "1"))
@@ -614,7 +625,8 @@ class BatchEngine:
         self.h_mask = [[host(3, k, j, (H, W), np.uint8) for j in range(self.P)] for k in range(self.nf)]
         self.h_res = [[host(4, k, j, (res_len,), np.float64) for j in range(self.P)] for k in range(self.nf)]
         # one eval executor per (lane, batch size): activations shared by the batch frames of a lane (one stream)
-        self.exl = [{n: UNetExecutor(model, n, size, size, False, "bce", 1.0) for n in range(1, self.P + 1)}
+        loss = "ce" if model.n_classes > 1 else "bce"
+        self.exl = [{n: UNetExecutor(model, n, size, size, False, loss, 1.0) for n in range(1, self.P + 1)}
                     for _ in range(lanes)]
         self.m256l = [{n: torch.empty(n * size * size, dtype=torch.uint8, device=dev) for n in range(1, self.P + 1)}
                       for _ in range(lanes)]
@@ -697,9 +709,14 @@ class BatchEngine:
                                [self.d_color[k][j] for j in range(n)], *self.tab, ex.x_in, int(self.src != SRC_BGR))
         else:
             self._fork(n, pre)
-        ex.forward(head=False, refresh_eval=False,
-                   mask_head=(m.store.view("outc.conv.weight").reshape(-1), m.store.view("outc.conv.bias"),
-                              self.thr_logit, m256))
+        if m.n_classes > 1:  # K-class model: arg-max class == mask_class; everything after it sees a u8 mask
+            ex.forward(head=False, refresh_eval=False,
+                       mask_head=(m.store.flat_slice("outc.conv.weight"), m.store.view("outc.conv.bias"),
+                                  self.mask_class, m256))
+        else:
+            ex.forward(head=False, refresh_eval=False,
+                       mask_head=(m.store.view("outc.conv.weight").reshape(-1), m.store.view("outc.conv.bias"),
+                                  self.thr_logit, m256))
         S2 = self.S * self.S
 
         if os.environ.get("RDP_BATCH_GEO", "1") != "0":
@@ -1095,7 +1112,7 @@ class EnginePool:
     def __init__(self, model, K, depth_scale, H: int = 480, W: int = 640, size: int = 256, n: int = 2,
                  threshold: float = 0.5, graph: bool = True, geo_cfg: Optional[GeometryConfig] = None,
                  devices=None, rgb: bool = False, jpeg: bool = False, max_sizes: int = 3, batch: Optional[int] = None,
-                 jpeg_entropy: Optional[str] = None, mask_class: int = 1):
+                 jpeg_entropy: Optional[str] = None, mask_class: int = 1, batch_multiclass: Optional[bool] = None):
         self.model = model
         self.home_size = (H, W)
         self.max_sizes = max(0, max_sizes)
@@ -1127,12 +1144,16 @@ class EnginePool:
         # a lone stream keeps its double-buffered pipelines (no batching wait on its latency).
         if batch is None:
             batch = int(os.environ.get("RDP_SERVE_BATCH", "4"))
-        # (BatchEngine is one-class: the streams of a K-class model keep their per-stream pipelines)
-        self.batch_positions = batch if (self.gpu and graph and batch >= 2 and not multi) else 0
+        # The streams of a K-class model keep their per-stream pipelines unless batch_multiclass is on (None:
+        # RDP_SERVE_BATCH_MULTICLASS, default 0): opt-in until the 4-stream gain is settled for K classes
+        # (profiles/serve_multiclass.md)
+        self.batch_multiclass = batch_multiclass_policy(batch_multiclass)
+        self.batch_positions = batch if (self.gpu and graph and batch >= 2 and
+                                         (not multi or self.batch_multiclass)) else 0
         self.batchers = []
         if self.batch_positions:
             src = SRC_JPEG if self.jpeg else (SRC_RGB if rgb else SRC_BGR)
-            bargs = {k: v for k, v in self.args.items() if k != "mask_class"}
+            bargs = {k: v for k, v in self.args.items() if multi or k != "mask_class"}
             self.batchers = [BatchEngine(self.replicas[r], H=H, W=W, device=self.devices[r], src=src,
                                          positions=self.batch_positions, **bargs) for r in range(len(self.replicas))]
         self._recent = [dict() for _ in self.replicas]  # replica -> {session id: last submit time}

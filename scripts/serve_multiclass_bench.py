@@ -1,0 +1,236 @@
+#!/usr/bin/env python3
+"""Serving a K-class model: the measurements of profiles/serve_multiclass.md.
+
+  kernel  the last conv (64 -> 64 at 256^2, eval) through the row-ring kernel + ``headk_mask`` (the pair) against
+          the fused ``conv_headk_mask`` launch, N = 1, 2, 4 and K = 3, 8: device time per call (events around
+          replays of a captured graph of 50 back-to-back calls, ``--reps`` calls per window), A and B alternating inside every round.
+  engine  GPU p50 per frame of FramePipeline with a K = 3 model, fused against RDP_SERVE_FUSED_HEADK=0, next to
+          the binary model's, the three pipelines taking turns inside every round.
+  streams 4 client streams through EnginePool: K = 3 with batch_multiclass on / off and the binary model,
+          the three pools taking turns inside every round; engine FPS and the batch-size histogram.
+
+Every figure is reported as min .. max over the rounds (``--rounds``, at least 5), never a single value. Prints
+one JSON line; ``--md`` also writes the tables as markdown."""
+import argparse
+import json
+import math
+import os
+import sys
+import threading
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _rng(v, nd=2):
+    return [round(float(min(v)), nd), round(float(max(v)), nd)]
+
+
+def kernel_level(C, rounds, reps, ks=(3, 8), ns=(1, 2, 4)):
+    dev = "cuda"
+    out = {}
+    torch.manual_seed(10)
+    w = (torch.randn(64, 64, 3, 3, device=dev) / math.sqrt(9 * 64)).to(torch.bfloat16)
+    wk = w.permute(0, 2, 3, 1).reshape(64, -1).contiguous()
+    coef = torch.zeros(4 * 64, device=dev)
+    C.bn_eval_coef(torch.rand(64, device=dev) + 0.5, torch.randn(64, device=dev) * 0.5,
+                   torch.randn(64, device=dev) * 0.1, torch.rand(64, device=dev) + 0.5, 1e-5, coef)
+    for N in ns:
+        x = torch.randn(N, 256, 256, 64, device=dev).to(torch.bfloat16)
+        a = torch.empty(N, 256, 256, 64, dtype=torch.bfloat16, device=dev)
+        M = N * 256 * 256
+        for K in ks:
+            hw = (torch.randn(K, 64, device=dev) * 0.3).reshape(-1)
+            hb = torch.randn(K, device=dev) * 0.1
+            m_pair = torch.empty(M, dtype=torch.uint8, device=dev)
+            m_fused = torch.empty(M, dtype=torch.uint8, device=dev)
+
+            def pair():
+                C.conv_fwd(x, None, wk, 9, 0, a, None, None, 0, coef, 1)
+                C.headk_mask(a, hw, hb, 1, m_pair)
+
+            def conv_only():
+                C.conv_fwd(x, None, wk, 9, 0, a, None, None, 0, coef, 1)
+
+            def fused():
+                assert C.conv_headk_mask(x, wk, coef, hw, hb, 1, m_fused)
+
+            # a captured graph of `inner` back-to-back calls, replayed: the host's launch cost (two calls for the
+            # pair, one for the fused launch) stays out of the device time
+            inner = 50
+
+            def graph_of(fn):
+                for _ in range(20):  # warm up every shape the timed window uses
+                    fn()
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for _ in range(inner):
+                        fn()
+                g.replay()
+                torch.cuda.synchronize()
+                return g
+
+            def timed(g):
+                n = max(1, reps // inner)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    g.replay()
+                e1.record()
+                e1.synchronize()
+                return e0.elapsed_time(e1) * 1e3 / (n * inner)  # us per call
+
+            pair, conv_only, fused = graph_of(pair), graph_of(conv_only), graph_of(fused)
+            assert torch.equal(m_pair, m_fused), "fused mask differs from the pair's"
+            tp, tc, tf = [], [], []
+            for _ in range(rounds):
+                tp.append(timed(pair))
+                tf.append(timed(fused))
+                tc.append(timed(conv_only))
+            out[f"N{N}_K{K}"] = {"pair_us": _rng(tp), "fused_us": _rng(tf), "conv_only_us": _rng(tc),
+                                 "fused_minus_pair_us": _rng([f - p for f, p in zip(tf, tp)])}
+            print(f"[kernel] N={N} K={K}: {out[f'N{N}_K{K}']}", file=sys.stderr, flush=True)
+    return out
+
+
+def engine_level(models, rounds, frames):
+    """models: name -> (model, scenes, kwargs, env value of RDP_SERVE_FUSED_HEADK or None)"""
+    from robotic_discovery_platform_amd.data.synthetic import DEFAULT_K
+    from robotic_discovery_platform_amd.serve.engine import FramePipeline
+    pipes = {}
+    for name, (model, scenes, kw, env) in models.items():
+        if env is None:
+            os.environ.pop("RDP_SERVE_FUSED_HEADK", None)
+        else:
+            os.environ["RDP_SERVE_FUSED_HEADK"] = env
+        pipes[name] = (FramePipeline(model, DEFAULT_K, 0.001, graph=True, **kw), scenes)  # the graph is captured here
+    os.environ.pop("RDP_SERVE_FUSED_HEADK", None)
+    res = {name: [] for name in pipes}
+    for name, (p, scenes) in pipes.items():
+        for i in range(30):
+            p.process(scenes[i % len(scenes)].color, scenes[i % len(scenes)].depth)
+    for _ in range(rounds):
+        for name, (p, scenes) in pipes.items():
+            g = [p.process(scenes[i % len(scenes)].color, scenes[i % len(scenes)].depth).timings["gpu_ms"]
+                 for i in range(frames)]
+            res[name].append(float(np.median(g)))
+    out = {name: {"gpu_p50_ms": _rng(v, 4), "mask_head_fused": bool(pipes[name][0].ex.mask_head_fused)}
+           for name, v in res.items()}
+    print(f"[engine] {out}", file=sys.stderr, flush=True)
+    return out
+
+
+def streams_level(pools, rounds, frames, streams=4):
+    """pools: name -> (EnginePool, scenes)"""
+    def run_round(pool, scenes, n):
+        res = {}
+
+        def run(k):
+            s = pool.session()
+            t0 = time.perf_counter()
+            for i in range(n):
+                sc = scenes[(i + k) % len(scenes)]
+                s.submit(sc.color, sc.depth, tag=i)
+            s.drain()
+            res[k] = time.perf_counter() - t0
+
+        ths = [threading.Thread(target=run, args=(k,)) for k in range(streams)]
+        [t.start() for t in ths]
+        [t.join() for t in ths]
+        return n * streams / max(res.values())
+
+    fps = {name: [] for name in pools}
+    for name, (pool, scenes) in pools.items():
+        run_round(pool, scenes, 50)  # warm up
+        for b in pool.batchers:
+            b.batch_sizes.clear()
+    for _ in range(rounds):
+        for name, (pool, scenes) in pools.items():
+            fps[name].append(run_round(pool, scenes, frames))
+    out = {}
+    for name, (pool, _) in pools.items():
+        out[name] = {"engine_fps": _rng(fps[name], 1)}
+        if pool.batchers:
+            out[name]["batch_sizes"] = {str(k): v for k, v in sorted(pool.batchers[0].batch_sizes.items())}
+    print(f"[streams] {out}", file=sys.stderr, flush=True)
+    return out
+
+
+def to_markdown(out):
+    L = []
+    if "kernel" in out:
+        L += ["| N | K | pair (ring conv + headk_mask), us | fused conv_headk_mask, us | fused - pair, us | ring conv alone, us |",
+              "|---|---|---|---|---|---|"]
+        for key, v in out["kernel"].items():
+            n, k = key[1:].split("_K")
+            f = lambda r: f"{r[0]:.2f} .. {r[1]:.2f}"  # noqa: E731
+            L.append(f"| {n} | {k} | {f(v['pair_us'])} | {f(v['fused_us'])} | {f(v['fused_minus_pair_us'])} | {f(v['conv_only_us'])} |")
+        L.append("")
+    if "engine" in out:
+        L += ["| pipeline | fused head | GPU p50 per frame, ms |", "|---|---|---|"]
+        for name, v in out["engine"].items():
+            L.append(f"| {name} | {v['mask_head_fused']} | {v['gpu_p50_ms'][0]:.4f} .. {v['gpu_p50_ms'][1]:.4f} |")
+        L.append("")
+    if "streams" in out:
+        L += ["| pool (4 streams) | engine FPS | batch sizes |", "|---|---|---|"]
+        for name, v in out["streams"].items():
+            L.append(f"| {name} | {v['engine_fps'][0]:.0f} .. {v['engine_fps'][1]:.0f} | {v.get('batch_sizes', '-')} |")
+        L.append("")
+    return "\n".join(L)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parts", default="kernel,engine,streams")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=1000, help="kernel level: calls per timed window")
+    ap.add_argument("--frames", type=int, default=300, help="engine / streams level: frames per round (and stream)")
+    ap.add_argument("--ks", default="3,8", help="kernel level: class counts")
+    ap.add_argument("--ns", default="1,2,4", help="kernel level: batch sizes")
+    ap.add_argument("--md", default=None)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("serve_multiclass_bench needs a GPU")
+    if a.rounds < 5:
+        raise SystemExit("at least 5 rounds")
+    from robotic_discovery_platform_amd.ops import native
+    C = native()
+    parts = a.parts.split(",")
+    out = {"rounds": a.rounds}
+    if "kernel" in parts:
+        out["kernel"] = kernel_level(C, a.rounds, a.reps, [int(k) for k in a.ks.split(",")],
+                                     [int(n) for n in a.ns.split(",")])
+    if "engine" in parts or "streams" in parts:
+        from robotic_discovery_platform_amd.data.synthetic import DEFAULT_K
+        from robotic_discovery_platform_amd.serve.bench_serve import prepare_model
+        from robotic_discovery_platform_amd.serve.engine import EnginePool
+        dev = torch.device("cuda")
+        m3, sc3 = prepare_model(dev, 30, n_scenes=8, n_classes=3)
+        m1, sc1 = prepare_model(dev, 30, n_scenes=8)
+        if "engine" in parts:
+            out["engine"] = engine_level({"K=3 fused": (m3, sc3, {"mask_class": 1}, None),
+                                          "K=3 separate headk_mask": (m3, sc3, {"mask_class": 1}, "0"),
+                                          "binary": (m1, sc1, {}, None)}, a.rounds, a.frames)
+        if "streams" in parts:
+            pools = {"K=3 batch_multiclass on": (EnginePool(m3, DEFAULT_K, 0.001, n=8, graph=True, batch=4, mask_class=1,
+                                                            batch_multiclass=True), sc3),
+                     "K=3 batch_multiclass off": (EnginePool(m3, DEFAULT_K, 0.001, n=8, graph=True, batch=4,
+                                                             mask_class=1, batch_multiclass=False), sc3),
+                     "binary (batched)": (EnginePool(m1, DEFAULT_K, 0.001, n=8, graph=True, batch=4), sc1)}
+            out["streams"] = streams_level(pools, a.rounds, a.frames)
+            for pool, _ in pools.values():
+                for b in pool.batchers:
+                    b.close()
+    if a.md:
+        with open(a.md, "w") as f:
+            f.write(to_markdown(out) + "\n")
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
