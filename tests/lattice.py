@@ -7,6 +7,9 @@ bf16 output is one fixed value: that integer rounded to nearest even. The GPU te
 builds the inputs and references and states the preconditions under which that demand is sound.
 tests/test_lattice_cpu.py checks, without a GPU, that every case of the tables meets them.
 
+The second half of the module does the same for the memory-bound passes between the convs (BN finalize /
+apply / backward, max pool, bilinear upsample): tests/test_pass_exact_gpu.py, tests/test_pass_lattice_cpu.py.
+
 Pure torch on the CPU: the native extension is never imported here.
 """
 import functools
@@ -651,3 +654,592 @@ def upT_window(c: UpT, t: torch.Tensor) -> torch.Tensor:
     """[N,H2,W2,C] -> the sub-pixel GEMM layout [N,h,w,(dh,dw,c)] of the 2h x 2w window at (oy, ox)."""
     win = t[:, c.oy:c.oy + 2 * c.h, c.ox:c.ox + 2 * c.w]
     return win.reshape(c.N, c.h, 2, c.w, 2, c.C).permute(0, 1, 3, 2, 4, 5).reshape(c.N, c.h, c.w, 4 * c.C).contiguous()
+
+
+# =============================================================================================
+# The memory-bound passes between the convs: BN finalize / apply / backward, max pool, bilinear
+# upsample (tests/test_pass_exact_gpu.py; preconditions in tests/test_pass_lattice_cpu.py)
+# =============================================================================================
+#
+# The elementwise passes evaluate fma(y, scale, shift) (and the backward's A * g + B * y + Cc) in fp32
+# and round once to bf16. With small-integer y, scale = +-2^k and integer shift every such value is a
+# small dyadic number: exact in fp32 whether or not the compiler fuses the multiply-add, and exactly
+# representable in bf16, so the stored value is fixed bit for bit. Because these passes are elementwise,
+# a case's preconditions depend only on the set of input values and its coefficients: the *_table
+# functions evaluate the reference for every possible input value of every channel.
+
+APX = 4                      # pixels in flight per thread in the BN apply kernels
+PX_GRID_CAP = 2048           # their grid cap
+FIN_DIRECT_ROWS = 2048       # rows the finalize kernels fold themselves; above, colsum_kernel (needs a workspace)
+POOL_GRID_CAP = 4096         # maxpool2_fwd / bwd: blocks of 256 items, grid-stride beyond
+APPLY_POOL_GRID_CAP = 16384  # bn_relu_apply_pool
+UP_MIN_ITEMS = 4096          # the upsample launchers halve the band height below this many work items
+
+
+def cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def px_grid(M: int, C: int):
+    """(grid, chunk, rows per block) of the pixel-walking BN apply launchers (grid_px / px_chunk)."""
+    rpb = 256 // (C // 8)
+    step = rpb * APX
+    grid = max(1, min(cdiv(M, step), PX_GRID_CAP))
+    chunk = cdiv(cdiv(M, grid), step) * step
+    return grid, chunk, rpb
+
+
+def up_band_rows(N: int, rows: int, cols: int, C: int, start: int) -> int:
+    """Band height of the upsample launchers: `start` (8 forward over output rows / columns, 4 backward
+    over input-gradient rows / columns), halved while fewer than 4096 work items would be in flight."""
+    nchunk = cdiv(cols * (C // 8), 256)
+    R = start
+    while R > 1 and N * cdiv(rows, R) * nchunk < UP_MIN_ITEMS:
+        R //= 2
+    return R
+
+
+def bf16_exact(ref64: torch.Tensor) -> bool:
+    return torch.equal(ref64, ref64.to(BF16).double())
+
+
+def f32_exact(ref64: torch.Tensor) -> bool:
+    return torch.equal(ref64, ref64.float().double())
+
+
+def _odd_signed(n: int, gen: torch.Generator, lo: int, hi: int) -> torch.Tensor:
+    """fp32 vector of odd integers with lo <= |v| <= hi, both signs present."""
+    v = torch.randint(lo // 2, (hi - 1) // 2 + 1, (n,), generator=gen) * 2 + 1
+    s = torch.randint(0, 2, (n,), generator=gen) * 2 - 1
+    s[0], s[1] = 1, -1
+    return (s * v).float()
+
+
+# ---------------------------------------------------------------------------------------------
+# bn_relu_apply / bn_relu_bwd_apply
+# ---------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Px:
+    """One launch of a pixel-walking BN pass over M = N * H * W pixels of C channels."""
+    name: str
+    N: int
+    H: int
+    W: int
+    C: int
+    relu: int = 1
+    cls: str = "exact"     # "exact" | "round"
+    views: bool = False
+    capped: bool = False   # M > 2048 * (2048 / C) * 4: the grid reaches its cap
+    seed: int = 0
+
+    @property
+    def M(self) -> int:
+        return self.N * self.H * self.W
+
+
+PX_CASES = [
+    Px("c64-one-block-views", 1, 7, 5, 64, views=True),
+    Px("c8-ragged", 2, 37, 29, 8),
+    Px("c512-ragged-norelu-views", 2, 37, 29, 512, relu=0, views=True),
+    Px("c2048-ragged", 1, 9, 11, 2048),
+    Px("c64-round", 2, 37, 29, 64, relu=0, cls="round"),
+    Px("c2048-round-views", 1, 9, 11, 2048, cls="round", views=True),
+    Px("c8-capped", 2, 1025, 1031, 8, capped=True),
+    Px("c64-capped", 3, 301, 293, 64, relu=0, capped=True),
+    Px("c512-capped", 1, 181, 183, 512, capped=True),
+    Px("c2048-capped-views", 1, 91, 93, 2048, capped=True, views=True),
+]
+
+
+def check_px_shape(c: Px) -> None:
+    """The last working block's chunk is ragged: its last step of rpb * APX pixels is partial, and (where a
+    block holds more than one pixel row) so is the last row group; capped cases reach 2048 blocks."""
+    grid, chunk, rpb = px_grid(c.M, c.C)
+    tail = c.M % chunk
+    assert tail % (rpb * APX) != 0 and (rpb == 1 or tail % rpb != 0), f"{c.name}: the last chunk is not ragged"
+    if c.capped:
+        assert c.M > PX_GRID_CAP * (2048 // c.C) * APX and grid == PX_GRID_CAP
+        assert chunk > rpb * APX  # more than one step per block
+    else:
+        assert grid < PX_GRID_CAP
+
+
+def apply_coef(c: Px) -> torch.Tensor:
+    """[mean | invstd | scale | shift]. exact: +-2^k (k = -2..1), integer shift. round: +-2^k (k = 1..5) and
+    odd shifts of magnitude 361..409, so y in -3..3 gives odd integers within 265..505: every one a tie."""
+    g = generator(11000 + c.seed + c.C)
+    if c.cls == "exact":
+        scale, shift = pow2_signed(c.C, g), int_vector(c.C, g, 8)
+    else:
+        scale, shift = pow2_signed(c.C, g, 1, 5), _odd_signed(c.C, g, 361, 409)
+    return torch.cat([torch.zeros(c.C), torch.ones(c.C), scale, shift])
+
+
+def apply_ref(y: torch.Tensor, coef: torch.Tensor, relu: int) -> torch.Tensor:
+    """fp64 relu(y * scale + shift), on the device y lives on."""
+    C = y.shape[-1]
+    z = y.double() * coef[2 * C:3 * C].double().to(y.device) + coef[3 * C:4 * C].double().to(y.device)
+    return torch.relu(z) if relu else z
+
+
+def apply_data(c: Px):
+    y = small_ints((c.N, c.H, c.W, c.C), generator(12000 + c.seed + c.C), 3)
+    coef = apply_coef(c)
+    return y, coef, apply_ref(y, coef, c.relu)
+
+
+def apply_table(c: Px) -> torch.Tensor:
+    """The reference for every input value -3..3 of every channel: [7, C] fp64."""
+    v = torch.arange(-3, 4).to(BF16).view(7, 1).expand(7, c.C)
+    return apply_ref(v, apply_coef(c), c.relu)
+
+
+def check_apply_table(c: Px, tab: torch.Tensor) -> None:
+    if c.cls == "exact":
+        assert bf16_exact(tab) and (tab.abs() * 4 < 256).all() and torch.equal(tab * 4, (tab * 4).round())
+        if c.relu:
+            assert (tab == 0).any() and (tab > 0).any()
+        else:
+            assert (tab < 0).any() and (tab > 0).any()
+    else:
+        pre = apply_ref(torch.arange(-3, 4).to(BF16).view(7, 1).expand(7, c.C), apply_coef(c), 0)
+        assert true_ties(pre) == pre.numel(), "round class: every pre-ReLU value must be a true tie"
+        assert_rounding_class(tab)
+
+
+def bwd_apply_coefs(c: Px):
+    """coef as the kernel reads it for the ReLU mask (scale = +-2^k, shift -1..1) and coef2 = [A | B | Cc].
+    exact: A = +-2^k (k = -1..2), B and Cc in -2..2 (firstbn_data's form). round: A = +-2^k (k = 1..4), B even,
+    Cc odd of magnitude 331..439: dy is an odd integer within 281..489."""
+    g = generator(13000 + c.seed + c.C)
+    scale = pow2_signed(c.C, g)
+    shift = torch.randint(-1, 2, (c.C,), generator=g).float()
+    if c.cls == "exact":
+        A, B, Cc = pow2_signed(c.C, g, -1, 2), int_vector(c.C, g, 2), int_vector(c.C, g, 2)
+    else:
+        A = pow2_signed(c.C, g, 1, 4)
+        B = (torch.randint(-1, 2, (c.C,), generator=g) * 2).float()
+        Cc = _odd_signed(c.C, g, 331, 439)
+    return torch.cat([torch.zeros(c.C), torch.ones(c.C), scale, shift]), torch.cat([A, B, Cc])
+
+
+def bwd_apply_ref(da, y, coef, coef2, relu: int) -> torch.Tensor:
+    """fp64 dy = A * g + B * y + Cc, g = da * [scale * y + shift > 0] (g = da without ReLU)."""
+    C = y.shape[-1]
+    k = [coef[2 * C:3 * C], coef[3 * C:4 * C], coef2[:C], coef2[C:2 * C], coef2[2 * C:3 * C]]
+    sc, sh, A, B, Cc = (t.double().to(y.device) for t in k)
+    yd, g = y.double(), da.double()
+    if relu:
+        g = g * ((yd * sc + sh) > 0)
+    return A * g + B * yd + Cc
+
+
+def bwd_apply_data(c: Px):
+    g = generator(14000 + c.seed + c.C)
+    shape = (c.N, c.H, c.W, c.C)
+    da, y = small_ints(shape, g, 3), ternary(shape, 0.7, g)
+    coef, coef2 = bwd_apply_coefs(c)
+    return da, y, coef, coef2, bwd_apply_ref(da, y, coef, coef2, c.relu)
+
+
+def bwd_apply_table(c: Px) -> torch.Tensor:
+    """[7 (da = -3..3), 3 (y = -1..1), C] fp64."""
+    da = torch.arange(-3, 4).to(BF16).view(7, 1, 1).expand(7, 3, c.C)
+    y = torch.arange(-1, 2).to(BF16).view(1, 3, 1).expand(7, 3, c.C)
+    coef, coef2 = bwd_apply_coefs(c)
+    return bwd_apply_ref(da, y, coef, coef2, c.relu)
+
+
+def check_bwd_apply_table(c: Px, tab: torch.Tensor) -> None:
+    if c.cls == "exact":
+        assert bf16_exact(tab) and (tab.abs() * 2 < 256).all() and torch.equal(tab * 2, (tab * 2).round())
+        if c.relu:  # the mask cuts some and keeps some
+            assert (tab[6] != tab[0]).any() and (tab[6] == tab[0]).any()
+    else:
+        assert true_ties(tab) == tab.numel()
+        assert_rounding_class(tab)
+
+
+# ---------------------------------------------------------------------------------------------
+# the BN backward reductions: bn_relu_bwd_reduce, maxpool2_bwd_bn_reduce, upsample2_bwd + reduce
+# ---------------------------------------------------------------------------------------------
+
+def bn_lattice_coef(C: int, gen: torch.Generator, shift_amax: int = 1) -> torch.Tensor:
+    """[mean | invstd | scale | shift] as bnred_data builds it: integer mean, invstd = 2^k, scale = +-2^k,
+    integer shift -- every term of sum(g) and sum(g * xhat) is then dyadic."""
+    mean = int_vector(C, gen, 2)
+    inv = torch.pow(2.0, torch.randint(-2, 2, (C,), generator=gen).double()).float()
+    return torch.cat([mean, inv, pow2_signed(C, gen), int_vector(C, gen, shift_amax)])
+
+
+def reduce_terms(g64: torch.Tensor, y: torch.Tensor, coef: torch.Tensor, relu: int = 1):
+    """(g * mask, g * mask * (y - mean) * invstd) in fp64 and their per-channel sums [2][C]."""
+    C = y.shape[-1]
+    mean, inv, sc, sh = (coef[k * C:(k + 1) * C].double().to(y.device) for k in range(4))
+    yd = y.double()
+    gg = g64 * ((yd * sc + sh) > 0) if relu else g64
+    t2 = gg * (yd - mean) * inv
+    return (gg, t2), torch.stack([gg.reshape(-1, C).sum(0), t2.reshape(-1, C).sum(0)])
+
+
+@dataclass(frozen=True)
+class Red:
+    name: str
+    N: int
+    H: int
+    W: int
+    C: int
+    relu: int = 1
+    views: bool = False
+    cap: int = 1024     # partial rows offered to the kernel
+    seed: int = 0
+
+
+RED_CASES = [
+    Red("red-c64-odd", 2, 37, 29, 64),
+    Red("red-c8", 3, 33, 47, 8),
+    Red("red-c512-views", 2, 9, 13, 512, views=True),
+    Red("red-c2048", 1, 9, 11, 2048),
+    Red("red-c96-not-pow2", 2, 9, 13, 96),
+    Red("red-c64-cap3-wraps", 2, 37, 29, 64, cap=3),
+    Red("red-c128-norelu-views", 1, 21, 17, 128, relu=0, views=True),
+]
+
+
+def red_data(c: Red):
+    g = generator(15000 + c.seed + c.C)
+    shape = (c.N, c.H, c.W, c.C)
+    da, y = small_ints(shape, g, 3), ternary(shape, 0.7, g)
+    coef = bn_lattice_coef(c.C, g)
+    terms, sums = reduce_terms(da.double(), y, coef, c.relu)
+    return da, y, coef, terms, sums
+
+
+def check_red_terms(terms, sums, masked: bool = True) -> None:
+    assert_f32_sums(terms[0], "sum g")
+    assert_f32_sums(terms[1], "sum g * xhat")
+    assert f32_exact(sums) and (sums[0] != 0).any() and (sums[1] != 0).any()
+    if masked:
+        assert (terms[0] == 0).any() and (terms[0] != 0).any()
+
+
+# ---------------------------------------------------------------------------------------------
+# max pool and its BN fusions
+# ---------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Pool:
+    name: str
+    N: int
+    H: int
+    W: int
+    C: int
+    dskip: bool = True
+    views: bool = False
+    cap: int = 1024      # fused backward: partial rows offered
+    big: bool = False    # a path-forcing size: its reference is evaluated by torch fp64 on the device
+    seed: int = 0
+
+
+POOL_CASES = [
+    Pool("pool-c64-even", 2, 16, 16, 64),
+    Pool("pool-c8-odd-both-views", 1, 9, 7, 8, views=True),
+    Pool("pool-c512-odd-h-noskip-views", 2, 9, 8, 512, dskip=False, views=True),
+    Pool("pool-c64-odd-w-noskip", 2, 8, 9, 64, dskip=False),
+    Pool("pool-c8-grid-wraps", 4, 1027, 1027, 8, big=True),
+]
+
+POOLFUSE_CASES = [
+    Pool("fuse-c64-even", 2, 16, 16, 64),
+    Pool("fuse-c8-odd-both-views", 1, 9, 13, 8, views=True),
+    Pool("fuse-c512-odd-w-noskip-views", 3, 8, 7, 512, dskip=False, views=True),
+    Pool("fuse-c64-odd-h-cap2-wraps", 4, 33, 24, 64, cap=2),
+    Pool("fuse-c128-odd-both", 1, 33, 31, 128),
+]
+APPLY_POOL_BIG = Pool("fuse-c512-grid-capped", 2, 363, 363, 512, big=True)
+
+
+def pool_items(c: Pool):
+    """(forward, backward) work items of maxpool2_fwd / maxpool2_bwd: one per (window, 8-channel group)."""
+    cg = c.C // 8
+    return c.N * (c.H // 2) * (c.W // 2) * cg, c.N * cdiv(c.H, 2) * cdiv(c.W, 2) * cg
+
+
+def apply_pool_blocks(c: Pool) -> int:
+    """Blocks bn_relu_apply_pool would need for one window row each (before the 16384 cap)."""
+    return cdiv(c.N * cdiv(c.H, 2) * cdiv(c.W, 2), 256 // (c.C // 8))
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def pool_ref(a64: torch.Tensor, dp: Optional[torch.Tensor], dskip: Optional[torch.Tensor]):
+    """fp64 F.max_pool2d(2) of an NHWC tensor and, with dp, its autograd input gradient (+ dskip): torch
+    routes each window's gradient to its first maximum in row-major order."""
+    x = _nchw(a64).contiguous().requires_grad_(dp is not None)
+    p = F.max_pool2d(x, 2)
+    if dp is None:
+        return _nhwc(p), None
+    p.backward(_nchw(dp.double()).contiguous())
+    dx = _nhwc(x.grad)
+    if dskip is not None:
+        dx = dx + dskip.double()
+    return _nhwc(p.detach()), dx
+
+
+def tie_fraction(a64: torch.Tensor) -> float:
+    """Fraction of 2x2 windows whose maximum is attained more than once."""
+    H, W = a64.shape[1] // 2 * 2, a64.shape[2] // 2 * 2
+    w = torch.stack([a64[:, i:H:2, j:W:2] for i in (0, 1) for j in (0, 1)])
+    return ((w == w.max(0).values).sum(0) > 1).double().mean().item()
+
+
+def pool_data(c: Pool, device="cpu"):
+    """Ternary x (most windows tie), small-integer dp / dskip. big cases draw on `device`."""
+    if c.big:
+        g = torch.Generator(device=device)
+        g.manual_seed(16000 + c.seed)
+        def draw(shape, amax):
+            return torch.randint(-amax, amax + 1, shape, generator=g, device=device).to(BF16)
+    else:
+        g = generator(16000 + c.seed + c.C)
+        def draw(shape, amax):
+            return torch.randint(-amax, amax + 1, shape, generator=g).to(BF16)
+    x = draw((c.N, c.H, c.W, c.C), 1)
+    dp = draw((c.N, c.H // 2, c.W // 2, c.C), 3)
+    ds = draw((c.N, c.H, c.W, c.C), 3) if c.dskip else None
+    return x, dp, ds
+
+
+def poolfuse_coef(c: Pool) -> torch.Tensor:
+    return bn_lattice_coef(c.C, generator(17000 + c.seed + c.C), shift_amax=2)
+
+
+def poolfuse_data(c: Pool, device="cpu"):
+    """y in -3..3 under +-2^k scales and integer shifts: a = relu(bn(y)) is exact in bf16 and its many zeros
+    tie. Returns y, dp, dskip, coef and the fp64 a."""
+    if c.big:
+        g = torch.Generator(device=device)
+        g.manual_seed(17000 + c.seed)
+        y = torch.randint(-3, 4, (c.N, c.H, c.W, c.C), generator=g, device=device).to(BF16)
+        dp = ds = None
+    else:
+        g = generator(18000 + c.seed + c.C)
+        y = small_ints((c.N, c.H, c.W, c.C), g, 3)
+        dp = small_ints((c.N, c.H // 2, c.W // 2, c.C), g, 3)
+        ds = small_ints((c.N, c.H, c.W, c.C), g, 3) if c.dskip else None
+    coef = poolfuse_coef(c)
+    return y, dp, ds, coef, apply_ref(y, coef, 1)
+
+
+def poolfuse_table(c: Pool) -> torch.Tensor:
+    v = torch.arange(-3, 4).to(BF16).view(7, 1).expand(7, c.C)
+    return apply_ref(v, poolfuse_coef(c), 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# bn_finalize / bn_bwd_finalize on synthetic partial rows
+# ---------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Fin:
+    name: str
+    T: int
+    C: int
+    ws: bool = False   # pass the colsum workspace (used when T > 2048)
+    seed: int = 0
+
+
+FIN_COUNT = 1 << 14
+FIN_CASES = [Fin(f"T{T}-C{C}", T, C) for T in (1, 16, 17, 63, 64, 65, 2048) for C in (64, 96, 512)] + \
+            [Fin(f"T{T}-C{C}-{'colsum' if ws else 'direct'}", T, C, ws)
+             for T in (2049, 5000) for C in (64, 96, 512) for ws in (True, False)]
+
+
+def split_rows(total: torch.Tensor, T: int, gen: torch.Generator, amp: int = 3) -> torch.Tensor:
+    """Integer rows [T][K] that sum to total [K] exactly: an even split plus zero-sum integer noise."""
+    total = total.long()
+    base = total // T
+    rem = total - base * T
+    rows = base[None, :] + (torch.arange(T)[:, None] < rem[None, :]).long()
+    n = torch.randint(-amp, amp + 1, (T, total.numel()), generator=gen)
+    return rows + n - n.roll(1, 0)
+
+
+def _dyadic(n: int, gen: torch.Generator, amax: int, denom: int, nonzero: bool = False) -> torch.Tensor:
+    v = torch.randint(-amax, amax + 1, (n,), generator=gen)
+    if nonzero:
+        v[v == 0] = amax
+    return (v.double() / denom).float()
+
+
+def fin_data(c: Fin):
+    """Synthetic (sum, sum of squares) rows of a layer whose channel has integer mean mu and sigma = 2^j over
+    count = 2^14 pixels; eps = 0, momentum = 1/2, dyadic gamma / beta / running stats. Every output is then
+    one fixed fp32 value (running_var, through count / (count - 1), within one ulp). Returns the inputs and
+    the expected outputs in fp64."""
+    g = generator(19000 + c.seed + 7 * c.T + c.C)
+    mu = torch.randint(-3, 4, (c.C,), generator=g).double()
+    j = torch.randint(0, 3, (c.C,), generator=g).double()
+    var = torch.pow(4.0, j)
+    S, Q = FIN_COUNT * mu, FIN_COUNT * (var + mu * mu)
+    rows = torch.cat([split_rows(S, c.T, g), split_rows(Q, c.T, g)], 1).float()   # [T][2C]
+    gamma, beta = _dyadic(c.C, g, 6, 2, nonzero=True), _dyadic(c.C, g, 8, 4)
+    rmean, rvar = _dyadic(c.C, g, 8, 4), (torch.randint(1, 9, (c.C,), generator=g).double() / 4).float()
+    inv = torch.pow(2.0, -j)
+    sc = gamma.double() * inv
+    exp = {"mean": mu, "invstd": inv, "scale": sc, "shift": beta.double() - mu * sc,
+           "rmean": 0.5 * rmean.double() + 0.5 * mu,
+           "rvar": 0.5 * rvar.double() + 0.5 * (var * FIN_COUNT / (FIN_COUNT - 1))}
+    return rows, gamma, beta, rmean, rvar, exp
+
+
+def bwd_fin_data(c: Fin):
+    """Integer partial rows of (sum g, sum g * xhat), dyadic gamma / invstd, integer mean. dbeta and dgamma
+    are the integer totals; coef2 = [A | B | Cc] is formed in fp64 from dyadic factors with fewer than 24
+    significant bits, so its fp32 value is fixed too."""
+    g = generator(20000 + c.seed + 7 * c.T + c.C)
+    S = torch.randint(-4000, 4001, (c.C,), generator=g).double()
+    Q = torch.randint(-4000, 4001, (c.C,), generator=g).double()
+    rows = torch.cat([split_rows(S, c.T, g), split_rows(Q, c.T, g)], 1).float()
+    gamma = _dyadic(c.C, g, 6, 2, nonzero=True)
+    mean = int_vector(c.C, g, 3)
+    inv = torch.pow(2.0, -torch.randint(0, 3, (c.C,), generator=g).double()).float()
+    coef = torch.cat([mean, inv, gamma * inv, torch.zeros(c.C)])
+    A = gamma.double() * inv.double()
+    mg, mgx = S / FIN_COUNT, Q / FIN_COUNT
+    exp = {"dbeta": S, "dgamma": Q,
+           "coef2": torch.cat([A, -A * inv.double() * mgx, -A * mg + A * inv.double() * mgx * mean.double()])}
+    return rows, gamma, coef, exp
+
+
+def check_fin_rows(c: Fin, rows: torch.Tensor) -> None:
+    """Integer rows whose every partial sum is exact in fp32 (the colsum pre-reduction adds them in fp32)."""
+    assert rows.shape == (c.T, 2 * c.C) and rows.dtype == torch.float32
+    assert_f32_sums(rows.double(), "partial rows")
+    assert torch.equal(rows, rows.round())
+
+
+# ---------------------------------------------------------------------------------------------
+# bilinear x2 upsample (align_corners) + centred pad: per-element class
+# ---------------------------------------------------------------------------------------------
+
+@dataclass(frozen=True)
+class Up:
+    """x [N,hin,win,C] -> out [N,Hout,Wout,C] with the 2x map at (oy, ox); R: the band height the launcher
+    must pick for this shape (forward: over Hout / Wout from 8; backward: over hin / win from 4)."""
+    name: str
+    N: int
+    hin: int
+    win: int
+    C: int
+    Hout: int
+    Wout: int
+    oy: int
+    ox: int
+    R: int
+    views: bool = False
+    coef: bool = False    # forward: also the fused producer BN + ReLU form
+    bnred: bool = False   # backward: also the fused BN reduction form (UP_BNRED_CASES: its sums are exact)
+    seed: int = 0
+
+
+UP_FWD_CASES = [
+    Up("fwd-R1-one-pixel", 2, 1, 1, 64, 3, 5, 1, 1, 1, views=True, coef=True),
+    Up("fwd-R1-hin1", 1, 1, 6, 128, 2, 13, 0, 1, 1),
+    Up("fwd-R1-win1", 3, 5, 1, 512, 11, 3, 1, 1, 1, coef=True),
+    Up("fwd-R1-odd-pad-views", 2, 5, 7, 64, 11, 15, 1, 1, 1, views=True, coef=True),
+    Up("fwd-R1-two-chunks", 1, 9, 19, 128, 20, 39, 1, 1, 1),
+    Up("fwd-R2-c512", 8, 30, 30, 512, 63, 63, 3, 1, 2, coef=True),
+    Up("fwd-R2-c64", 14, 61, 64, 64, 125, 130, 1, 1, 2),
+    Up("fwd-R4-c512", 16, 30, 30, 512, 63, 63, 1, 3, 4),
+    Up("fwd-R4-c128", 16, 61, 64, 128, 125, 130, 3, 1, 4, coef=True),
+    Up("fwd-R8-c512", 32, 30, 30, 512, 63, 63, 1, 1, 8),
+    Up("fwd-R8-c64", 52, 61, 64, 64, 125, 130, 1, 1, 8, coef=True),
+    Up("fwd-R4-c128-views", 16, 61, 64, 128, 125, 130, 1, 1, 4, views=True),
+]
+
+UP_BWD_CASES = [
+    Up("bwd-R1-one-pixel", 2, 1, 1, 64, 3, 5, 1, 1, 1, views=True, bnred=True),
+    Up("bwd-R1-hin1", 1, 1, 6, 128, 2, 13, 0, 1, 1, bnred=True),
+    Up("bwd-R1-win1", 3, 5, 1, 512, 11, 3, 1, 1, 1),
+    Up("bwd-R1-odd-pad-views", 2, 5, 7, 64, 11, 15, 1, 1, 1, views=True, bnred=True),
+    Up("bwd-R1-two-chunks", 1, 9, 37, 64, 20, 75, 1, 1, 1),
+    Up("bwd-R2-c512", 32, 31, 30, 512, 63, 61, 1, 1, 2),
+    Up("bwd-R2-c64", 45, 61, 65, 64, 125, 133, 3, 1, 2),
+    Up("bwd-R4-c512", 64, 30, 30, 512, 63, 63, 1, 3, 4),
+    Up("bwd-R4-c128", 52, 61, 65, 128, 125, 133, 1, 1, 4),
+    Up("bwd-R2-c128-views", 27, 61, 65, 128, 123, 131, 1, 1, 2, views=True),
+]
+
+# The fused BN reduction is exact only while M = N * hin * win is small (below): the banded heights are
+# reached at C = 2048, where a chunk of 256 lanes is one pixel.
+UP_BNRED_CASES = [
+    Up("bnred-R1-c512", 2, 9, 7, 512, 19, 15, 1, 1, 1, bnred=True),
+    Up("bnred-R2-c2048", 1, 91, 91, 2048, 183, 183, 1, 1, 2, bnred=True),
+    Up("bnred-R4-c2048", 2, 91, 91, 2048, 183, 183, 1, 1, 4, bnred=True),
+]
+
+
+def check_up_shape(c: Up, fwd: bool) -> None:
+    assert 2 * c.hin + c.oy <= c.Hout and 2 * c.win + c.ox <= c.Wout
+    assert (c.oy, c.ox) != (0, 0)
+    rows, cols, start = (c.Hout, c.Wout, 8) if fwd else (c.hin, c.win, 4)
+    assert up_band_rows(c.N, rows, cols, c.C, start) == c.R, f"{c.name}: the launcher would not pick R = {c.R}"
+    if c.R > 1:
+        assert rows % c.R != 0, f"{c.name}: the last band is not ragged"
+        if c.C < 2048:  # at C = 2048 a chunk is exactly one pixel
+            assert (cols * (c.C // 8)) % 256 != 0, f"{c.name}: the last 256-lane chunk is not ragged"
+
+
+def up_bnred_coef(C: int, seed: int = 0) -> torch.Tensor:
+    """mean -1..1, invstd 1 or 2, scale +-2^k, shift -1..1: with dout in 4..6 the gradient dx lies in two
+    binades, so the terms of the reduction share a coarse quantum (asserted on the dx read back)."""
+    g = generator(21000 + seed + C)
+    mean = int_vector(C, g, 1)
+    inv = torch.pow(2.0, torch.randint(0, 2, (C,), generator=g).double()).float()
+    return torch.cat([mean, inv, pow2_signed(C, g), int_vector(C, g, 1)])
+
+
+def up_ref(x64: torch.Tensor, c: Up) -> torch.Tensor:
+    """fp64 F.interpolate(scale 2, bilinear, align_corners) + the pad that puts it at (oy, ox); NHWC."""
+    up = F.interpolate(_nchw(x64), scale_factor=2, mode="bilinear", align_corners=True)
+    return F.pad(up, [c.ox, c.Wout - 2 * c.win - c.ox, c.oy, c.Hout - 2 * c.hin - c.oy]).permute(0, 2, 3, 1)
+
+
+def ulp_bf16(ref64: torch.Tensor) -> torch.Tensor:
+    """Spacing of bf16 at |ref| (8 significant bits); 0 at 0."""
+    _, e = torch.frexp(ref64)
+    return torch.where(ref64 == 0, torch.zeros_like(ref64), torch.ldexp(torch.ones_like(ref64), e - 8))
+
+
+def up_bwd_ref(dout64: torch.Tensor, c: Up) -> torch.Tensor:
+    """fp64 autograd gradient of up_ref with respect to its input, NHWC [N,hin,win,C']."""
+    x = torch.zeros(c.N, c.hin, c.win, dout64.shape[-1], dtype=torch.float64, device=dout64.device).requires_grad_(True)
+    up_ref(x, c).backward(dout64)
+    return x.grad
+
+
+UP_TILE = 128  # the fused-reduction cases draw this many channels and repeat them: the kernel treats channels alike
+
+
+def up_bnred_inputs(c: Up):
+    """dout in 4..6 over the whole padded map (dx then lies within [8, 32)), ternary y, up_bnred_coef."""
+    g = generator(22000 + c.seed + c.C)
+    cb = min(c.C, UP_TILE)
+    dout = torch.randint(4, 7, (c.N, c.Hout, c.Wout, cb), generator=g).to(BF16)
+    y = ternary((c.N, c.hin, c.win, cb), 0.7, g)
+    rep = c.C // cb
+    return dout.repeat(1, 1, 1, rep), y.repeat(1, 1, 1, rep), up_bnred_coef(c.C, c.seed)
+
+
+def up_bnred_ref_dx(c: Up, dout: torch.Tensor) -> torch.Tensor:
+    """fp64 autograd dx of a fused-reduction case (computed on the drawn channels, then repeated)."""
+    cb = min(c.C, UP_TILE)
+    return up_bwd_ref(dout[..., :cb].double(), c).repeat(1, 1, 1, c.C // cb)
