@@ -2008,6 +2008,27 @@ void mask_upsample(torch::Tensor m, torch::Tensor out, torch::Tensor count) {
                     (unsigned*)count.data_ptr(), unplanned_stream());
 }
 
+// The serving mask's component filter (csrc/mask_components.hip), in place on n contiguous u8 H x W masks. Every
+// refusal is a ValueError and leaves the mask as it was.
+void mask_components(torch::Tensor mask, int n, int H, int W, int keep_largest, int min_area,
+                     c10::optional<torch::Tensor> stats) {
+  TORCH_CHECK_VALUE(n >= 1 && H >= 1 && W >= 1, "mask_components: n, H, W must be >= 1 (got ", n, ", ", H, ", ", W, ")");
+  TORCH_CHECK_VALUE((long)H * W <= 65536, "mask_components: H * W = ", (long)H * W, " above 65,536 pixels");
+  TORCH_CHECK_VALUE(min_area >= 0, "mask_components: min_area must be >= 0 (got ", min_area, ")");
+  TORCH_CHECK_VALUE(mask.is_cuda() && mask.scalar_type() == torch::kUInt8 && mask.is_contiguous() &&
+                        mask.numel() >= (long)n * H * W,
+                    "mask_components: mask must be a contiguous u8 GPU tensor of n * H * W elements");
+  int* sp = nullptr;
+  if (stats) {
+    TORCH_CHECK_VALUE(stats->is_cuda() && stats->scalar_type() == torch::kInt32 && stats->is_contiguous() &&
+                          stats->numel() >= 4l * n,
+                      "mask_components: stats must be a contiguous int32 GPU tensor of n * 4 elements");
+    sp = stats->data_ptr<int>();
+  }
+  TORCH_CHECK_VALUE(rdp_mask_components(mask.data_ptr(), n, H, W, keep_largest ? 1 : 0, min_area, sp,
+                                        unplanned_stream()) == 0, "mask_components: unsupported arguments");
+}
+
 }  // namespace
 
 void register_serve_runtime(py::module_& m);  // serve_runtime.cpp
@@ -2163,6 +2184,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("preprocess", on_device(&preprocess), py::arg("bgr"), py::arg("ystart"), py::arg("ysize"), py::arg("yw"),
         py::arg("xstart"), py::arg("xsize"), py::arg("xw"), py::arg("out"), py::arg("rgb") = 0);
   m.def("mask_upsample", on_device(&mask_upsample));
+  m.def("mask_components", on_device(&mask_components), py::arg("mask"), py::arg("n"), py::arg("H"), py::arg("W"),
+        py::arg("keep_largest"), py::arg("min_area"), py::arg("stats") = py::none());
   m.def("splev", &splev);
   m.def("fit_curvature", &fit_curvature);
 }

@@ -289,6 +289,15 @@ int rdp_jpeg_entropy_gpu(const void* scan, long cap_bytes, const int* nbits, con
                          void* coefs, long cap_coefs, int* work, long work_words, int* status, int S,
                          long* stats_word, hipStream_t st);
 
+// ---- csrc/mask_components.hip ---------------------------------------------------------------------------------
+// In place on n contiguous u8 H x W masks (blockIdx.x = frame, each on its own): the 8-connected components with
+// fewer than min_area pixels are zeroed and, with keep_largest, every survivor but the largest (ties: the one
+// whose first pixel in row-major order comes first). stats (optional, device): per frame {components found,
+// components kept, pixels kept, pixels removed}. One launch, no workspace. Returns 0, or -1 (nothing launched)
+// unless n >= 1, H, W >= 1, H * W <= 65,536 and min_area >= 0.
+int rdp_mask_components(void* mask, int n, int H, int W, int keep_largest, int min_area, int* stats /* [n][4] or null */,
+                        hipStream_t s);
+
 // ---- csrc/norm_act.hip ----------------------------------------------------------------------------------------
 int rdp_bn_finalize(const float* stats, int T, int C, long count, const float* gamma, const float* beta,
                     float* rmean, float* rvar, long long* nbt, float momentum, float eps, float* coef, float* ws,

@@ -126,6 +126,12 @@ class ServeConfig:
     # models always are. Off until the 4-stream gain is settled for K classes (profiles/serve_multiclass.md).
     # RDP_SERVE_BATCH_MULTICLASS overrides.
     batch_multiclass: bool = False
+    # Component filter of the model-resolution mask, before geometry, coverage and the response mask see it
+    # (geometry/components.py): "largest" keeps only the largest 8-connected component, "all" every one;
+    # components of fewer than ``mask_min_area`` model-resolution pixels are removed first. ("all", 0) = off:
+    # the frame's launches are unchanged. RDP_SERVE_MASK_COMPONENTS / RDP_SERVE_MASK_MIN_AREA override.
+    mask_components: str = "all"
+    mask_min_area: int = 0
     backend: str = "auto"
     graph: bool = True
     devices: str = ""  # comma-separated GPU indices for per-GPU replicas ("" = current device only; "all")

@@ -80,10 +80,11 @@ def prepare_model(dev, train_steps: int = 200, batch: int = 16, n_scenes: int = 
     return model.eval(), scenes
 
 
-def measure_engine(model, scenes, frames: int = 200, warmup: int = 20):
+def measure_engine(model, scenes, frames: int = 200, warmup: int = 20, pipelined: bool = True, **pipeline_args):
+    """``pipeline_args``: further FramePipeline options (scripts/mask_components_bench.py: the component filter)."""
     from ..data.synthetic import DEFAULT_K
     from .engine import FramePipeline
-    p = FramePipeline(model, DEFAULT_K, 0.001, graph=True)
+    p = FramePipeline(model, DEFAULT_K, 0.001, graph=True, **pipeline_args)
     lat, gpu, fit = [], [], []
     ok = 0
     for i in range(warmup + frames):
@@ -104,7 +105,8 @@ def measure_engine(model, scenes, frames: int = 200, warmup: int = 20):
            "engine_gpu_p99_ms": round(_pct(gpu, 99), 3), "engine_frames": len(lat),
            "engine_fit_p50_ms": round(_pct(fit, 50), 3), "engine_ok_frac": ok / max(1, len(lat)),
            "engine_slow_frames": slow_frames(lat, {"gpu": gpu, "fit": fit, "host": host})}
-    out.update(measure_engine_pipelined(model, scenes, frames, warmup))
+    if pipelined:
+        out.update(measure_engine_pipelined(model, scenes, frames, warmup))
     return out
 
 

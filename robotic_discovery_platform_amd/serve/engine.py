@@ -10,6 +10,8 @@ resize -> numpy/scipy geometry -> coverage) with one device program per frame:
                     maxpools fused into the split-K reduces    csrc/conv_igemm.hip, conv_ring.hip
     head mask       1x1 head + (logit > 0) -> u8 256x256, fused into the last conv's epilogue
                     (csrc/conv_ring.hip HEAD; head_mask in csrc/head_loss.hip where it does not apply)
+    mask filter     optional (ServeConfig.mask_components / mask_min_area): small 8-connected components
+                    removed, or only the largest kept, in place on the 256x256 mask   csrc/mask_components.hip
     geo_edges       nearest upsample -> HxW u8 mask + coverage, deproject + compaction + 50-bin
                     top-5 %                                     csrc/geometry.hip
     geo_spline      per-bin x-sort, FITPACK-equivalent spline fit, 100-sample splev + curvature
@@ -41,6 +43,7 @@ import torch
 
 from ..config import GeometryConfig
 from ..data.jpeg import JpegCoefs, JpegScan, coefs_to_rgb_reference, entropy_decode
+from ..geometry.components import check_filter, check_native_size, filter_components_reference
 from ..geometry.curvature import CurvatureResult, GeometryEngine, compute_curvature_profile
 from ..utils import trace
 
@@ -155,20 +158,36 @@ def _check_mask_class(n_classes: int, mask_class: int):
         raise ValueError(f"mask_class {mask_class} outside 0..{n_classes - 1} for a {n_classes}-class model")
 
 
+def mask_filter_at_geo() -> bool:
+    """Where the native pipelines run an active mask component filter: last in the network graph (default: it
+    runs while the depth PNG is still inflating) or, with RDP_SERVE_MASK_FILTER_AT=geo, first in the geometry
+    graph (the A/B of profiles/mask_components.md)."""
+    at = os.environ.get("RDP_SERVE_MASK_FILTER_AT", "net")
+    if at not in ("net", "geo"):
+        raise ValueError(f"RDP_SERVE_MASK_FILTER_AT must be net or geo (got {at!r})")
+    return at == "geo"
+
+
 class FramePipeline:
     """One static-shape (H, W) per-frame program on its own HIP stream (GPU, native kernels)."""
 
     def __init__(self, model, K: np.ndarray, depth_scale: float, H: int = 480, W: int = 640, size: int = 256,
                  threshold: float = 0.5, graph: bool = True, geo_cfg: Optional[GeometryConfig] = None,
                  device: Optional[torch.device] = None, rgb: bool = False, jpeg: bool = False,
-                 jpeg_entropy: Optional[str] = None, mask_class: int = 1):
+                 jpeg_entropy: Optional[str] = None, mask_class: int = 1, mask_components: str = "all",
+                 mask_min_area: int = 0):
         """``threshold``: one-class models (``sigmoid(logit) > threshold``). ``mask_class``: K-class models
-        (``n_classes > 1``): the mask is the pixels whose arg-max class it is; ``threshold`` is not used."""
+        (``n_classes > 1``): the mask is the pixels whose arg-max class it is; ``threshold`` is not used.
+        ``mask_components`` / ``mask_min_area``: the component filter of the model-resolution mask
+        (geometry/components.py), off by default; when active, one launch after the head."""
         from ..models.unet import UNetNative
         if not isinstance(model, UNetNative):
             raise TypeError("FramePipeline needs the native UNet (UNetNative); use CpuFramePipeline otherwise")
         _check_mask_class(model.n_classes, mask_class)
         self.mask_class = int(mask_class)
+        # (keep, min_area), or None when inactive: then no launch and no buffer is added
+        self.mask_filter = check_filter(mask_components, mask_min_area)
+        check_native_size(self.mask_filter, size)
         dev = _norm_device(device if device is not None else model.store.device)
         if dev != _norm_device(model.store.device):
             raise ValueError(f"FramePipeline on {dev} for a model on {model.store.device}: replicate it first")
@@ -199,6 +218,9 @@ class FramePipeline:
         self.d_color = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
         self.d_depth = torch.empty(H, W, dtype=torch.int16, device=dev)
         self.m256 = torch.empty(size * size, dtype=torch.uint8, device=dev)
+        if self.mask_filter is not None:  # [found, kept, pixels kept, pixels removed] of the last frame
+            self.stats = torch.zeros(4, dtype=torch.int32, device=dev)
+            self.filter_at_geo = mask_filter_at_geo()
         self.mask = torch.empty(H, W, dtype=torch.uint8, device=dev)
         ecap = self.cfg.num_bins + int(H * W * self.cfg.top_k_percent) + 1
         self.geo = GeometryEngine(H, W, dev, self.cfg, ecap=ecap)
@@ -303,13 +325,23 @@ class FramePipeline:
             ex.forward(head=False, refresh_eval=False,
                        mask_head=(m.store.flat_slice("outc.conv.weight"), m.store.view("outc.conv.bias"),
                                   self.mask_class, self.m256))
-            return
-        # BN-fold coefficients: see refresh_weights(); the head (+ threshold) is fused into the last conv
-        ex.forward(head=False, refresh_eval=False,
-                   mask_head=(m.store.view("outc.conv.weight").reshape(-1), m.store.view("outc.conv.bias"),
-                              self.thr_logit, self.m256))
+        else:
+            # BN-fold coefficients: see refresh_weights(); the head (+ threshold) is fused into the last conv
+            ex.forward(head=False, refresh_eval=False,
+                       mask_head=(m.store.view("outc.conv.weight").reshape(-1), m.store.view("outc.conv.bias"),
+                                  self.thr_logit, self.m256))
+        if self.mask_filter is not None and not self.filter_at_geo:
+            self._filter_mask()
+
+    def _filter_mask(self):
+        """The component filter on the model-resolution mask, whichever head wrote it: everything downstream
+        (nearest upsample, coverage, geometry, the response mask) sees the filtered mask."""
+        keep, min_area = self.mask_filter
+        self.C.mask_components(self.m256, 1, self.S, self.S, int(keep == "largest"), min_area, self.stats)
 
     def _geo_program(self):
+        if self.mask_filter is not None and self.filter_at_geo:
+            self._filter_mask()
         zc = self.zero_copy
         self.geo.launch_frame(self.m256.view(self.S, self.S), self.mask, self.d_depth, self.K, self.scale,
                               mask_host=self.h_mask if zc else None, host_copy_in_spline=True)
@@ -546,11 +578,15 @@ class BatchEngine:
     def __init__(self, model, K, depth_scale, H: int = 480, W: int = 640, size: int = 256, threshold: float = 0.5,
                  geo_cfg: Optional[GeometryConfig] = None, device: Optional[torch.device] = None, src: int = SRC_JPEG,
                  frames: Optional[int] = None, positions: int = 4, window_us: float = 300.0,
-                 lanes: Optional[int] = None, mask_class: int = 1):
+                 lanes: Optional[int] = None, mask_class: int = 1, mask_components: str = "all",
+                 mask_min_area: int = 0):
         """``mask_class``: K-class models (``n_classes > 1``): the mask is the pixels whose arg-max class it is,
-        as in :class:`FramePipeline`; ``threshold`` is not used then."""
+        as in :class:`FramePipeline`; ``threshold`` is not used then. ``mask_components`` / ``mask_min_area``:
+        the component filter, as in :class:`FramePipeline`: one launch over the batch's masks."""
         _check_mask_class(model.n_classes, mask_class)
         self.mask_class = int(mask_class)
+        self.mask_filter = check_filter(mask_components, mask_min_area)
+        check_native_size(self.mask_filter, size)
         dev = _norm_device(device if device is not None else model.store.device)
         if lanes is None:
             lanes = int(os.environ.get("RDP_BATCH_LANES", "1"))
@@ -631,6 +667,10 @@ class BatchEngine:
         self.m256l = [{n: torch.empty(n * size * size, dtype=torch.uint8, device=dev) for n in range(1, self.P + 1)}
                       for _ in range(lanes)]
         self.ex, self.m256 = self.exl[0], self.m256l[0]
+        if self.mask_filter is not None:  # per (lane, batch size): each position's [found, kept, pixels kept, removed]
+            self.statsl = [{n: torch.zeros(n, 4, dtype=torch.int32, device=dev) for n in range(1, self.P + 1)}
+                           for _ in range(lanes)]
+            self.stats = self.statsl[0]
         self.graphs = {}
         self.refresh_weights()
         for k in range(self.nf):
@@ -717,6 +757,9 @@ class BatchEngine:
             ex.forward(head=False, refresh_eval=False,
                        mask_head=(m.store.view("outc.conv.weight").reshape(-1), m.store.view("outc.conv.bias"),
                                   self.thr_logit, m256))
+        if self.mask_filter is not None:  # every position's mask in one launch, blockIdx = position
+            keep, min_area = self.mask_filter
+            C.mask_components(m256, n, self.S, self.S, int(keep == "largest"), min_area, self.statsl[lane][n])
         S2 = self.S * self.S
 
         if os.environ.get("RDP_BATCH_GEO", "1") != "0":
@@ -995,8 +1038,10 @@ class CpuFramePipeline:
     """Same contract on the CPU: torch (any UNet module) + numpy geometry + native C++ spline."""
 
     def __init__(self, model, K, depth_scale, H: int = 480, W: int = 640, size: int = 256, threshold: float = 0.5,
-                 geo_cfg: Optional[GeometryConfig] = None, mask_class: int = 1, **_):
+                 geo_cfg: Optional[GeometryConfig] = None, mask_class: int = 1, mask_components: str = "all",
+                 mask_min_area: int = 0, **_):
         self.model, self.K, self.scale = model, np.asarray(K, np.float64), float(depth_scale)
+        self.mask_filter = check_filter(mask_components, mask_min_area)  # (keep, min_area), None when inactive
         self.H, self.W, self.S, self.thr = H, W, size, threshold
         # K-class models: the mask is arg-max == mask_class (checked against the model's class count when
         # it is known here, else against the output's on the first frame); one-class models ignore it
@@ -1055,6 +1100,9 @@ class CpuFramePipeline:
             m = (out.float().argmax(1) == self.mask_class)[0].cpu().numpy().astype(np.uint8)
         else:
             m = (torch.sigmoid(out.float()) > self.thr)[0, 0].cpu().numpy().astype(np.uint8)
+        self.m_model = m  # the model-resolution mask before the component filter
+        if self.mask_filter is not None:
+            m, self.stats = filter_components_reference(m, *self.mask_filter)
         mask = resize_nearest(m, (color_bgr.shape[1], color_bgr.shape[0]))
         t1 = time.perf_counter()
         res = compute_curvature_profile(mask, depth, self.K, self.scale, self.cfg, device="cpu")
@@ -1112,14 +1160,18 @@ class EnginePool:
     def __init__(self, model, K, depth_scale, H: int = 480, W: int = 640, size: int = 256, n: int = 2,
                  threshold: float = 0.5, graph: bool = True, geo_cfg: Optional[GeometryConfig] = None,
                  devices=None, rgb: bool = False, jpeg: bool = False, max_sizes: int = 3, batch: Optional[int] = None,
-                 jpeg_entropy: Optional[str] = None, mask_class: int = 1, batch_multiclass: Optional[bool] = None):
+                 jpeg_entropy: Optional[str] = None, mask_class: int = 1, batch_multiclass: Optional[bool] = None,
+                 mask_components: str = "all", mask_min_area: int = 0):
         self.model = model
         self.home_size = (H, W)
         self.max_sizes = max(0, max_sizes)
         self.rgb = rgb  # channel order of the frames this pool will be fed (graphs captured for it)
         # mask_class: the served class of a K-class model (ServeConfig.mask_class; one-class models ignore it)
+        # mask_components / mask_min_area: the component filter (ServeConfig; geometry/components.py). In args, so
+        # per-stream pipelines, batch engines and pipelines built later for another frame size all get them
+        self.mask_filter = check_filter(mask_components, mask_min_area)
         self.args = dict(K=K, depth_scale=depth_scale, size=size, threshold=threshold, geo_cfg=geo_cfg,
-                         mask_class=mask_class)
+                         mask_class=mask_class, mask_components=mask_components, mask_min_area=int(mask_min_area))
         multi = int(getattr(model, "n_classes", 1)) > 1
         self.graph = graph
         self.n = max(1, n)

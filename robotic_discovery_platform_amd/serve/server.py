@@ -641,7 +641,10 @@ def build_server(cfg: ServeConfig, device: Optional[torch.device] = None, pool_s
     engine = EnginePool(model, K, ds, n=pool_size or cfg.replicas_per_device, threshold=cfg.mask_threshold,
                         graph=cfg.graph, size=cfg.model_img_size, devices=devices, rgb=True,
                         jpeg=cfg.gpu_jpeg and _is_native(model), jpeg_entropy=cfg.jpeg_entropy,
-                        mask_class=cfg.mask_class, batch_multiclass=cfg.batch_multiclass)
+                        mask_class=cfg.mask_class, batch_multiclass=cfg.batch_multiclass,
+                        mask_components=cfg.mask_components, mask_min_area=cfg.mask_min_area)
+    if engine.mask_filter is not None:
+        log.info("mask component filter: keep=%s min_area=%d (model-resolution pixels)", *engine.mask_filter)
     service = VisionAnalysisService(engine, metrics, frame_errors=cfg.frame_errors, faults=faults)
     server = grpc.server(futures.ThreadPoolExecutor(max_workers=cfg.max_workers))
     pb.add_VisionAnalysisServiceServicer_to_server(service, server)
