@@ -499,20 +499,20 @@ float* ws_ptr(const c10::optional<torch::Tensor>& ws, int K) {
   return ws->data_ptr<float>();
 }
 
-// stats slab rows written by conv_fwd: one per (M tile, wave row)
-int conv_stats_rows(long M, int Cout, int bm_pref) {
-  bm_pref %= 1000;
-  // forced tiles: one row per (M tile, wave row), or up to 512 rows when split-K reduces them
-  if (bm_pref == 128 && Cout % 128 == 0) return (int)std::max<long>((M + 127) / 128 * 2, 512);
-  if (bm_pref == 256) return (int)std::max<long>((M + 255) / 256 * 4, 512);
-  // auto / halo: upper bound over every tile choice (halo: up to 8 wave rows per 256-pixel tile)
-  // split-K reduce: up to 512 rows
-  const long a = (M + 127) / 128 * 2, b = (M + 255) / 256 * 8;
-  const long ab = a > b ? a : b;
-  // + room for batch-chunked launches (conv_fwd: tensors past 2 GiB run as image slices, each with
-  // its own 512-row floor and tile rounding): one chunk per 2 GiB of a 1024-channel bf16 tensor
-  const long chunks = 1 + M * 2048 / (1L << 31);
-  return (int)((ab > 512 ? ab : 512) + 520 * chunks);
+// The plan of a dense conv of this shape, as a dict (kernel: the RdpConvKernel value, -1 = unsupported)
+py::dict conv_plan(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed, int kernel, bool stats,
+                   bool eval, int split, long ws_elems, bool pool, bool up, bool bn, bool wfrag) {
+  RdpConvQuery q;
+  q.N = N; q.H = H; q.W = W; q.C1 = C1; q.C2 = C2; q.Cout = Cout; q.taps = taps; q.packed = packed; q.kernel = kernel;
+  q.stats = stats; q.eval = eval; q.split = split; q.ws_elems = ws_elems; q.pool = pool; q.up = up; q.bn = bn;
+  q.wfrag = wfrag;
+  const RdpConvPlan p = rdp_conv_plan_dense(q);
+  py::dict d;
+  d["kernel"] = p.kernel; d["name"] = rdp_conv_kernel_name(p.kernel);
+  d["bm"] = p.BM; d["bn"] = p.BN; d["waves"] = p.waves; d["ksplit"] = p.ksplit; d["rowband_mode"] = p.rowband_mode;
+  d["launches"] = p.launches; d["grid"] = p.grid; d["reduce_grid"] = p.rgrid; d["stats_rows"] = p.stats_rows;
+  d["ws_elems"] = p.ws_elems; d["pool_fused"] = p.pool_fused; d["up_fused"] = p.up_fused; d["bn_rows"] = p.bn_rows;
+  return d;
 }
 
 // y = conv(cat(x1, x2), w); returns #M-tiles (stats rows)
@@ -536,7 +536,7 @@ int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w,
   if (stats) {
     check_f32(*stats, "stats");
     const long M = (long)a1.N * a1.H * a1.W;
-    const long rows = conv_stats_rows(M, Cout, bm_pref);
+    const long rows = rdp_conv_stats_rows(M, Cout, bm_pref);
     TORCH_CHECK(stats->numel() >= rows * 2 * Cout, "stats slab too small");
     sp = stats->data_ptr<float>();
   }
@@ -574,7 +574,7 @@ int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w,
   int rows = 0;
   for (int n0 = 0; n0 < a1.N; n0 += nc) {
     const int nn = std::min(nc, a1.N - n0);
-    if (sp) TORCH_CHECK(rows + conv_stats_rows((long)nn * a1.H * a1.W, Cout, bm_pref) <= avail_rows, "stats slab too small");
+    if (sp) TORCH_CHECK(rows + rdp_conv_stats_rows((long)nn * a1.H * a1.W, Cout, bm_pref) <= avail_rows, "stats slab too small");
     // every launch argument is a value here (the blocks are captured by copy): RDP_PLAN may keep the launch for
     // replay (plan mode)
     RdpConv c;
@@ -597,28 +597,14 @@ int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w,
     const bool want_fused = pool || up;
     // the fused pool / upsample result flag: a heap cell owned by the launch (kept alive in a plan)
     auto pooled = std::make_shared<int>(0);
-    // eval with the fragment-major weight copy (wfrag): the row-band kernel wherever its traffic model picks it
-    const int fmode = wfrag && esc && !sp && !y2 && taps == 9 && !packed && bm_pref == 0
-                          ? rdp_conv_rowband_frag_auto(nn, a1.H, a1.W, a1.C, c.C2, Cout) : 0;
-    int r = -1;
-    if (fmode > 0) {
-      RdpConv cf = c;
-      cf.w = wfrag->data_ptr(); cf.wbytes = wfrag->numel() * 2; cf.ldw = 0;
-      const long pbytes = pool ? po.span_bytes(nn) : 0;
-      const int rb = RDP_PLAN(rdp_conv_rowband_ex(cf, fuse.pool, pbytes, fuse.ppitch, fmode, st));
-      // the selector checks every predicate of the launch; should one still reject (rb < 0: nothing was
-      // launched), the layer runs on the implicit GEMM below instead of failing the eval
-      if (rb >= 0) {
-        *pooled = rb == 1 ? 1 : 0;
-        r = 0;
-      }
-    }
-    if (r < 0) {
-      // `pooled` is named inside the closure so that a recorded launch owns the cell it writes on every replay
-      r = RDP_PLAN(rdp_conv_igemm(c, taps, packed, bm_pref, wsp, wsn, fuse, want_fused ? pooled.get() : nullptr,
-                                  RdpConvBnBwd{}, nullptr, st));
-    }
-    TORCH_CHECK(r >= 0, "conv_fwd: unsupported shape (C1=", a1.C, ", C2=", c.C2, ", Cout=", Cout, ")");
+    // wfrag (eval): the fragment-major copy of w, for the row-band kernel where the dispatcher picks it
+    const void* const wfp = wfrag ? wfrag->data_ptr() : nullptr;
+    const long wfn = wfrag ? (long)wfrag->numel() * 2 : 0L;
+    // `pooled` is named inside the closure so that a recorded launch owns the cell it writes on every replay
+    const int r = RDP_PLAN(rdp_conv_igemm(c, taps, packed, bm_pref, wsp, wsn, wfp, wfn, fuse,
+                                          want_fused ? pooled.get() : nullptr, RdpConvBnBwd{}, nullptr, st));
+    TORCH_CHECK(r >= 0, "conv_fwd: no kernel for this conv (C1=", a1.C, ", C2=", c.C2, ", Cout=", Cout, ", kernel=",
+                rdp_conv_kernel_name(bm_pref), " (", bm_pref, "))");
     void* const py1 = c.y1;
     const int oH = o1.H, oW = o1.W, oC = o1.C, op1 = o1.pitch;
     if (pool && !*pooled)
@@ -782,7 +768,7 @@ int conv_dgrad_splitk_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx,
   // the row-count cell: owned by the launch; `rows` is named inside the closure so that a recorded launch keeps
   // the cell it writes on every replay alive
   auto rows = std::make_shared<int>(0);
-  const int r = RDP_PLAN(rdp_conv_igemm(c, 9, 0, 0, wsp, wsn, RdpConvFuse{}, nullptr, bn, rows.get(), st));
+  const int r = RDP_PLAN(rdp_conv_igemm(c, 9, 0, RDP_CONV_AUTO, wsp, wsn, nullptr, 0, RdpConvFuse{}, nullptr, bn, rows.get(), st));
   TORCH_CHECK(r >= 0, "conv_dgrad_splitk_bnred: unsupported shape (Cin=", a.C, ", Cout=", o.C, ")");
   return *rows;
 }
@@ -2066,10 +2052,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("y1"), py::arg("y2"), py::arg("stats"), py::arg("bm_pref"), py::arg("affine"), py::arg("relu"),
         py::arg("ws") = py::none(), py::arg("pool") = py::none(), py::arg("up") = py::none(),
         py::arg("up_oy") = 0, py::arg("up_ox") = 0, py::arg("wfrag") = py::none());
-  m.def("conv_ws_elems", [](int N, int H, int W, int C1, int C2, int Cout, int taps, int packed, int bm_pref) {
-    return rdp_conv_ws_elems(N, H, W, C1, C2, Cout, taps, packed, bm_pref);
-  });
-  m.def("conv_stats_rows", &conv_stats_rows);
+  m.def("conv_ws_elems", &rdp_conv_ws_elems);
+  m.def("conv_stats_rows", &rdp_conv_stats_rows);
+  // the kernels conv_fwd's bm_pref may name (csrc/conv_plan.h RdpConvKernel), as plain ints
+  for (int i = 0; i < rdp_conv_kernel_count; ++i)
+    m.attr((std::string("CONV_") + rdp_conv_kernel_names[i].name).c_str()) = rdp_conv_kernel_names[i].kernel;
+  m.def("conv_plan", &conv_plan, py::arg("n"), py::arg("h"), py::arg("w"), py::arg("c1"), py::arg("c2"), py::arg("cout"),
+        py::arg("taps") = 9, py::arg("packed") = 0, py::arg("kernel") = 0, py::arg("stats") = false,
+        py::arg("eval") = false, py::arg("split") = 0, py::arg("ws_elems") = 0, py::arg("pool") = false,
+        py::arg("up") = false, py::arg("bn") = false, py::arg("wfrag") = false,
+        "host only, launches nothing: what conv_fwd would run for a dense conv of this shape (rdp_conv_plan)");
   m.def("conv_wgrad", on_device(&conv_wgrad), py::arg("x1"), py::arg("x2"), py::arg("dy"), py::arg("taps"),
         py::arg("packed"), py::arg("cin_real"), py::arg("slab"), py::arg("out"), py::arg("accumulate"),
         py::arg("splits"), py::arg("variant"));
@@ -2131,7 +2123,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_rowband_chain", on_device(&conv_rowband_chain));
   m.def("conv_rowband", on_device(&conv_rowband));
   // host-only: the eval conv's row-band mode for a shape (0 = implicit GEMM), the same decision conv_fwd takes
-  m.def("rowband_frag_mode", &rdp_conv_rowband_frag_auto, py::arg("n"), py::arg("h"), py::arg("w"), py::arg("c1"),
+  m.def("rowband_frag_mode", &rdp_rowband_frag_mode, py::arg("n"), py::arg("h"), py::arg("w"), py::arg("c1"),
         py::arg("c2"), py::arg("cout"));
   m.def("adam", on_device(&adam), py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("lr"),
         py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("gscale"), py::arg("step"),

@@ -19,8 +19,6 @@
 //     then the block's 4 wave rows are summed through LDS into ONE stats row per block.
 #include "common.h"
 #include "rdp_api.h"
-#include <algorithm>
-#include <stdlib.h>
 
 struct FirstArgs {
   const u16* x;  // [M][pitch], channels 0..3 read (3..7 are the zero pad of the 3-channel input)
@@ -182,19 +180,17 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const FirstArgs a) {
 }
 
 extern "C" int rdp_conv_first(const RdpConv& c, hipStream_t s) {
-  if (c.pitch1 < 4 || c.wbytes < 64l * 128 * 2 || c.ypitch1 < 64 || c.ypitch1 % 8) return -1;
-  if (c.xbytes1 >= (1l << 31) || c.ybytes1 >= (1l << 31)) return -1;
+  const RdpFirstGeo g = rdp_first_geo(c, 9, 1);
+  if (!g.fits) return -1;
   FirstArgs a;
   a.x = (const u16*)c.x1; a.xbytes = (uint32_t)c.xbytes1; a.pitch = c.pitch1;
   a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes;
   a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
   a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
   a.H = c.H; a.W = c.W; a.M = c.N * c.H * c.W;
-  a.nseg = (a.M + 63) / 64;
+  a.nseg = g.nseg;
   const FastDiv fhw = make_fastdiv((uint32_t)(c.H * c.W)), fw = make_fastdiv((uint32_t)c.W);
   a.fhw_m = fhw.m; a.fhw_s = fhw.s; a.fw_m = fw.m; a.fw_s = fw.s;
-  // grid <= nseg / 4 keeps the stats rows within conv_stats_rows() (>= M / 32 rows)
-  const int grid = std::max(1, std::min((a.nseg + 3) / 4, 512));
-  hipLaunchKernelGGL(conv_first_kernel, dim3(grid), dim3(256), 0, s, a);
-  return c.stats ? grid : 0;
+  hipLaunchKernelGGL(conv_first_kernel, dim3(g.grid), dim3(256), 0, s, a);
+  return g.rows;
 }

@@ -304,34 +304,13 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void conv_halo_kernel(const HaloAr
 }
 
 template <int TC, int TR, int WM, int WN>
-static int halo_launch(HaloArgs a, hipStream_t s) {
-  a.tilesH = a.H / TR;
-  a.tilesW = a.W / TC;
-  a.tilesN = a.Cout / (64 * WN);
-  const int tilesM = a.N * a.tilesH * a.tilesW;
-  a.ntiles = tilesM * a.tilesN;
-  const int grid = a.ntiles < 256 ? a.ntiles : 256;
+static void halo_launch(const HaloArgs& a, int grid, hipStream_t s) {
   hipLaunchKernelGGL((conv_halo_kernel<TC, TR, WM, WN>), dim3(grid), dim3(64 * WM * WN), 0, s, a);
-  return tilesM * WM;
-}
-
-extern "C" int rdp_conv_halo_tiles(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed) {
-  if (taps != 9 || packed || C1 % 64 || C2 % 64 || C1 == 0 || Cout % 64) return 0;
-  int tc, tr;
-  if (W % 64 == 0 && H % 4 == 0) { tc = 64; tr = 4; }
-  else if (W % 32 == 0 && H % 8 == 0) { tc = 32; tr = 8; }
-  else if (W % 16 == 0 && H % 16 == 0) { tc = 16; tr = 16; }
-  else return 0;
-  const int wn = Cout % 128 == 0 ? 2 : 1;
-  return N * (H / tr) * (W / tc) * (Cout / (64 * wn));
 }
 
 extern "C" int rdp_conv_halo(const RdpConv& c, hipStream_t s) {
-  if (!rdp_conv_halo_tiles(c.N, c.H, c.W, c.C1, c.C2, c.Cout, 9, 0)) return -1;
-  if (c.ldw < 9 * (c.C1 + c.C2) || c.Cy1 % 4) return -1;
-  if (c.xbytes1 >= (1l << 31) || c.xbytes2 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.ybytes2 >= (1l << 31) ||
-      c.wbytes >= (1l << 31))
-    return -1;
+  const RdpHaloGeo g = rdp_halo_geo(c, 9, 0);
+  if (!g.fits) return -1;
   HaloArgs a;
   a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
   a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
@@ -342,9 +321,10 @@ extern "C" int rdp_conv_halo(const RdpConv& c, hipStream_t s) {
   a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
   a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout;
   a.nchunks = (c.C1 + c.C2) / 64;
-  const bool wide = c.Cout % 128 == 0;
-  // 8 waves per block either way (2 per SIMD): BN=128 -> 4 (pixels) x 2 (couts), BN=64 -> 8 x 1
-  if (c.W % 64 == 0 && c.H % 4 == 0) return wide ? halo_launch<64, 4, 4, 2>(a, s) : halo_launch<64, 4, 8, 1>(a, s);
-  if (c.W % 32 == 0 && c.H % 8 == 0) return wide ? halo_launch<32, 8, 4, 2>(a, s) : halo_launch<32, 8, 8, 1>(a, s);
-  return wide ? halo_launch<16, 16, 4, 2>(a, s) : halo_launch<16, 16, 8, 1>(a, s);
+  a.tilesH = g.tilesH; a.tilesW = g.tilesW; a.tilesN = g.tilesN; a.ntiles = g.ntiles;
+  const bool wide = g.WN == 2;
+  if (g.TC == 64) wide ? halo_launch<64, 4, 4, 2>(a, g.grid, s) : halo_launch<64, 4, 8, 1>(a, g.grid, s);
+  else if (g.TC == 32) wide ? halo_launch<32, 8, 4, 2>(a, g.grid, s) : halo_launch<32, 8, 8, 1>(a, g.grid, s);
+  else wide ? halo_launch<16, 16, 4, 2>(a, g.grid, s) : halo_launch<16, 16, 8, 1>(a, g.grid, s);
+  return g.rows;
 }

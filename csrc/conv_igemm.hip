@@ -25,7 +25,6 @@
 // 64-channel layers. The epilogue uses no LDS and no block barrier.
 #include "common.h"
 #include "rdp_api.h"
-#include <stdlib.h>
 
 struct ConvArgs {
   const u16* x1;
@@ -76,12 +75,6 @@ struct ConvArgs {
   int bnypitch = 0;
   int* bnrows = nullptr;  // host cell: the partial rows written (set when the split-K reduce ran)
 };
-
-// 128 -> 128 convs as two two-source-ring launches where the ring grid is at least this large. Measured
-// (scripts/conv_microbench.py --shapes 2, one MI355X): 128^2 128 -> 128 at bs 64 330.5 vs 368.9 us for the
-// 256 x 128 ping-pong kernel, but 106.8 vs 98.5 at bs 16 and 45.8 vs 28.3 at bs 4 (each launch reads the
-// whole input); bs-64 step 19.43 / 19.55 vs 19.47 / 19.61 ms (interleaved).
-constexpr long RING2_X2_PAIRS = 4096;
 
 // tap (0..8) -> (dr, ds) without division: dr + 1 = (tap * 11) >> 5
 RDP_DEV int tap_dr(int tap) { return ((tap * 11) >> 5) - 1; }
@@ -735,44 +728,40 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const ConvArgs a) {
   }
 }
 
-static int launch_split_reduce(const ConvArgs& a, hipStream_t s, int* pooled);
+// what the plan's geometry functions (conv_plan.h) see of a filled ConvArgs
+static RdpGemmShape gemm_shape(const ConvArgs& a) {
+  RdpGemmShape g;
+  g.M = a.M; g.Cout = a.Cout; g.Cy1 = a.Cy1; g.nks = a.nks; g.packed = a.packed; g.stats = a.stats != nullptr;
+  g.N = a.N; g.uH = a.up ? a.uH : 0;
+  return g;
+}
+static RdpConvFuseOk fuse_of(const ConvArgs& a) { return {a.pool != nullptr, a.up != nullptr, a.bnpart != nullptr}; }
 
-// ksplit > 1 (a.kslab set, ksplit divides nks, slab within 2 GiB -- the caller's plan): fp32
-// partial tiles, then the shared split-K reduce (stats / eval epilogue / fused pool or upsample).
+static int launch_split_reduce(const ConvArgs& a, const RdpIgemmGeo& g, hipStream_t s, int* pooled);
+
+// ksplit > 1 (rdp_pp_split's d, a.kslab set): fp32 partial tiles, then the shared split-K reduce (stats / eval
+// epilogue / fused pool or upsample).
 template <int BN>
 static int launch_pp(ConvArgs a, hipStream_t s, int ksplit = 1, int* pooled = nullptr) {
-  constexpr int BM = 256;
-  if (a.packed || a.Cout % BN || a.Cy1 % 32) return -1;
-  const int tilesM = (a.M + BM - 1) / BM;
-  a.tilesN = a.Cout / BN;
-  a.ntiles = tilesM * a.tilesN;
-  if (ksplit > 1) {
-    if (!a.kslab || a.nks % ksplit) return -1;
-    a.ksplit = ksplit;
-    a.nks /= ksplit;
-    a.ntiles *= ksplit;
+  const RdpIgemmGeo g = rdp_pp_geo(gemm_shape(a), BN, ksplit, a.kslab != nullptr, fuse_of(a));
+  if (!g.fits) return -1;
+  a.tilesN = g.tilesN; a.ntiles = g.ntiles; a.ksplit = g.ksplit; a.nks = g.nks;
+  if (g.ksplit > 1) {
     ConvArgs k = a;
     k.stats = nullptr;  // statistics come from the reduce
-    const int grid = k.ntiles < 256 ? k.ntiles : 256;
-    hipLaunchKernelGGL((conv_pp_kernel<BN, true>), dim3(grid), dim3(512), 0, s, k);
-    return launch_split_reduce(a, s, pooled);
+    hipLaunchKernelGGL((conv_pp_kernel<BN, true>), dim3(g.grid), dim3(512), 0, s, k);
+    return launch_split_reduce(a, g, s, pooled);
   }
-  a.ksplit = 1;
   a.pool = nullptr;
   a.up = nullptr;
   if (a.tlc || a.taps == 4) {  // ConvTranspose2d output (rdp_conv_upT_fwd) / input gradient (rdp_conv_upT_dgrad)
     if (a.stats || a.escale || a.y2) return -1;
-    const int grid = a.ntiles < 256 ? a.ntiles : 256;
-    if (a.tlc) hipLaunchKernelGGL((conv_pp_kernel<BN, false, true>), dim3(grid), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((conv_pp_kernel<BN, false, false, true>), dim3(grid), dim3(512), 0, s, a);
+    if (a.tlc) hipLaunchKernelGGL((conv_pp_kernel<BN, false, true>), dim3(g.grid), dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((conv_pp_kernel<BN, false, false, true>), dim3(g.grid), dim3(512), 0, s, a);
     return 0;
   }
-  // one persistent block per CU (512 blocks or one block per tile, which let the dispatcher balance
-  // the tiles around the concurrent wgrads, measured 0.8 % / 1.7 % slower: profiles/dead_ends.md)
-  const int grid = a.ntiles < 256 ? a.ntiles : 256;
-  if (a.stats && grid % a.tilesN) return -1;
-  hipLaunchKernelGGL((conv_pp_kernel<BN>), dim3(grid), dim3(512), 0, s, a);
-  return grid / a.tilesN * 2;
+  hipLaunchKernelGGL((conv_pp_kernel<BN>), dim3(g.grid), dim3(512), 0, s, a);
+  return g.rows;
 }
 
 extern "C" int rdp_conv_upT_fwd(const void* x, long xbytes, int Cin, int pitch, const void* w, long wbytes, int ldw,
@@ -827,22 +816,6 @@ extern "C" int rdp_conv_upT_dgrad(const void* du, long dubytes, int C, int dupit
 }
 
 
-
-// Eval convs on small maps run on the row-band kernel (csrc/conv_rowband.hip) where its operand traffic
-// model says it wins (<= 160 MB; a pool it cannot fuse would cost a separate launch): RDP_ROWBAND=0 turns
-// the auto choice off (A/B); bm_pref 16 forces it.
-static bool rowband_auto(int N, int H, int W, int Cin, int Cout, bool pool) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("RDP_ROWBAND");
-    on = e ? atoi(e) : 1;
-  }
-  if (on == 0 || (long)N * H * W > 4096 || W > 64 || Cin < 128 || Cout < 64) return false;
-  if (pool && !(H % 2 == 0 && 2 * W <= 64)) return false;
-  // (the estimate without the pool's two-row blocks: with or without a pool the same kernel runs, so the
-  // two calls give bitwise the same activations)
-  return rdp_conv_rowband_bytes(N, H, W, Cin, Cout, 0) <= 160000000L;
-}
 
 // Split-K reduction + epilogue: y[m][n] = epi(sum_s slab[s][m][n]); optional BN-stats rows (one per
 // block). Thread = fixed 4-channel group (epilogue coefficients in registers), rows grid-strided.
@@ -966,8 +939,8 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvArgs 
 // two bands are written twice with equal values) -- into LDS as bf16; phase 2 interpolates the output
 // rows from LDS with the arithmetic of upsample2_fwd_kernel (csrc/pool_up.hip). The low-res tensor is
 // never re-read from memory and the upsample launch disappears.
-#define UP_TY 4
-#define UP_CG 16
+#define UP_TY RDP_UP_TY
+#define UP_CG RDP_UP_CG
 RDP_DEV void up_src_f(int u, int in, float r, int& i0, int& i1, float& l1) {  // = up_src (pool_up.hip)
   const float sv = r * (float)u;
   i0 = (int)sv;
@@ -1053,164 +1026,100 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_up_kernel(const ConvAr
   }
 }
 
-// The reduce + epilogue launch after a split-K conv: returns the stats rows written (0 with the fused
-// upsample / pool, whose *pooled is set)
-static int launch_split_reduce(const ConvArgs& a, hipStream_t s, int* pooled) {
-  const int rpb = 256 / (a.Cout / 4);
-  int nblk = (a.M + rpb - 1) / rpb;  // <= 512 stats rows: within conv_stats_rows()'s bound
-  nblk = nblk < 512 ? nblk : 512;
-  if (a.up) {  // fused eval upsample: bands of UP_TY output rows x UP_CG channels
-    const int nb = (a.uH + UP_TY - 1) / UP_TY;
+// The reduce + epilogue launch after a split-K conv (g: its geometry): returns the rows it reports; *pooled is set
+// where it wrote the fused pool / upsample
+static int launch_split_reduce(const ConvArgs& a, const RdpIgemmGeo& g, hipStream_t s, int* pooled) {
+  if (g.up) {  // fused eval upsample: bands of UP_TY output rows x UP_CG channels
     const size_t lds = (size_t)(UP_TY / 2 + 2) * a.W * UP_CG * 2;
-    hipLaunchKernelGGL(conv_splitk_reduce_up_kernel, dim3(a.N * nb, a.Cout / UP_CG), dim3(256), lds, s, a);
+    hipLaunchKernelGGL(conv_splitk_reduce_up_kernel, dim3(g.rgrid, g.rgrid_y), dim3(256), lds, s, a);
     if (pooled) *pooled = 1;
-    return 0;
+    return g.rows;
   }
-  if (a.pool) {  // fused eval MaxPool2d(2): one work row per 2x2 window, no stats rows
-    nblk = (a.M / 4 + rpb - 1) / rpb;
-    nblk = nblk < 2048 ? nblk : 2048;
-    if (pooled) *pooled = 1;
-  }
-  const bool bnr = !a.stats && a.bnpart && !a.pool;
-  const size_t lds = (a.stats || bnr) ? (size_t)rpb * 2 * a.Cout * sizeof(float) : 0;
-  hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(nblk), dim3(256), lds, s, a, nblk);
-  if (bnr && a.bnrows) *a.bnrows = nblk;
-  return nblk;
-}
-
-// Split-K when the tile grid leaves most CUs idle: the smallest divisor of the K steps that gives
-// >= 256 work items with >= 4 K steps each, as long as the fp32 slab fits `ws_elems`.
-static int choose_ksplit(int ntiles, int nks, int M, int Cout, int packed, long ws_elems) {
-  const bool pow2 = Cout >= 64 && Cout <= 1024 && (Cout & (Cout - 1)) == 0;  // reduce kernel's groups
-  int ks = 1;
-  if (!pow2 || packed || ntiles >= 192) return 1;
-  for (int d = 2; d <= nks / 4; ++d) {
-    if (nks % d) continue;
-    if ((long)d * M * Cout > ws_elems) break;
-    ks = d;
-    if (ntiles * d >= 256) break;
-  }
-  return ks;
-}
-
-// Split-K ping-pong plan for the small-M / long-K convs (reference-batch training, deep layers): the
-// 256 x BN tile grid alone leaves most CUs idle, so the K steps are split over d work items (the
-// smallest divisor of nks giving >= 256 items, one block per CU, each >= PP_SPLIT_MIN_KS K steps)
-// when the fp32 slab d * M * Cout fits. Returns d (0: no split-K ping-pong plan).
-constexpr int PP_SPLIT_MIN_KS = 8;
-static int pp_split_plan(int M, int Cout, int BN, int nks, long ws_elems) {
-  // (the split-K reduce kernel maps a power-of-two channel count, 64..1024, onto its threads)
-  if (Cout % BN || Cout > 1024 || (Cout & (Cout - 1))) return 0;
-  const long tiles = (long)(M + 255) / 256 * (Cout / BN);
-  if (tiles >= 256) return 0;
-  for (int d = 2; d <= nks / PP_SPLIT_MIN_KS; ++d) {
-    if (nks % d) continue;
-    if ((long)d * M * Cout > ws_elems) return 0;
-    if (tiles * d >= 256) return d;
-  }
-  return 0;
-}
-
-static bool pp_split_enabled() {  // RDP_PP_SPLIT=0: the 128 x 128 split-K kernel instead (A/B)
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("RDP_PP_SPLIT");
-    on = e ? atoi(e) != 0 : 1;
-  }
-  return on != 0;
+  if (g.pool && pooled) *pooled = 1;  // fused eval MaxPool2d(2): one work row per 2x2 window
+  const int rpb = 256 / (a.Cout / 4);
+  const size_t lds = (a.stats || g.bn) ? (size_t)rpb * 2 * a.Cout * sizeof(float) : 0;
+  hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(g.rgrid), dim3(256), lds, s, a, g.rgrid);
+  if (g.bn && a.bnrows) *a.bnrows = g.rows;
+  return g.rows;
 }
 
 template <int BM, int BN, int NWV = 4>
-static int launch_cfg(ConvArgs a, int max_blocks, long ws_elems, hipStream_t s, int* pooled = nullptr) {
-  const int tilesM = (a.M + BM - 1) / BM;
-  a.tilesN = a.Cout / BN;
-  a.ntiles = tilesM * a.tilesN;
-  a.ksplit = a.kslab ? choose_ksplit(a.ntiles, a.nks, a.M, a.Cout, a.packed, ws_elems) : 1;
-  if (a.ksplit > 1) {
-    a.nks /= a.ksplit;
-    a.ntiles *= a.ksplit;
-    const int grid = a.ntiles < max_blocks ? a.ntiles : max_blocks;
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, NWV>), dim3(grid), dim3(64 * NWV), 0, s, a);
-    return launch_split_reduce(a, s, pooled);
+static int launch_cfg(ConvArgs a, long ws_limit, hipStream_t s, int* pooled = nullptr) {
+  const RdpIgemmGeo g = rdp_igemm_geo(gemm_shape(a), BM, BN, a.kslab ? ws_limit : 0, 512, fuse_of(a));
+  if (!g.fits) return -1;
+  a.tilesN = g.tilesN; a.ntiles = g.ntiles; a.ksplit = g.ksplit; a.nks = g.nks;
+  if (g.ksplit > 1) {
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, NWV>), dim3(g.grid), dim3(64 * NWV), 0, s, a);
+    return launch_split_reduce(a, g, s, pooled);
   }
   a.pool = nullptr;  // the non-split epilogue does not pool / upsample (the caller launches them)
   a.up = nullptr;
-  const int grid = a.ntiles < max_blocks ? a.ntiles : max_blocks;
-  // the per-block stats rows need every block to keep one channel tile (see the kernel)
-  if (a.stats && grid % a.tilesN) return -1;
-  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, NWV>), dim3(grid), dim3(64 * NWV), 0, s, a);
-  return grid / a.tilesN * (BM / 64);
+  hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, NWV>), dim3(g.grid), dim3(64 * NWV), 0, s, a);
+  return g.rows;
 }
 
-extern "C" int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int bm_pref, float* ws, long ws_elems,
-                              const RdpConvFuse& fuse, int* pooled, const RdpConvBnBwd& bn, int* bnrows,
-                              hipStream_t s) {
+// The one RdpConv -> ConvArgs fill. ws: the split-K fp32 slab or nullptr; the fused pool / upsample / BN-backward
+// operands are set where rdp_conv_fuse_ok allows them (they act only if the launch splits K).
+static ConvArgs conv_args(const RdpConv& c, int taps, int packed, float* ws, const RdpConvFuse& fuse, int* pooled,
+                          const RdpConvBnBwd& bn, int* bnrows) {
+  const RdpConvFuseOk ok = rdp_conv_fuse_ok(c, fuse, pooled != nullptr, bn);
+  ConvArgs a;
+  a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
+  a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
+  a.C1 = c.C1; a.C2 = c.C2; a.pitch1 = c.pitch1; a.pitch2 = c.pitch2;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
+  a.y1 = (u16*)c.y1; a.y2 = (u16*)c.y2; a.ybytes1 = (uint32_t)c.ybytes1; a.ybytes2 = (uint32_t)c.ybytes2;
+  a.Cy1 = c.Cy1; a.ypitch1 = c.ypitch1; a.ypitch2 = c.ypitch2; a.stats = c.stats;
+  a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.M = c.N * c.H * c.W;
+  a.taps = taps; a.packed = packed;
+  a.cpt = packed ? 1 : (c.C1 + c.C2) / 64;
+  a.nks = packed ? 2 : taps * a.cpt;
+  a.ksplit = 1;
+  a.kslab = ws;
+  a.pool = ok.pool ? (u16*)fuse.pool : nullptr;
+  a.ppitch = fuse.ppitch;
+  a.up = ok.up ? (u16*)fuse.up : nullptr;
+  a.upitch = fuse.upitch; a.uH = fuse.uH; a.uW = fuse.uW; a.uoy = fuse.uoy; a.uox = fuse.uox;
+  a.urh = 2 * c.H > 1 ? (float)(c.H - 1) / (float)(2 * c.H - 1) : 0.f;  // = ac_scale (pool_up.hip)
+  a.urw = 2 * c.W > 1 ? (float)(c.W - 1) / (float)(2 * c.W - 1) : 0.f;
+  if (ok.bn) {
+    a.bny = (const u16*)bn.bny; a.bnypitch = bn.bnypitch; a.bncoef = bn.bncoef; a.bnpart = bn.bnpart;
+    a.bnrows = bnrows;
+  }
+  const FastDiv fhw = make_fastdiv((uint32_t)(c.H * c.W)), fw = make_fastdiv((uint32_t)c.W);
+  a.fhw_m = fhw.m; a.fhw_s = fhw.s; a.fw_m = fw.m; a.fw_s = fw.s;
+  return a;
+}
+
+extern "C" int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int kernel, float* ws, long ws_elems,
+                              const void* wfrag, long wfrag_bytes, const RdpConvFuse& fuse, int* pooled,
+                              const RdpConvBnBwd& bn, int* bnrows, hipStream_t s) {
   if (pooled) *pooled = 0;
   if (bnrows) *bnrows = 0;
-  // first layer (3-channel input, packed K): conv_first.hip (auto, or bm_pref 13 = force; bm_pref 256
-  // runs this file's packed implicit GEMM, the tests' second opinion)
-  {
-    const int pref = bm_pref % 1000;
-    if (packed && (pref == 13 || pref == 0) && c.C1 == 8 && c.C2 == 0 && c.x2 == nullptr && taps == 9 &&
-        c.Cout == 64 && c.y2 == nullptr) {
-      const int r = rdp_conv_first(c, s);
-      if (r >= 0 || pref == 13) return r;
+  const bool has_ws = ws != nullptr && ws_elems > 0;
+  const RdpConvPlan p =
+      rdp_conv_plan(c, taps, packed, kernel, has_ws, ws_elems, fuse, pooled != nullptr, bn, wfrag ? wfrag_bytes : 0);
+  switch (p.kernel) {
+    case RDP_CONV_UNSUPPORTED: return -1;
+    case RDP_CONV_FIRST: return rdp_conv_first(c, s);
+    case RDP_CONV_ROWBAND: {
+      RdpConv cw = c;
+      if (p.rowband_mode) { cw.w = wfrag; cw.wbytes = wfrag_bytes; cw.ldw = 0; }
+      void* const pool = p.pool_fused ? fuse.pool : nullptr;
+      const int r = rdp_conv_rowband_ex(cw, pool, pool ? rdp_conv_pool_bytes(c, fuse) : 0, fuse.ppitch, p.rowband_mode, s);
+      if (r == 1) *pooled = 1;
+      return r < 0 ? -1 : 0;
     }
-  }
-  // eval (BN folded, one destination) on small maps: the row-band kernel, MaxPool2d fused (16 = force)
-  {
-    const int pref = bm_pref % 1000;
-    if (c.escale && c.eshift && !c.stats && !c.y2 && taps == 9 && !packed &&
-        (pref == 16 || (pref == 0 && rowband_auto(c.N, c.H, c.W, c.C1 + c.C2, c.Cout, fuse.pool && pooled)))) {
-      const bool wp = fuse.pool && pooled && c.H % 2 == 0 && c.W % 2 == 0;
-      const long pbytes = wp ? ((long)c.N * (c.H / 2) * (c.W / 2) - 1) * fuse.ppitch * 2 + (long)c.Cout * 2 : 0;
-      const int r = rdp_conv_rowband(c, wp ? fuse.pool : nullptr, pbytes, fuse.ppitch, s);
-      if (r >= 0) {
-        if (r == 1) *pooled = 1;
-        return 0;
-      }
-      if (pref == 16) return -1;
+    case RDP_CONV_RING: {
+      if (!p.pool_fused) return rdp_conv_ring(c, 256, s);
+      const int r = rdp_conv_ring_pool(c, fuse.pool, fuse.ppitch, s);
+      if (r == 0) *pooled = 1;
+      return r;
     }
-  }
-  // bm_pref % 1000: 0 = auto, 1 = force the halo-tile kernel, 6 = force the row-ring kernel,
-  // 128 / 256 (2 / 3: 8-wave) = force this kernel's tile
-  {
-    const int pref = bm_pref % 1000;
-    // row-ring kernel (conv_ring.hip): 64 -> 64 channels, 3x3, one source, no output split. Auto only
-    // when its grid (one block per pair of 64-pixel row segments, <= 256) fills the chip: at N = 1,
-    // 128^2 x 64 -> 128 the 128-block ring took 15.2 us vs 11.9 us for the implicit GEMM
-    const long ring_pairs = c.W % 64 == 0 ? (long)c.N * (c.W / 64) * c.H / 2 : 0;
-    if ((pref == 6 || (pref == 0 && ring_pairs >= 256)) && taps == 9 && !packed && c.C2 == 0 &&
-        c.x2 == nullptr) {
-      if (fuse.pool && pooled && !c.stats && !c.y2 && c.escale) {  // eval: MaxPool2d fused into the ring epilogue
-        const int r = rdp_conv_ring_pool(c, fuse.pool, fuse.ppitch, s);
-        if (r == 0) {
-          *pooled = 1;
-          return 0;
-        }
-      }
-      const int r = rdp_conv_ring(c, 256, s);
-      if (r >= 0 || pref == 6) return r;
-    }
-  }
-  // two-source row ring (conv_ring.hip conv_ring2_kernel): 128 input channels (two 64-channel sources,
-  // or one 128-channel tensor as its two halves) -> 64, 3x3, one destination; 14 = force. 15 = force
-  // (auto: RING2_X2_PAIRS) 128 -> 128 as two launches over the output-channel halves (each reads the input).
-  {
-    const int pref = bm_pref % 1000;
-    const long ring_pairs = c.W % 64 == 0 ? (long)c.N * (c.W / 64) * c.H / 2 : 0;
-    const bool two = c.C1 == 64 && c.C2 == 64 && c.x2 != nullptr;
-    const bool one = c.C1 == 128 && c.C2 == 0 && c.x2 == nullptr;
-    const bool c64 = c.Cout == 64 && (pref == 14 || (pref == 0 && ring_pairs >= 256));
-    const bool c128 = c.Cout == 128 && (pref == 15 || (pref == 0 && ring_pairs >= RING2_X2_PAIRS));
-    if ((c64 || c128) && taps == 9 && !packed && (two || one) && c.y2 == nullptr && !(fuse.pool && pooled) &&
-        !(fuse.up && pooled)) {
-      RdpConv h = c;  // one launch per 64 output channels: a copy of the block with the slice offsets applied
-      if (one) {      // the second source = the upper half of the one 128-channel tensor
-        h.x2 = (const u16*)c.x1 + 64;
-        h.xbytes2 = c.xbytes1 - 128;
-        h.pitch2 = c.pitch1;
-      }
+    case RDP_CONV_RING2:
+    case RDP_CONV_RING2X2: {
+      RdpConv h = rdp_ring2_sources(c);  // one launch per 64 output channels: the block with the slice offsets applied
       int r = -1;
       for (int co0 = 0; co0 < c.Cout; co0 += 64) {
         h.w = (const u16*)c.w + (long)co0 * c.ldw;
@@ -1222,142 +1131,22 @@ extern "C" int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int bm_pre
         r = rdp_conv_ring2(h, 256, c.Cout, co0, s);
         if (r < 0) break;
       }
-      if (r >= 0 || pref == 14 || pref == 15) return r;
+      return r;
     }
+    case RDP_CONV_HALO: return rdp_conv_halo(c, s);
+    default: break;
   }
-  {
-    const int pref = bm_pref % 1000;
-    const int ht = rdp_conv_halo_tiles(c.N, c.H, c.W, c.C1, c.C2, c.Cout, taps, packed);
-    // auto: the halo kernel wins only where a 64-channel output reads >= 256 input channels
-    // (measured, scripts/conv_microbench.py); elsewhere this kernel's 2 blocks/CU overlap better
-    const bool halo_auto = pref == 0 && ht >= 256 && c.Cout == 64 && c.C1 + c.C2 >= 256;
-    if (ht > 0 && (pref == 1 || halo_auto))
-      return rdp_conv_halo(c, s);
-    if (pref == 1) return -1;
+  const ConvArgs a = conv_args(c, taps, packed, has_ws ? ws : nullptr, fuse, pooled, bn, bnrows);
+  const long ws_limit = rdp_conv_ws_limit(has_ws, ws_elems);
+  switch (p.kernel) {
+    case RDP_CONV_PP256: return launch_pp<256>(a, s);
+    case RDP_CONV_PP128: return launch_pp<128>(a, s);
+    case RDP_CONV_PPSK128: return launch_pp<128>(a, s, p.ksplit, pooled);
+    case RDP_CONV_PPSK256: return launch_pp<256>(a, s, p.ksplit, pooled);
+    case RDP_CONV_IGEMM8_128: return launch_cfg<128, 128, 8>(a, ws_limit, s, pooled);
+    case RDP_CONV_IGEMM8_256: return launch_cfg<256, 64, 8>(a, ws_limit, s, pooled);
+    case RDP_CONV_IGEMM4_128: return launch_cfg<128, 128>(a, ws_limit, s, pooled);
+    case RDP_CONV_IGEMM4_256: return launch_cfg<256, 64>(a, ws_limit, s, pooled);
+    default: return -1;
   }
-  ConvArgs a;
-  a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
-  // ws = the split-K fp32 slab (rdp_conv_ws_elems)
-  const bool has_ws = ws != nullptr && ws_elems > 0;
-  a.kslab = has_ws ? ws : nullptr;
-  a.ksplit = 1;
-  a.pool = (fuse.pool != nullptr && pooled != nullptr && c.stats == nullptr && c.y2 == nullptr && c.H % 2 == 0 &&
-            c.W % 2 == 0)
-               ? (u16*)fuse.pool : nullptr;
-  a.ppitch = fuse.ppitch;
-  // fused upsample needs the eval epilogue, 16-channel groups and the LDS band (<= 64 KB). Measured
-  // (serving frame, N = 1): it wins only at the 16^2 bottleneck (6.9 us vs 4.8 + 4.8 us); at 32^2 /
-  // 64^2 / 128^2 the banded two-phase kernel is slower than reduce + upsample (10.9 / 13.2 / 15.4 vs
-  // 9.8 / 10.3 / 10.6 us; 2-row bands x 8 channels were slower still), so larger maps take the
-  // separate upsample launch.
-  const bool up_ok = fuse.up != nullptr && pooled != nullptr && fuse.pool == nullptr && c.stats == nullptr &&
-                     c.y2 == nullptr &&
-                     c.escale != nullptr && c.eshift != nullptr && c.Cout % UP_CG == 0 && fuse.upitch % 4 == 0 &&
-                     (long)(UP_TY / 2 + 2) * c.W * UP_CG * 2 <= 65536 && fuse.uH >= 2 * c.H && fuse.uW >= 2 * c.W &&
-                     (long)c.H * c.W <= 256;
-  a.up = up_ok ? (u16*)fuse.up : nullptr;
-  a.upitch = fuse.upitch; a.uH = fuse.uH; a.uW = fuse.uW; a.uoy = fuse.uoy; a.uox = fuse.uox;
-  a.urh = 2 * c.H > 1 ? (float)(c.H - 1) / (float)(2 * c.H - 1) : 0.f;  // = ac_scale (pool_up.hip)
-  a.urw = 2 * c.W > 1 ? (float)(c.W - 1) / (float)(2 * c.W - 1) : 0.f;
-  long wse = has_ws ? ws_elems : 0;
-  wse = wse < (1L << 29) ? wse : (1L << 29);  // slab bytes < 2 GiB (buffer offsets)
-  a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
-  a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
-  a.C1 = c.C1; a.C2 = c.C2; a.pitch1 = c.pitch1; a.pitch2 = c.pitch2;
-  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
-  a.y1 = (u16*)c.y1; a.y2 = (u16*)c.y2; a.ybytes1 = (uint32_t)c.ybytes1; a.ybytes2 = (uint32_t)c.ybytes2;
-  a.Cy1 = c.Cy1; a.ypitch1 = c.ypitch1; a.ypitch2 = c.ypitch2; a.stats = c.stats;
-  if (bn.bnpart && bn.bny && bn.bncoef && !c.stats && !c.escale && c.y2 == nullptr && c.Cy1 == c.Cout &&
-      bn.bnypitch % 4 == 0 && fuse.pool == nullptr && fuse.up == nullptr) {
-    a.bny = (const u16*)bn.bny; a.bnypitch = bn.bnypitch; a.bncoef = bn.bncoef; a.bnpart = bn.bnpart;
-    a.bnrows = bnrows;
-  }
-  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.M = c.N * c.H * c.W;
-  a.taps = taps; a.packed = packed;
-  if (packed) {
-    if (c.C1 != 8 || c.C2 != 0 || taps != 9 || c.ldw != 128) return -1;
-    a.nks = 2; a.cpt = 1;
-  } else {
-    if (c.C1 % 64 || c.C2 % 64 || (taps != 9 && taps != 1)) return -1;
-    a.cpt = (c.C1 + c.C2) / 64;
-    a.nks = taps * a.cpt;
-    if (c.ldw < taps * (c.C1 + c.C2)) return -1;
-  }
-  if (c.Cout % 64 || c.Cy1 % 8) return -1;  // widened 16-B epilogue stores never straddle the split
-  if (c.xbytes1 >= (1l << 31) || c.xbytes2 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.ybytes2 >= (1l << 31))
-    return -1;
-  const FastDiv fhw = make_fastdiv((uint32_t)(c.H * c.W)), fw = make_fastdiv((uint32_t)c.W);
-  a.fhw_m = fhw.m; a.fhw_s = fhw.s; a.fw_m = fw.m; a.fw_s = fw.s;
-  // bm_pref: 0 = auto, 128 / 256 = force the tile; +1000*k: k = blocks per CU of the persistent
-  // grid (k = 0 => 2 per CU, every block resident; large k ~ one tile per block)
-  int per_cu = bm_pref / 1000;
-  bm_pref %= 1000;
-  if (per_cu == 0) per_cu = 2;  // default: 2 blocks per CU, every block resident
-  // bm_pref 4 / 5: force the ping-pong 256 x 256 / 256 x 128 kernel (conv_pp_kernel)
-  if (bm_pref == 4) return launch_pp<256>(a, s);
-  if (bm_pref == 5) return launch_pp<128>(a, s);
-  // auto: the ping-pong 256 x 256 kernel wherever its tile grid fills the chip (>= 256 tiles of 256
-  // pixels x 256 couts; fewer tiles leave CUs idle at one block per CU). Measured
-  // (scripts/conv_microbench.py, bs 64, one MI355X): 64^2 256->256 903 -> 1082 TF/s, 32^2 512->512
-  // 962 -> 1205, 32^2 512+512->256 927 -> 1120; bs 64 step 2973 -> 3150 img/s. The 256 x 128 form is
-  // 2-4 % faster than the 128 x 128 kernel where K >= 1152 (128^2 128->128 851 -> 889, 64^2
-  // 256+256->128 882 -> 907; slower at K = 576) and +1.0-1.4 % on the bs 64 step.
-  if (bm_pref == 0 && !packed) {
-    const long tiles256 = (long)(a.M + 255) / 256 * (c.Cout / 256);
-    if (c.Cout % 256 == 0 && c.Cy1 % 32 == 0 && tiles256 >= 256 && c.escale == nullptr) return launch_pp<256>(a, s);
-    // 256 x 128 form: only where K is long enough (>= 128 input channels)
-    const long tiles128 = (long)(a.M + 255) / 256 * (c.Cout / 128);
-    if (c.Cout % 128 == 0 && c.Cy1 % 32 == 0 && tiles128 >= 256 && c.C1 + c.C2 >= 128 && c.escale == nullptr)
-      return launch_pp<128>(a, s);
-  }
-  // bm_pref 7 / 8: force the split-K ping-pong 256 x 128 / 256 x 256 kernel (pp_split_plan's split)
-  if (bm_pref == 7 || bm_pref == 8) {
-    const int d = pp_split_plan(a.M, c.Cout, bm_pref == 7 ? 128 : 256, a.nks, wse);
-    if (d < 2 || packed || c.Cy1 % 32) return -1;
-    return bm_pref == 7 ? launch_pp<128>(a, s, d, pooled) : launch_pp<256>(a, s, d, pooled);
-  }
-  // auto, small M x long K (training): split-K ping-pong 256 x 128 where its plan exists and the 128 x 128
-  // kernel would split K too (measured, scripts/conv_microbench.py --batch 4 --ws 1, one MI355X: 32^2
-  // 1024->512 63.5 -> 53.2 us, 512->512 39.9 -> 36.7, 512+512->256 39.0 -> 36.7, 64^2 256->128 31.5 ->
-  // 29.4; where the 128 x 128 grid needs no split (64^2 256->256) the unsplit kernel wins, 32.9 vs 39.5,
-  // and at M = 1024 (16^2 512->1024: 29.5 vs 31.0 us) the 128 x 128 split does)
-  // (eval too, BN fold in the shared reduce: the batched serving network at N = 4, scripts/rowband_bench.py
-  // --batch 4 --variants 0,7: 32^2 1024->512 63.2 -> 52.3 us, 512->512 + pool 39.3 -> 36.4)
-  if (bm_pref == 0 && !packed && c.Cout % 128 == 0 && c.Cy1 % 32 == 0 && c.C1 + c.C2 >= 128 &&
-      a.M >= 4096 && (long)(a.M + 127) / 128 * (c.Cout / 128) < 192 && pp_split_enabled()) {
-    const int d = pp_split_plan(a.M, c.Cout, 128, a.nks, wse);
-    if (d > 1) return launch_pp<128>(a, s, d, pooled);
-  }
-  const int max_blocks = 256 * per_cu;
-  // bm_pref 2 / 3: 8-wave blocks (64 x 32 per wave; twice the waves per SIMD to hide the per-step
-  // barrier + DMA latency, 1.5x the LDS fragment reads per MFMA) for the 128x128 / 256x64 tiles
-  // (measured dead end: 256 x 256 / 256 x 128 tiles in this 2-phase structure, one 8-wave block
-  // per CU -- 49 spilled VGPRs at 256 x 256; +6 % on 32^2 x 512 -> 512 only, -5..-40 % elsewhere)
-  if (bm_pref == 2 && c.Cout % 128 == 0) return launch_cfg<128, 128, 8>(a, max_blocks, wse, s, pooled);
-  if (bm_pref == 3) return launch_cfg<256, 64, 8>(a, max_blocks, wse, s, pooled);
-  if (bm_pref == 128 && c.Cout % 128 == 0) return launch_cfg<128, 128>(a, max_blocks, wse, s, pooled);
-  if (bm_pref == 0 && c.Cout % 128 == 0) return launch_cfg<128, 128, 8>(a, max_blocks, wse, s, pooled);
-  if (bm_pref == 256) return launch_cfg<256, 64>(a, max_blocks, wse, s, pooled);
-  return launch_cfg<256, 64, 8>(a, max_blocks, wse, s, pooled);
-}
-
-extern "C" long rdp_conv_ws_elems(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed, int bm_pref) {
-  const int pref = bm_pref % 1000;
-  const int ht = rdp_conv_halo_tiles(N, H, W, C1, C2, Cout, taps, packed);
-  if (ht > 0 && (pref == 1 || (pref == 0 && ht >= 256 && Cout == 64 && C1 + C2 >= 256))) return 0;
-  if (packed) return 0;
-  const int M = N * H * W;
-  const int nks = taps * ((C1 + C2) / 64);
-  const int BM = ((pref == 128 || pref == 0) && Cout % 128 == 0) ? 128 : 256, BN = BM == 128 ? 128 : 64;
-  const int ntiles = (M + BM - 1) / BM * (Cout / BN);
-  const int d = choose_ksplit(ntiles, nks, M, Cout, packed, 1L << 29);
-  long need = d > 1 ? (long)d * M * Cout : 0;
-  // the split-K ping-pong plan (auto at >= 128 input channels, or forced by bm_pref 7 / 8)
-  if ((pref == 0 && C1 + C2 >= 128 && Cout % 128 == 0 && M >= 4096 && (long)(M + 127) / 128 * (Cout / 128) < 192) ||
-      pref == 7 ||
-      pref == 8) {
-    const int dp = pp_split_plan(M, Cout, pref == 8 ? 256 : 128, nks, 1L << 29);
-    if (dp > 1 && (long)dp * M * Cout > need) need = (long)dp * M * Cout;
-  }
-  return need;
 }

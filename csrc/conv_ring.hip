@@ -626,9 +626,38 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
   }
 }
 
-// Applicability of the ring kernel (3x3, one 64-channel source, 64 or 128 outputs -- split at a
-// multiple of 32 into two destinations --, W % 64 == 0, even H); returns the stats rows it writes,
-// or -1 when not applicable.
+// The one RdpConv -> RingArgs fill, for every form of the kernel (the head and pool forms add their own fields)
+static RingArgs ring_args(const RdpConv& c, const RdpRingFuse& f, const RdpRingGeo& g) {
+  RingArgs a = {};
+  a.x = (const u16*)c.x1; a.xbytes = (uint32_t)c.xbytes1; a.pitch = c.pitch1;
+  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
+  a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
+  a.y2 = (u16*)(c.y2 ? c.y2 : c.y1); a.ybytes2 = c.y2 ? (uint32_t)c.ybytes2 : 0u;
+  a.ypitch2 = c.y2 ? c.ypitch2 : c.ypitch1;
+  a.Cy1 = c.Cy1;
+  a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
+  a.bny = (const u16*)f.bn_y; a.bnypitch = f.bn_ypitch; a.bncoef = f.bn_coef;
+  a.iscale = f.iscale; a.ishift = f.ishift;
+  a.aout = (u16*)f.aout; a.abytes = (uint32_t)f.abytes; a.apitch = f.apitch;
+  a.H = c.H; a.W = c.W; a.WS = g.WS;
+  a.nrows = g.nrows; a.npairs = g.npairs; a.pairs_per_block = g.pairs_per_block;
+  const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)g.WS);
+  a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
+  return a;
+}
+
+// the eval conv (64 -> 64, BN folded + ReLU) whose output only the fused serving heads consume
+static RdpConv ring_head_conv(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw, int Cout,
+                              int N, int H, int W, const float* escale, const float* eshift) {
+  RdpConv c;
+  c.x1 = x; c.xbytes1 = xbytes; c.C1 = C; c.pitch1 = pitch;
+  c.w = w; c.wbytes = wbytes; c.ldw = ldw;
+  c.Cy1 = 64; c.ypitch1 = 64;
+  c.N = N; c.H = H; c.W = W; c.Cout = Cout;
+  c.escale = escale; c.eshift = eshift; c.erelu = 1;
+  return c;
+}
+
 extern "C" int rdp_conv_ring(const RdpConv& c, int max_blocks, hipStream_t s) {
   return rdp_conv_ring_ex(c, max_blocks, RdpRingFuse{}, s);
 }
@@ -636,27 +665,12 @@ extern "C" int rdp_conv_ring(const RdpConv& c, int max_blocks, hipStream_t s) {
 extern "C" int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
                                   int Cout, int N, int H, int W, const float* escale, const float* eshift,
                                   const float* hw, const float* hb, float hthr, void* mask, hipStream_t s) {
-  if (C != 64 || Cout != 64 || W % 64 || H % 2 || ldw < 576 || !escale || !eshift || !hw || !hb || !mask) return -1;
-  if (xbytes >= (1l << 31) || wbytes >= (1l << 31)) return -1;
-  RingArgs a;
-  a.x = (const u16*)x; a.xbytes = (uint32_t)xbytes; a.pitch = pitch;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y = nullptr; a.ybytes = 0; a.ypitch = 64; a.y2 = nullptr; a.ybytes2 = 0; a.ypitch2 = 64; a.Cy1 = 64;
-  a.stats = nullptr; a.escale = escale; a.eshift = eshift; a.erelu = 1;
-  a.bny = nullptr; a.bnypitch = 0; a.bncoef = nullptr;
-  a.hw = hw; a.hb = hb; a.hthr = hthr; a.hmask = (uint8_t*)mask; a.hcls = 0;
-  a.pool = nullptr; a.ppitch = 0;
-  a.iscale = nullptr; a.ishift = nullptr;
-  a.aout = nullptr; a.abytes = 0; a.apitch = 0;
-  a.H = H; a.W = W; a.WS = W / 64;
-  a.nrows = N * a.WS * H;
-  a.npairs = a.nrows / 2;
-  const int blocks = std::max(1, std::min(256, a.npairs));
-  a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
-  const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
-  const FastDiv fh = make_fastdiv((uint32_t)H), fs = make_fastdiv((uint32_t)a.WS);
-  a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
-  hipLaunchKernelGGL((conv_ring_kernel<64, false, true>), dim3(grid), dim3(512), 0, s, a);
+  const RdpConv c = ring_head_conv(x, xbytes, C, pitch, w, wbytes, ldw, Cout, N, H, W, escale, eshift);
+  const RdpRingGeo g = rdp_ring_geo(c, RdpRingFuse{}, RDP_RING_HEAD, 0, 256);
+  if (!g.fits || !hw || !hb || !mask) return -1;
+  RingArgs a = ring_args(c, RdpRingFuse{}, g);
+  a.hw = hw; a.hb = hb; a.hthr = hthr; a.hmask = (uint8_t*)mask;
+  hipLaunchKernelGGL((conv_ring_kernel<64, false, true>), dim3(g.grid), dim3(512), 0, s, a);
   return 0;
 }
 
@@ -668,113 +682,46 @@ static void launch_ring_headk(int grid, hipStream_t s, const RingArgs& a) {
 extern "C" int rdp_conv_ring_headk(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
                                    int Cout, int N, int H, int W, const float* escale, const float* eshift,
                                    const float* hw, const float* hb, int K, int cls, void* mask, hipStream_t s) {
-  if (C != 64 || Cout != 64 || W % 64 || H % 2 || ldw < 576 || !escale || !eshift || !hw || !hb || !mask) return -1;
-  if (xbytes >= (1l << 31) || wbytes >= (1l << 31)) return -1;
+  const RdpConv c = ring_head_conv(x, xbytes, C, pitch, w, wbytes, ldw, Cout, N, H, W, escale, eshift);
+  const RdpRingGeo g = rdp_ring_geo(c, RdpRingFuse{}, RDP_RING_HEAD, 0, 256);
+  if (!g.fits || !hw || !hb || !mask) return -1;
   // (a channel-sliced view of a wider tensor, pitch != 64, keeps the separate launches)
   if (pitch != 64 || K < 2 || K > 8 || cls < 0 || cls >= K || N <= 0 || H <= 0 || (long)N * H * W >= (1l << 31))
     return -1;
-  RingArgs a;
-  a.x = (const u16*)x; a.xbytes = (uint32_t)xbytes; a.pitch = pitch;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y = nullptr; a.ybytes = 0; a.ypitch = 64; a.y2 = nullptr; a.ybytes2 = 0; a.ypitch2 = 64; a.Cy1 = 64;
-  a.stats = nullptr; a.escale = escale; a.eshift = eshift; a.erelu = 1;
-  a.bny = nullptr; a.bnypitch = 0; a.bncoef = nullptr;
-  a.hw = hw; a.hb = hb; a.hthr = 0.f; a.hmask = (uint8_t*)mask; a.hcls = cls;
-  a.pool = nullptr; a.ppitch = 0;
-  a.iscale = nullptr; a.ishift = nullptr;
-  a.aout = nullptr; a.abytes = 0; a.apitch = 0;
-  a.H = H; a.W = W; a.WS = W / 64;
-  a.nrows = N * a.WS * H;
-  a.npairs = a.nrows / 2;
-  const int blocks = std::max(1, std::min(256, a.npairs));
-  a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
-  const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
-  const FastDiv fh = make_fastdiv((uint32_t)H), fs = make_fastdiv((uint32_t)a.WS);
-  a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
+  RingArgs a = ring_args(c, RdpRingFuse{}, g);
+  a.hw = hw; a.hb = hb; a.hmask = (uint8_t*)mask; a.hcls = cls;
   switch (K) {
-    case 2: launch_ring_headk<2>(grid, s, a); break;
-    case 3: launch_ring_headk<3>(grid, s, a); break;
-    case 4: launch_ring_headk<4>(grid, s, a); break;
-    case 5: launch_ring_headk<5>(grid, s, a); break;
-    case 6: launch_ring_headk<6>(grid, s, a); break;
-    case 7: launch_ring_headk<7>(grid, s, a); break;
-    default: launch_ring_headk<8>(grid, s, a); break;
+    case 2: launch_ring_headk<2>(g.grid, s, a); break;
+    case 3: launch_ring_headk<3>(g.grid, s, a); break;
+    case 4: launch_ring_headk<4>(g.grid, s, a); break;
+    case 5: launch_ring_headk<5>(g.grid, s, a); break;
+    case 6: launch_ring_headk<6>(g.grid, s, a); break;
+    case 7: launch_ring_headk<7>(g.grid, s, a); break;
+    default: launch_ring_headk<8>(g.grid, s, a); break;
   }
   return 0;
 }
 
 extern "C" int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipStream_t s) {
-  if (c.C1 != 64 || c.Cout != 64 || c.W % 64 || c.H % 2 || c.ldw < 576 || !c.escale || !c.eshift || !pool ||
-      ppitch % 4)
-    return -1;
-  if (c.xbytes1 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.wbytes >= (1l << 31)) return -1;
-  RingArgs a;
-  a.x = (const u16*)c.x1; a.xbytes = (uint32_t)c.xbytes1; a.pitch = c.pitch1;
-  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
-  a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
-  a.y2 = (u16*)c.y1; a.ybytes2 = 0; a.ypitch2 = c.ypitch1; a.Cy1 = 64;
-  a.stats = nullptr; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
-  a.bny = nullptr; a.bnypitch = 0; a.bncoef = nullptr;
-  a.hw = nullptr; a.hb = nullptr; a.hthr = 0.f; a.hmask = nullptr; a.hcls = 0;
+  const RdpRingGeo g = rdp_ring_geo(c, RdpRingFuse{}, RDP_RING_POOL, ppitch, 256);
+  if (!g.fits || !pool) return -1;
+  RingArgs a = ring_args(c, RdpRingFuse{}, g);
   a.pool = (u16*)pool; a.ppitch = ppitch;
-  a.iscale = nullptr; a.ishift = nullptr;
-  a.aout = nullptr; a.abytes = 0; a.apitch = 0;
-  a.H = c.H; a.W = c.W; a.WS = c.W / 64;
-  a.nrows = c.N * a.WS * c.H;
-  a.npairs = a.nrows / 2;
-  const int blocks = std::max(1, std::min(256, a.npairs));
-  a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
-  const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
-  const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)a.WS);
-  a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
-  hipLaunchKernelGGL((conv_ring_kernel<64, false, false, true>), dim3(grid), dim3(512), 0, s, a);
+  hipLaunchKernelGGL((conv_ring_kernel<64, false, false, true>), dim3(g.grid), dim3(512), 0, s, a);
   return 0;
 }
 
 extern "C" int rdp_conv_ring_ex(const RdpConv& c, int max_blocks, const RdpRingFuse& f, hipStream_t s) {
-  const u16* bn_y = (const u16*)f.bn_y;
-  if (f.aout && (!f.iscale || f.abytes >= (1l << 31) || f.apitch % 8)) return -1;
-  if (bn_y && (!c.stats || c.escale || c.y2 || f.bn_ypitch % 4 || c.Cout != 64)) return -1;
-  if (f.iscale && (!f.ishift || bn_y || c.escale || c.y2 || c.Cout != 64)) return -1;
-  if (c.C1 != 64 || (c.Cout != 64 && c.Cout != 128) || c.W % 64 || c.H % 2 || c.ldw < 576 || c.Cy1 % 32) return -1;
-  if (c.y2 == nullptr && c.Cy1 != c.Cout) return -1;
-  if (c.xbytes1 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.ybytes2 >= (1l << 31) || c.wbytes >= (1l << 31))
-    return -1;
-  RingArgs a;
-  a.x = (const u16*)c.x1; a.xbytes = (uint32_t)c.xbytes1; a.pitch = c.pitch1;
-  a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
-  a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
-  a.y2 = (u16*)(c.y2 ? c.y2 : c.y1); a.ybytes2 = c.y2 ? (uint32_t)c.ybytes2 : 0u;
-  a.ypitch2 = c.y2 ? c.ypitch2 : c.ypitch1;
-  a.Cy1 = c.Cy1;
-  a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
-  a.bny = bn_y; a.bnypitch = f.bn_ypitch; a.bncoef = f.bn_coef;
-  a.hw = nullptr; a.hb = nullptr; a.hthr = 0.f; a.hmask = nullptr; a.hcls = 0;
-  a.pool = nullptr; a.ppitch = 0;
-  a.iscale = f.iscale; a.ishift = f.ishift;
-  a.aout = (u16*)f.aout; a.abytes = (uint32_t)f.abytes; a.apitch = f.apitch;
-  a.H = c.H; a.W = c.W; a.WS = c.W / 64;
-  a.nrows = c.N * a.WS * c.H;
-  a.npairs = a.nrows / 2;
-  const int blocks = std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, a.npairs));
-  a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
-  const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
-  const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)a.WS);
-  a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
-  if (c.Cout == 128) {
-    hipLaunchKernelGGL((conv_ring_kernel<128>), dim3(grid), dim3(512), 0, s, a);
-    return grid * 2;
-  }
-  if (bn_y) {
-    hipLaunchKernelGGL((conv_ring_kernel<64, true>), dim3(grid), dim3(512), 0, s, a);
-    return grid * 4;
-  }
-  if (f.iscale) {
-    hipLaunchKernelGGL((conv_ring_kernel<64, false, false, false, true>), dim3(grid), dim3(512), 0, s, a);
-    return grid * 4;
-  }
-  hipLaunchKernelGGL((conv_ring_kernel<64>), dim3(grid), dim3(512), 0, s, a);
-  return grid * 4;
+  const RdpRingForm form = rdp_ring_form(f);
+  const RdpRingGeo g = rdp_ring_geo(c, f, form, 0, max_blocks);
+  if (!g.fits) return -1;
+  const RingArgs a = ring_args(c, f, g);
+  if (c.Cout == 128) hipLaunchKernelGGL((conv_ring_kernel<128>), dim3(g.grid), dim3(512), 0, s, a);
+  else if (form == RDP_RING_BNRED) hipLaunchKernelGGL((conv_ring_kernel<64, true>), dim3(g.grid), dim3(512), 0, s, a);
+  else if (form == RDP_RING_BNIN)
+    hipLaunchKernelGGL((conv_ring_kernel<64, false, false, false, true>), dim3(g.grid), dim3(512), 0, s, a);
+  else hipLaunchKernelGGL((conv_ring_kernel<64>), dim3(g.grid), dim3(512), 0, s, a);
+  return g.rows;
 }
 
 // ---- two-source (128 -> 64) row ring ---------------------------------------------------------------
@@ -1042,26 +989,19 @@ __global__ __launch_bounds__(512, 2) void conv_ring2_kernel(const Ring2Args a) {
 }
 
 extern "C" int rdp_conv_ring2(const RdpConv& c, int max_blocks, int cout_total, int co0, hipStream_t s) {
-  if (c.W % 64 || c.H % 2 || c.ldw < 1152 || c.ypitch1 % 8 || c.pitch1 % 8 || c.pitch2 % 8) return -1;
-  if (c.xbytes1 >= (1l << 31) || c.xbytes2 >= (1l << 31) || c.ybytes1 >= (1l << 31) || c.wbytes >= (1l << 31))
-    return -1;
-  if ((c.escale == nullptr) != (c.eshift == nullptr)) return -1;
+  const RdpRingGeo g = rdp_ring2_geo(c, max_blocks, cout_total, co0);
+  if (!g.fits) return -1;
   Ring2Args a;
   a.x0 = (const u16*)c.x1; a.x1 = (const u16*)c.x2;
   a.xbytes0 = (uint32_t)c.xbytes1; a.xbytes1 = (uint32_t)c.xbytes2; a.pitch0 = c.pitch1; a.pitch1 = c.pitch2;
   a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
   a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
   a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
-  if (cout_total < 64 || co0 < 0 || co0 + 64 > cout_total) return -1;
   a.scout = cout_total; a.co0 = co0;
-  a.H = c.H; a.W = c.W; a.WS = c.W / 64;
-  a.nrows = c.N * a.WS * c.H;
-  a.npairs = a.nrows / 2;
-  const int blocks = std::max(1, std::min(max_blocks > 0 ? max_blocks : 256, a.npairs));
-  a.pairs_per_block = (a.npairs + blocks - 1) / blocks;
-  const int grid = (a.npairs + a.pairs_per_block - 1) / a.pairs_per_block;
-  const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)a.WS);
+  a.H = c.H; a.W = c.W; a.WS = g.WS;
+  a.nrows = g.nrows; a.npairs = g.npairs; a.pairs_per_block = g.pairs_per_block;
+  const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)g.WS);
   a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
-  hipLaunchKernelGGL(conv_ring2_kernel, dim3(grid), dim3(512), 0, s, a);
-  return grid * 4;
+  hipLaunchKernelGGL(conv_ring2_kernel, dim3(g.grid), dim3(512), 0, s, a);
+  return g.rows;
 }

@@ -25,8 +25,7 @@
 //   * conv_rowband_x_kernel: fragment-major weights + each wave's 32-channel input chunk staged once per
 //     tile in LDS for all 9 taps (the serving default wherever the input has 128 or 256k channels);
 //   * conv_rowband_chain_kernel: the persistent multi-layer experiment (measured slower, kept tested).
-// The eval dispatch is rdp_conv_rowband_frag_auto (bindings conv_fwd with the executor's fragment-major
-// weights); rdp_conv_rowband_bytes is the OHWI form's traffic model used by rdp_conv_igemm.
+// Where the eval dispatch takes them is conv_plan.h's business (rdp_rowband_auto, rdp_rowband_frag_mode).
 #include "common.h"
 #include "rdp_api.h"
 #include <algorithm>
@@ -513,131 +512,34 @@ __global__ __launch_bounds__(512, 4) void conv_rowband_chain_kernel(const Rowban
   }
 }
 
-// Measured (scripts/rowband_bench.py, N = 1, MI355X) the kernel runs at ~8-9 TB/s of these bytes: it beats the
-// split-K implicit GEMM + reduce pair at <= ~150 MB (17-25 % faster on the 64^2 128 -> 256, 32^2 256 -> 512,
-// 16^2 512 -> 512, 32^2 512 -> 256 and 64^2 256 -> 128 layers) and loses from ~225 MB up (32^2 1024 -> 512: 64
-// vs 27 us).
-extern "C" long rdp_conv_rowband_bytes(int N, int H, int W, int Cin, int Cout, int pool) {
-  const int R = pool && H % 2 == 0 && 2 * W <= 64 ? 2 : 1;
-  const long wb = (long)Cout * 9 * Cin * 2, xb = (long)N * H * W * Cin * 2;
-  return wb * ((long)N * H / R) + xb * 9 * (Cout / 32);
-}
-
-// With the fragment-major weight copy (1 KiB contiguous per MFMA fragment: 8 full lines per load instead of
-// 16 half lines) a weight byte costs about half an activation byte (scripts/rowband_bench.py variant 17:
-// 16^2 512 -> 512 8.8 vs 14.6 us on OHWI weights, 32^2 256 -> 512 13.2 vs 18.9). The eval dispatch
-// (bindings conv_fwd with wfrag) takes the row-band kernel up to 250 MB of weighted operand bytes: every
-// <= 64^2 layer of the U-Net but the two long-K decoder convs (32^2 1024 -> 512, 64^2 512 -> 256).
-static int ilog2_exact(long v);
-
-extern "C" int rdp_conv_rowband_frag_auto(int N, int H, int W, int C1, int C2, int Cout) {
-  static const int on = [] {
-    const char* e = getenv("RDP_ROWBAND");
-    return e ? atoi(e) : 1;
-  }();
-  const int Cin = C1 + C2;
-  if (!on || W < 16 || Cin < 64 || Cout < 64 || Cout % 32 || C1 % 32 || C2 % 32) return 0;
-  if (ilog2_exact(W) < 0 || ilog2_exact(Cin / 32) < 0) return 0;
-  const long M = (long)N * H * W;
-  const long wb = (long)Cout * 9 * Cin * 2, xb = M * Cin * 2;
-  static const long xmax = [] {
-    const char* e = getenv("RDP_ROWBAND_X_MAXPIX");  // 0 turns the activation-staged kernel off
-    return e ? atol(e) : 65536L;  // (the work bound below decides; up3.conv2 at N = 2: 20.0 vs 32.5 us)
-  }();
-  // (64 input channels stay on the split-K GEMM: 128^2 64 -> 128 18.0 vs 11.5 us, four waves staging one chunk)
-  const bool xch = (Cin / 32) % 8 == 0 || Cin == 128;
-  if (xch && M <= xmax && W <= 256) {  // activation-staged (x read ~3x instead of 9x)
-    // ... while its work (blocks x K, the launch's own tiling below) stays within about two waves of 512
-    // blocks: past that the GEMM wins (scripts/rowband_bench.py --batch 1 / 2 / 4, every <= 128^2 layer of
-    // the U-Net: e.g. up1.conv1 17.9 vs 26.9 us at N = 1 but 44.9 vs 38.8 at N = 2, down2.conv1 20.9 vs
-    // 25.3 at N = 2 but 38.9 vs 20.2 at N = 4; 128-channel inputs, staged in 4 chunks, cross over earlier)
-    const int WB = W < 32 ? W : 32, segs = W / WB;
-    const bool r2 = H % 2 == 0 && (long)N * (H / 2) * segs * (Cout / 32) >= 256;
-    const long blocks = (long)N * (H / (r2 ? 2 : 1)) * segs * (Cout / 32);
-    const long work = blocks * 9 * Cin;
-    if (work <= ((Cin / 32) % 8 == 0 ? 2500000L : 1300000L)) return 2;
-    return 0;
-  }
-  if (M > 4096 || W > 64) return 0;
-  return wb * ((long)N * H) / 2 + xb * 9 * (Cout / 32) <= 250000000L ? 1 : 0;
-}
-
 static int ilog2_exact(long v) {
   int s = 0;
   while ((1L << s) < v) ++s;
   return (1L << s) == v ? s : -1;
 }
 
-extern "C" int rdp_conv_rowband(const RdpConv& c, void* pool, long pbytes, int ppitch, hipStream_t s) {
-  return rdp_conv_rowband_ex(c, pool, pbytes, ppitch, 0, s);
-}
-
 extern "C" int rdp_conv_rowband_ex(const RdpConv& c, void* pool, long pbytes, int ppitch, int wfrag, hipStream_t s) {
-  const int Cin = c.C1 + c.C2;
-  const int cs = ilog2_exact(Cin / 32), ws = ilog2_exact(c.W);
-  if (c.C1 % 32 || c.C2 % 32 || Cin < 64 || Cin % 32 || cs < 0 || ws < 4 || c.W > (wfrag == 2 ? 256 : 64) ||
-      c.Cout % 32)
-    return -1;
-  if (!c.escale || !c.eshift || (!wfrag && c.ldw < 9 * Cin) || (wfrag && c.wbytes < (long)c.Cout * 9 * Cin * 2) ||
-      (c.C2 && !c.x2))
-    return -1;
-  if (c.pitch1 % 8 || (c.C2 && c.pitch2 % 8) || c.ypitch1 % 4) return -1;
-  if (c.xbytes1 >= (1L << 31) || c.xbytes2 >= (1L << 31) || c.wbytes >= (1L << 31) || c.ybytes1 >= (1L << 31) ||
-      pbytes >= (1L << 31))
-    return -1;
-  if (wfrag == 2) {  // the activation-staged kernel: 32-channel chunks (a multiple of 8, or 2 / 4)
-    if ((Cin / 32) % 8 && Cin != 64 && Cin != 128) return -1;
-    const int WB = c.W < 32 ? c.W : 32;
-    const bool plx = pool != nullptr && c.H % 2 == 0 && ppitch % 4 == 0;
-    // two-row tiles (each block's weight slice serves twice the pixels) wherever that grid still has >= 256
-    // blocks: up1.conv1 22.4 -> 18.2 us, up2.conv1 24.5 -> 21.9, down3.conv1 7.8 -> 6.9 (at 128 blocks, the
-    // 16^2 and 32^2 -> 256 convs, one-row tiles stay faster); RDP_ROWBAND_R2=0 keeps one-row tiles (A/B)
-    static const int r2_on = [] {
-      const char* e = getenv("RDP_ROWBAND_R2");
-      return e ? atoi(e) : 1;
-    }();
-    const bool r2 =
-        r2_on && c.H % 2 == 0 && (long)c.N * (c.H / 2) * (c.W / (c.W < 32 ? c.W : 32)) * (c.Cout / 32) >= 256;
-    const int Rx = plx || r2 ? 2 : 1;
-    RowbandArgs a;
-    a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
-    a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
-    a.C1 = c.C1; a.C2 = c.C2; a.pitch1 = c.pitch1; a.pitch2 = c.pitch2;
-    a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
-    a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
-    a.pool = plx ? (u16*)pool : nullptr; a.pbytes = plx ? (uint32_t)pbytes : 0u; a.ppitch = ppitch;
-    a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
-    a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.wshift = ws;
-    a.R = Rx; a.bands = c.H / Rx; a.cshift = cs; a.T = 9 * Cin / 32; a.wfrag = 1; a.segs = c.W / WB;
-    const int grid = c.N * a.bands * a.segs * (c.Cout / 32);
-    const int PBx = Rx * WB;
-    if (PBx == 16) hipLaunchKernelGGL((conv_rowband_x_kernel<1, 1>), dim3(grid), dim3(512), 0, s, a);
-    else if (PBx == 32 && Rx == 1) hipLaunchKernelGGL((conv_rowband_x_kernel<2, 1>), dim3(grid), dim3(512), 0, s, a);
-    else if (PBx == 32) hipLaunchKernelGGL((conv_rowband_x_kernel<2, 2>), dim3(grid), dim3(512), 0, s, a);
-    else if (PBx == 64) hipLaunchKernelGGL((conv_rowband_x_kernel<4, 2>), dim3(grid), dim3(512), 0, s, a);
-    else return -1;
-    return plx ? 1 : 0;
-  }
-  // the pool needs two rows per block: only where that block is <= 64 pixels (else the caller pools)
-  const bool pl = pool != nullptr && c.H % 2 == 0 && ppitch % 4 == 0 && 2 * c.W <= 64;
-  const int R = pl ? 2 : 1;
-  const int PB = R * c.W;
+  const RdpRowbandGeo g = rdp_rowband_geo(c, pool != nullptr, pbytes, ppitch, wfrag);
+  if (!g.fits) return -1;
   RowbandArgs a;
   a.x1 = (const u16*)c.x1; a.x2 = (const u16*)c.x2;
   a.xbytes1 = (uint32_t)c.xbytes1; a.xbytes2 = (uint32_t)c.xbytes2;
   a.C1 = c.C1; a.C2 = c.C2; a.pitch1 = c.pitch1; a.pitch2 = c.pitch2;
   a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
   a.y = (u16*)c.y1; a.ybytes = (uint32_t)c.ybytes1; a.ypitch = c.ypitch1;
-  a.pool = pl ? (u16*)pool : nullptr; a.pbytes = pl ? (uint32_t)pbytes : 0u; a.ppitch = ppitch;
+  a.pool = g.pools ? (u16*)pool : nullptr; a.pbytes = g.pools ? (uint32_t)pbytes : 0u; a.ppitch = ppitch;
   a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
-  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.wshift = ws;
-  a.R = R; a.bands = c.H / R; a.cshift = cs; a.T = 9 * Cin / 32; a.wfrag = wfrag;
-  const int grid = c.N * a.bands * (c.Cout / 32);
-  if (PB == 16) hipLaunchKernelGGL((conv_rowband_kernel<2, 1, 4>), dim3(grid), dim3(512), 0, s, a);
-  else if (PB == 32) hipLaunchKernelGGL((conv_rowband_kernel<2, 2, 2>), dim3(grid), dim3(512), 0, s, a);
-  else if (PB == 64) hipLaunchKernelGGL((conv_rowband_kernel<2, 4, 1>), dim3(grid), dim3(512), 0, s, a);
-  else return -1;
-  return pl ? 1 : 0;
+  a.N = c.N; a.H = c.H; a.W = c.W; a.Cout = c.Cout; a.wshift = g.wshift;
+  a.R = g.R; a.bands = g.bands; a.cshift = g.cshift; a.T = g.T; a.wfrag = wfrag ? 1 : 0; a.segs = g.segs;
+  if (wfrag == 2) {  // the activation-staged kernel
+    if (g.PB == 16) hipLaunchKernelGGL((conv_rowband_x_kernel<1, 1>), dim3(g.grid), dim3(512), 0, s, a);
+    else if (g.PB == 32 && g.R == 1) hipLaunchKernelGGL((conv_rowband_x_kernel<2, 1>), dim3(g.grid), dim3(512), 0, s, a);
+    else if (g.PB == 32) hipLaunchKernelGGL((conv_rowband_x_kernel<2, 2>), dim3(g.grid), dim3(512), 0, s, a);
+    else hipLaunchKernelGGL((conv_rowband_x_kernel<4, 2>), dim3(g.grid), dim3(512), 0, s, a);
+  } else if (g.PB == 16) hipLaunchKernelGGL((conv_rowband_kernel<2, 1, 4>), dim3(g.grid), dim3(512), 0, s, a);
+  else if (g.PB == 32) hipLaunchKernelGGL((conv_rowband_kernel<2, 2, 2>), dim3(g.grid), dim3(512), 0, s, a);
+  else hipLaunchKernelGGL((conv_rowband_kernel<2, 4, 1>), dim3(g.grid), dim3(512), 0, s, a);
+  return g.pools ? 1 : 0;
 }
 
 extern "C" int rdp_conv_rowband_chain(int nl, const void* x, long xbytes, int C0, int xpitch, const void* const* w,

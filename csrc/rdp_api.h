@@ -6,64 +6,8 @@
 
 #include "rdp_host_api.h"
 
-// ---- the conv family's operand blocks ----------------------------------------------------------------------------
-// Activations are NHWC bf16 views: pointer, extent in bytes (the kernels size their buffer descriptors from it;
-// every extent must stay below 2 GiB), channels and pixel pitch in elements. Every field defaults to zero / null;
-// a launcher ignores the fields its kernel has no use for. The blocks hold values only: a launch that is recorded
-// for replay keeps a copy. Host cells a launch writes its result to (int*) are separate parameters.
-struct RdpConv {
-  // the sources: the conv reads cat(x1, x2) along channels (one source: x2 = nullptr, C2 = 0)
-  const void* x1 = nullptr;
-  const void* x2 = nullptr;
-  long xbytes1 = 0, xbytes2 = 0;
-  int C1 = 0, C2 = 0, pitch1 = 0, pitch2 = 0;
-  // the weights, bf16 [Cout][ldw]
-  const void* w = nullptr;
-  long wbytes = 0;
-  int ldw = 0;
-  // the destinations: output channels [0, Cy1) go to y1, [Cy1, Cout) to y2 (one destination: y2 = nullptr)
-  void* y1 = nullptr;
-  void* y2 = nullptr;
-  long ybytes1 = 0, ybytes2 = 0;
-  int Cy1 = 0, ypitch1 = 0, ypitch2 = 0;
-  float* stats = nullptr;  // training: the BN partial (sum, sum of squares) rows, [rows][2][Cout]
-  int N = 0, H = 0, W = 0, Cout = 0;
-  // the eval epilogue y = acc * escale[c] + eshift[c], then ReLU if erelu (both null: none)
-  const float* escale = nullptr;
-  const float* eshift = nullptr;
-  int erelu = 0;
-};
-// rdp_conv_igemm, eval, optional: MaxPool2d(2) of y1 into pool [N][H/2][W/2][Cout], or (exclusive) the bilinear
-// x2 upsample of y1 into up [N][uH][uW][Cout] at (uoy, uox), fused into the split-K reduce when that path runs
-struct RdpConvFuse {
-  void* pool = nullptr;
-  int ppitch = 0;
-  void* up = nullptr;
-  int upitch = 0, uH = 0, uW = 0, uoy = 0, uox = 0;
-};
-// rdp_conv_igemm, training dgrad into one BN + ReLU layer's activation gradient, optional: that layer's pre-BN
-// output bny, its coefficients bncoef [mean|invstd|scale|shift], and bnpart, which receives its BN-backward partial
-// rows from the split-K reduce when that path runs
-struct RdpConvBnBwd {
-  const void* bny = nullptr;
-  int bnypitch = 0;
-  const float* bncoef = nullptr;
-  float* bnpart = nullptr;
-};
-// rdp_conv_ring_ex, optional and exclusive: bn_y / bn_coef = the dgrad form (the BN-backward partial rows of the
-// layer that owns the output go to stats; bn_y: its pre-BN activations, bn_coef: its [mean|invstd|scale|shift],
-// ReLU applied); iscale / ishift = BN + ReLU of the producer layer applied to the staged input rows, which aout
-// (optional) also receives as an activation tensor
-struct RdpRingFuse {
-  const void* bn_y = nullptr;
-  int bn_ypitch = 0;
-  const float* bn_coef = nullptr;
-  const float* iscale = nullptr;
-  const float* ishift = nullptr;
-  void* aout = nullptr;
-  long abytes = 0;
-  int apitch = 0;
-};
+// The conv family's operand blocks (RdpConv, RdpConvFuse, RdpConvBnBwd, RdpRingFuse), the kernel names and the plan
+#include "conv_plan.h"
 
 extern "C" {
 
@@ -74,14 +18,11 @@ int rdp_comm_emulate_traffic(double us, int blocks, void* scratch, long scratch_
                              hipStream_t s);
 
 // ---- csrc/conv_first.hip --------------------------------------------------------------------------------------
-// Returns the number of stats rows written (training) / 0, or -1 if the shape is not this kernel's
-// (3-channel input stored with pitch >= 4, 64 couts, packed [64][128] weights).
+// Returns the number of stats rows written (training) / 0, or -1 if the conv is not this kernel's (rdp_first_geo).
 int rdp_conv_first(const RdpConv& c, hipStream_t s);
 
 // ---- csrc/conv_halo.hip ---------------------------------------------------------------------------------------
-// Number of 256-pixel output tiles x cout tiles the halo kernel would use (0 = shape unsupported).
-int rdp_conv_halo_tiles(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed);
-// Returns stats rows written (>= 0) or -1 if unsupported.
+// Returns stats rows written (>= 0) or -1 if unsupported (rdp_halo_geo).
 int rdp_conv_halo(const RdpConv& c, hipStream_t s);
 
 // ---- csrc/conv_igemm.hip --------------------------------------------------------------------------------------
@@ -102,21 +43,20 @@ int rdp_conv_upT_fwd(const void* x, long xbytes, int Cin, int pitch, const void*
 int rdp_conv_upT_dgrad(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
                        const void* wd, long wbytes, int ldw, void* dx, long dxbytes, int Cin, int dxpitch, int N,
                        int h, int wdt, hipStream_t s);
-// The conv dispatcher: forwards to the first-layer, row-band, row-ring and halo launchers where they apply, else
-// runs this file's implicit GEMM. Returns the number of stats-slab rows written, or -1 on unsupported shape.
-// bm_pref % 1000: 0 = auto, else force one kernel (see the definition); bm_pref / 1000: blocks per CU of the
-// persistent grid (0 = 2). ws: the split-K fp32 slab of ws_elems elements (rdp_conv_ws_elems), or nullptr.
-// *pooled = 1 if fuse's pool / upsample was written, else 0 (the caller launches the pool / upsample; nullptr: no
-// fusion). *bnrows = the rows written to bn.bnpart, else 0 (the caller runs bn_relu_bwd_reduce).
-int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int bm_pref, float* ws, long ws_elems,
-                   const RdpConvFuse& fuse, int* pooled, const RdpConvBnBwd& bn, int* bnrows, hipStream_t s);
-// fp32 workspace elements the auto dispatch would use for split-K on this shape (0 = no split)
-long rdp_conv_ws_elems(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed, int bm_pref);
+// The conv dispatcher: launches what rdp_conv_plan (conv_plan.h) picks. Returns the number of stats-slab rows
+// written, or -1 (nothing launched) where the plan is unsupported. kernel: RDP_CONV_AUTO, or the RdpConvKernel to
+// force. ws: the split-K fp32 slab of ws_elems elements (rdp_conv_ws_elems), or nullptr. wfrag / wfrag_bytes: the
+// fragment-major copy of the weights for the row-band kernel, or nullptr. *pooled = 1 if fuse's pool / upsample was
+// written, else 0 (the caller launches the pool / upsample; nullptr: no fusion). *bnrows = the rows written to
+// bn.bnpart, else 0 (the caller runs bn_relu_bwd_reduce).
+int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int kernel, float* ws, long ws_elems, const void* wfrag,
+                   long wfrag_bytes, const RdpConvFuse& fuse, int* pooled, const RdpConvBnBwd& bn, int* bnrows,
+                   hipStream_t s);
 
 // ---- csrc/conv_ring.hip ---------------------------------------------------------------------------------------
 // The ring kernel (3x3, one 64-channel source, 64 or 128 outputs -- split at a multiple of 32 into two
-// destinations --, W % 64 == 0, even H); max_blocks caps the grid (<= 0: 256). Returns the stats rows it writes,
-// or -1 when not applicable.
+// destinations --, W % 64 == 0, even H: rdp_ring_geo); max_blocks caps the grid (<= 0: 256). Returns the stats
+// rows it writes, or -1 when not applicable.
 int rdp_conv_ring(const RdpConv& c, int max_blocks, hipStream_t s);
 int rdp_conv_ring_ex(const RdpConv& c, int max_blocks, const RdpRingFuse& f, hipStream_t s);
 // Eval conv (64 -> 64, BN folded + ReLU) fused with the serving 1x1 head: writes only the u8 mask
@@ -142,19 +82,10 @@ int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipStream_t s);
 int rdp_conv_ring2(const RdpConv& c, int max_blocks, int cout_total, int co0, hipStream_t s);
 
 // ---- csrc/conv_rowband.hip ------------------------------------------------------------------------------------
-// Operand bytes the kernel moves from L2 (every block re-reads its weight slice; every activation is read
-// once per tap and per 32-channel output slice): the dispatcher's traffic model.
-long rdp_conv_rowband_bytes(int N, int H, int W, int Cin, int Cout, int pool);
-// C1 / C2: the two sources' channels (C2 = 0 for one source). Every shape predicate rdp_conv_rowband_ex
-// applies is checked here too, so a mode this returns is never rejected by the launch (W and Cin / 32
-// powers of two, each source a multiple of 32 channels); the Python executor asks this same function
-// (binding rowband_frag_mode) which layers need a fragment-major weight copy.
-int rdp_conv_rowband_frag_auto(int N, int H, int W, int C1, int C2, int Cout);
 // Eval conv on the row-band kernel into y1; pool (optional, pbytes / ppitch): MaxPool2d(2) of the output where the
 // kernel can fuse it. Returns 1 if it also wrote the pool, 0 if not, < 0 (nothing launched) when the shape does
 // not fit. wfrag 1: w is the fragment-major copy of the OHWI weights instead of OHWI; 2: that copy on the
-// activation-staged kernel (rdp_conv_rowband_frag_auto picks); rdp_conv_rowband = wfrag 0.
-int rdp_conv_rowband(const RdpConv& c, void* pool, long pbytes, int ppitch, hipStream_t s);
+// activation-staged kernel (rdp_rowband_frag_mode picks).
 int rdp_conv_rowband_ex(const RdpConv& c, void* pool, long pbytes, int ppitch, int wfrag, hipStream_t s);
 // The chain launch: layer 0 reads x (C0 channels), layer l > 0 reads layer l - 1's output; every layer is
 // an eval conv (BN folded + ReLU) on the same N x H x W map. cnt: >= 1 + nl * N * H ints, err: 1 int.

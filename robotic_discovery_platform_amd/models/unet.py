@@ -671,7 +671,8 @@ class UNetExecutor:
         self.loss_sums = torch.zeros(4 if self.K == 1 else 2 + 3 * self.K, dtype=torch.float32, device=dev)
         self.loss = torch.zeros(2, dtype=torch.float32, device=dev)
         # stats slab (reused by every conv; finalize runs right after each conv)
-        max_rows = max(C.conv_stats_rows(L.x1.shape[0] * L.x1.shape[1] * L.x1.shape[2], L.spec.cout, 0) * 2 * L.spec.cout
+        max_rows = max(C.conv_stats_rows(L.x1.shape[0] * L.x1.shape[1] * L.x1.shape[2], L.spec.cout,
+                                         C.CONV_AUTO) * 2 * L.spec.cout
                        for L in self.layers)
         self.stats = torch.zeros(max_rows, dtype=torch.float32, device=dev)
         # SyncBatchNorm (optional): process group whose ranks share batch statistics.
@@ -689,14 +690,14 @@ class UNetExecutor:
         for L in self.layers:
             n, h, w, c1 = L.x1.shape
             c2 = L.x2.shape[3] if L.x2 is not None else 0
-            ws = max(ws, C.conv_ws_elems(n, h, w, c1, c2, L.spec.cout, L.spec.taps, int(L.spec.packed), 0))
+            ws = max(ws, C.conv_ws_elems(n, h, w, c1, c2, L.spec.cout, L.spec.taps, int(L.spec.packed), C.CONV_AUTO))
             if training and not L.spec.packed:  # dgrad: dy (cout ch) -> d(input) (c1 + c2 ch)
-                ws = max(ws, C.conv_ws_elems(n, h, w, L.spec.cout, 0, c1 + c2, L.spec.taps, 0, 0))
+                ws = max(ws, C.conv_ws_elems(n, h, w, L.spec.cout, 0, c1 + c2, L.spec.taps, 0, C.CONV_AUTO))
         for i, us in enumerate(model.up_specs):
             n, h, w, _ = self.yTs[i].shape
-            ws = max(ws, C.conv_ws_elems(n, h, w, us.cin, 0, 4 * us.cout, 1, 0, 0))
+            ws = max(ws, C.conv_ws_elems(n, h, w, us.cin, 0, 4 * us.cout, 1, 0, C.CONV_AUTO))
             if training:
-                ws = max(ws, C.conv_ws_elems(n, h, w, 4 * us.cout, 0, us.cin, 1, 0, 0))
+                ws = max(ws, C.conv_ws_elems(n, h, w, 4 * us.cout, 0, us.cin, 1, 0, C.CONV_AUTO))
         self.kws = torch.zeros(ws, dtype=torch.float32, device=dev) if ws else None
         self._frag_names = frozenset()  # layers whose fragment-major eval weights prepare_eval refreshed
         if training:
@@ -841,17 +842,18 @@ class UNetExecutor:
             if up is not None:
                 oy = (up.shape[1] - 2 * L.a.shape[1]) // 2
                 ox = (up.shape[2] - 2 * L.a.shape[2]) // 2
-                C.conv_fwd(L.x1, L.x2, w, sp.taps, int(sp.packed), L.a, None, None, 0, L.coef, 1, self.kws, None, up,
-                           oy, ox, wf)
+                C.conv_fwd(L.x1, L.x2, w, sp.taps, int(sp.packed), L.a, None, None, C.CONV_AUTO, L.coef, 1, self.kws,
+                           None, up, oy, ox, wf)
                 return True
-            C.conv_fwd(L.x1, L.x2, w, sp.taps, int(sp.packed), L.a, None, None, 0, L.coef, 1, self.kws, pool, None, 0, 0,
-                       wf)
+            C.conv_fwd(L.x1, L.x2, w, sp.taps, int(sp.packed), L.a, None, None, C.CONV_AUTO, L.coef, 1, self.kws,
+                       pool, None, 0, 0, wf)
             return pool is not None
         if L.bnin is not None:  # the producer's BN + ReLU applied by this conv (row-ring BNIN)
             rows = C.conv_fwd_bnin(L.bnin.y, w, L.y, self.stats, L.bnin.coef, L.bnin.a)
             assert rows > 0, "conv_fwd_bnin: ring kernel not applicable"
         else:
-            rows = C.conv_fwd(L.x1, L.x2, w, sp.taps, int(sp.packed), L.y, None, self.stats, 0, None, 0, self.kws)
+            rows = C.conv_fwd(L.x1, L.x2, w, sp.taps, int(sp.packed), L.y, None, self.stats, C.CONV_AUTO, None, 0,
+                              self.kws)
         g = m.store.view(sp.bn + ".weight")
         b = m.store.view(sp.bn + ".bias")
         if self.training:
@@ -952,8 +954,8 @@ class UNetExecutor:
                 # the sub-pixel scatter + bias in the ping-pong GEMM's epilogue where that kernel takes the
                 # shape (u's zero border is never written); else the GEMM into yT + the shuffle pass
                 if C.conv_upT_fwd(low, self.m.upT_fwd_weight(us), bias, u, oy, ox) != 0:
-                    C.conv_fwd(low, None, self.m.upT_fwd_weight(us), 1, 0, self.yTs[i - 1], None, None, 0, None, 0,
-                               self.kws)
+                    C.conv_fwd(low, None, self.m.upT_fwd_weight(us), 1, 0, self.yTs[i - 1], None, None, C.CONV_AUTO,
+                               None, 0, self.kws)
                     C.upT_shuffle(self.yTs[i - 1], bias, u, oy, ox)
             la, lb = self.up_layers[i - 1]
             self._conv_bn_relu(C, la)
@@ -1250,7 +1252,8 @@ class UNetExecutor:
                 owner.bwd_rows = rows
                 done = True
         if L.dx1 is not None and not done:
-            C.conv_fwd(L.dy, None, self.m.dgrad_weight(sp), sp.taps, 0, L.dx1, L.dx2, None, 0, None, 0, self.kws)
+            C.conv_fwd(L.dy, None, self.m.dgrad_weight(sp), sp.taps, 0, L.dx1, L.dx2, None, C.CONV_AUTO, None, 0,
+                       self.kws)
         if hooks is not None:  # the weight gradient is final once its stream's work so far has run
             hooks(sp, wstream)
 
@@ -1335,15 +1338,15 @@ class UNetExecutor:
                                           C.conv_wgrad_upT(du, xa, 0, 0, slab, g, 0, ns))
                     if C.conv_upT_dgrad(du, self.m.upT_dgrad_weight(us), low_layer.da, 0, 0) != 0:
                         C.upT_unshuffle(du, dyT, oy, ox)
-                        C.conv_fwd(dyT, None, self.m.upT_dgrad_weight(us), 1, 0, low_layer.da, None, None, 0, None,
-                                   0, self.kws)
+                        C.conv_fwd(dyT, None, self.m.upT_dgrad_weight(us), 1, 0, low_layer.da, None, None,
+                                   C.CONV_AUTO, None, 0, self.kws)
                 else:
                     C.upT_unshuffle(du, dyT, oy, ox)
                     C.colsum_bf16(dyT, 4, self.colsum_ws, bgrad, 0)
                     self._on_wgrad_stream(lambda slab, dyT=dyT, xa=low_layer.a, us=us, ns=ns, g=wgrad:
                                           C.conv_wgrad(dyT, None, xa, 1, 0, 4 * us.cout, slab, g, 0, ns, 0))
-                    C.conv_fwd(dyT, None, self.m.upT_dgrad_weight(us), 1, 0, low_layer.da, None, None, 0, None, 0,
-                               self.kws)
+                    C.conv_fwd(dyT, None, self.m.upT_dgrad_weight(us), 1, 0, low_layer.da, None, None, C.CONV_AUTO,
+                               None, 0, self.kws)
                 if grad_hook is not None:  # bias (main) + weight (side, forked after the bias)
                     grad_hook(us, self.side if self.side is not None else torch.cuda.current_stream())
         for i in range(D, 0, -1):

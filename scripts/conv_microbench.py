@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B microbenchmark of conv kernel variants on the U-Net's layer shapes (one process, interleaved).
 
-usage: python scripts/conv_microbench.py [--batch 32] [--variants 0,1] [--reps 10] [--wgrad]
+usage: python scripts/conv_microbench.py [--batch 32] [--variants AUTO,HALO] [--reps 10] [--wgrad]
 Prints TF/s per (layer, variant): median over interleaved rounds (cdna_hip_programming.md §5.4 r24).
 """
 import argparse
@@ -27,7 +27,8 @@ SHAPES = [  # (H, Cin1, Cin2, Cout)   spatial = H x H
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--variants", default="0,1")
+    ap.add_argument("--variants", default="AUTO,HALO",
+                    help="conv kernels by name (the extension's CONV_<name>) or number; 9 / 10: the BN-on-input ring")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--wgrad", action="store_true")
@@ -40,7 +41,7 @@ def main():
     a = ap.parse_args()
     C = native()
     dev = torch.device("cuda")
-    variants = [int(v) for v in a.variants.split(",")]
+    variants = [int(v) if v.isdigit() else getattr(C, "CONV_" + v.upper()) for v in a.variants.split(",")]
     results = []
     shapes = SHAPES if a.shapes is None else [SHAPES[int(i)] for i in a.shapes.split(",")]
     for (H, C1, C2, Co) in shapes:
@@ -50,7 +51,7 @@ def main():
         Cin = C1 + C2
         w = (torch.randn(Co, 9 * Cin, device=dev) * 0.02).to(torch.bfloat16)
         y = torch.empty(N, H, H, Co, dtype=torch.bfloat16, device=dev)
-        stats = torch.zeros(max(C.conv_stats_rows(N * H * H, Co, 0), 1024) * 2 * Co, device=dev)
+        stats = torch.zeros(max(C.conv_stats_rows(N * H * H, Co, C.CONV_AUTO), 1024) * 2 * Co, device=dev)
         flops = 2.0 * N * H * H * 9 * Cin * Co
         times = {v: [] for v in variants}
         ws = None
@@ -81,7 +82,7 @@ def main():
                 if C.conv_fwd_bnin(x1, w, y, stats, coef, a_st if v == 10 else None) <= 0:
                     raise RuntimeError("bnin n/a")
             else:
-                # v = bm_pref (1 halo, 2 igemm 128x128 8-wave, 4 / 5 ping-pong, 7 / 8 split-K ping-pong)
+                # v = the conv kernel to force (C.CONV_*)
                 C.conv_fwd(x1, x2, w, 9, 0, y, None, stats, v, None, 0, ws)
 
         ok = []

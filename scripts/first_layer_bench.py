@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the first-layer conv (3 -> 64, packed K) at the training shape: packed implicit GEMM
-(bm_pref 256) vs conv_first.hip (bm_pref 13), interleaved rounds, median us."""
+(CONV_IGEMM4_256) vs conv_first.hip (CONV_FIRST), interleaved rounds, median us."""
 import os
 import statistics
 import sys
@@ -18,9 +18,9 @@ for N in (64, 4, 1):
     x8[..., :3] = torch.rand(N, H, W, 3, device=dev).to(torch.bfloat16)
     wk = (torch.randn(64, 128, device=dev) * 0.1).to(torch.bfloat16)
     y = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
-    rows = C.conv_stats_rows(N * H * W, 64, 0)
+    rows = C.conv_stats_rows(N * H * W, 64, C.CONV_AUTO)
     st = torch.zeros(rows * 2 * 64, device=dev)
-    times = {256: [], 13: []}
+    times = {C.CONV_IGEMM4_256: [], C.CONV_FIRST: []}
     for p in times:
         C.conv_fwd(x8, None, wk, 9, 1, y, None, st, p, None, 0)
     torch.cuda.synchronize()
@@ -33,5 +33,5 @@ for N in (64, 4, 1):
             e1.record()
             torch.cuda.synchronize()
             times[p].append(e0.elapsed_time(e1) / 10 * 1e3)
-    print(f"N={N}: packed igemm {statistics.median(times[256]):.1f} us, conv_first {statistics.median(times[13]):.1f} us "
+    print(f"N={N}: packed igemm {statistics.median(times[C.CONV_IGEMM4_256]):.1f} us, conv_first {statistics.median(times[C.CONV_FIRST]):.1f} us "
           f"(output {N * H * W * 128 / 1e6:.0f} MB)", flush=True)

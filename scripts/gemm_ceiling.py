@@ -48,9 +48,9 @@ def main():
         x = torch.rand(N, H, H, Cin, device=dev).sub_(0.5).to(torch.bfloat16)
         w = (torch.rand(Cout, K, device=dev).sub_(0.5) * 0.05).to(torch.bfloat16)
         y = torch.empty(N, H, H, Cout, dtype=torch.bfloat16, device=dev)
-        stats = torch.zeros(max(C.conv_stats_rows(M, Cout, 0), 1024) * 2 * Cout, device=dev)
+        stats = torch.zeros(max(C.conv_stats_rows(M, Cout, C.CONV_AUTO), 1024) * 2 * Cout, device=dev)
         gemm = lambda: torch.matmul(A, B)  # noqa: E731
-        conv = lambda: C.conv_fwd(x, None, w, 9, 0, y, None, stats, 0, None, 0)  # noqa: E731
+        conv = lambda: C.conv_fwd(x, None, w, 9, 0, y, None, stats, C.CONV_AUTO, None, 0)  # noqa: E731
         gemm(), conv()
         torch.cuda.synchronize()
         tg, tc = [], []

@@ -49,12 +49,12 @@ def main():
     xc = torch.randn(1, 16, 16, 512, device=dev).to(bf)
     wc = (torch.randn(512, 9 * 512, device=dev) * 0.02).to(bf)
     yc = torch.zeros(1, 16, 16, 512, dtype=bf, device=dev)
-    out["conv_16x16x512_nosplit"] = per_launch(lambda: C.conv_fwd(xc, None, wc, 9, 0, yc, None, None, 0, None, 0),
+    out["conv_16x16x512_nosplit"] = per_launch(lambda: C.conv_fwd(xc, None, wc, 9, 0, yc, None, None, C.CONV_AUTO, None, 0),
                                                k=50)
-    n_ws = C.conv_ws_elems(1, 16, 16, 512, 0, 512, 9, 0, 0)
+    n_ws = C.conv_ws_elems(1, 16, 16, 512, 0, 512, 9, 0, C.CONV_AUTO)
     ws = torch.zeros(n_ws, device=dev)
     out["conv_16x16x512_splitk_pair"] = per_launch(
-        lambda: C.conv_fwd(xc, None, wc, 9, 0, yc, None, None, 0, None, 0, ws), k=50)
+        lambda: C.conv_fwd(xc, None, wc, 9, 0, yc, None, None, C.CONV_AUTO, None, 0, ws), k=50)
     print(json.dumps({k: round(v, 2) for k, v in out.items()}))
 
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Serving-size eval convs (BN folded + ReLU, N = 1): the row-band kernel (bm_pref 16,
-csrc/conv_rowband.hip) against the split-K implicit GEMM + reduce launch pair (bm_pref 2: the 8-wave
+"""Serving-size eval convs (BN folded + ReLU, N = 1): the row-band kernel (CONV_ROWBAND,
+csrc/conv_rowband.hip) against the split-K implicit GEMM + reduce launch pair (CONV_IGEMM8_128: the 8-wave
 128 x 128 kernel the auto dispatch otherwise picks at these shapes).
 
 Each variant runs `--reps` convs back to back inside one captured hipGraph (kernel boundaries included,
@@ -56,7 +56,7 @@ def chain_bench(C, a):
         ys2.append(torch.empty(N, H, H, co, dtype=torch.bfloat16, device=dev))
     cnt = torch.zeros(1 + len(ws) * N * H, dtype=torch.int32, device=dev)
     err = torch.zeros(1, dtype=torch.int32, device=dev)
-    kws = torch.zeros(max(max(C.conv_ws_elems(N, H, H, 512, 0, 512, 9, 0, 2), 1), 1), device=dev)
+    kws = torch.zeros(max(max(C.conv_ws_elems(N, H, H, 512, 0, 512, 9, 0, C.CONV_IGEMM8_128), 1), 1), device=dev)
 
     def per_layer(pref):
         inp = x
@@ -106,7 +106,9 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--variants", default="2,16")
+    ap.add_argument("--variants", default="IGEMM8_128,ROWBAND",
+                    help="conv kernels by name (the extension's CONV_<name>) or number; 17 / 18: conv_rowband on "
+                         "fragment-major weights")
     a = ap.parse_args()
     C = native()
     if a.chain:
@@ -114,7 +116,7 @@ def main():
         return
     dev = torch.device("cuda")
     N = a.batch
-    variants = [int(v) for v in a.variants.split(",")]
+    variants = [int(v) if v.isdigit() else getattr(C, "CONV_" + v.upper()) for v in a.variants.split(",")]
     total = {v: 0.0 for v in variants}
     s = torch.cuda.Stream()
     for (name, H, C1, C2, Co, fuse) in SHAPES:

@@ -50,11 +50,11 @@ def kernel_level(C, rounds, reps, ks=(3, 8), ns=(1, 2, 4)):
             m_fused = torch.empty(M, dtype=torch.uint8, device=dev)
 
             def pair():
-                C.conv_fwd(x, None, wk, 9, 0, a, None, None, 0, coef, 1)
+                C.conv_fwd(x, None, wk, 9, 0, a, None, None, C.CONV_AUTO, coef, 1)
                 C.headk_mask(a, hw, hb, 1, m_pair)
 
             def conv_only():
-                C.conv_fwd(x, None, wk, 9, 0, a, None, None, 0, coef, 1)
+                C.conv_fwd(x, None, wk, 9, 0, a, None, None, C.CONV_AUTO, coef, 1)
 
             def fused():
                 assert C.conv_headk_mask(x, wk, coef, hw, hb, 1, m_fused)

@@ -193,7 +193,8 @@ def outside_view_intact(flat: torch.Tensor, view: torch.Tensor, fill=SENTINEL) -
 
 @dataclass(frozen=True)
 class Conv:
-    """One conv_fwd launch: cat(x1, x2) [N,H,W,C1+C2] -> Cout, forced onto dispatch path `pref`."""
+    """One conv_fwd launch: cat(x1, x2) [N,H,W,C1+C2] -> Cout, on the kernel `pref` names: an RdpConvKernel
+    enumerator of csrc/conv_plan.h without its prefix (the extension exports its value as _C.CONV_<name>)."""
     name: str
     N: int
     H: int
@@ -201,7 +202,7 @@ class Conv:
     C1: int
     C2: int
     Cout: int
-    pref: int
+    pref: str
     taps: int = 9
     packed: bool = False     # first layer: 3 real channels stored as 8, C1 = 8
     cls: str = "exact"       # "exact" | "round"
@@ -239,66 +240,66 @@ S_FIRST2 = (2, 20, 12, 8, 0, 64)
 
 FWD_CASES = [
     # implicit GEMM, 4- and 8-wave tiles, auto
-    _c("auto-256x64", S_TINY, 0),
-    _c("auto-128x128", S_DUAL, 0),
-    _c("tile128-split-views", S_DUAL, 128, split=64, views=True),
-    _c("tile256", S_TINY, 256),
-    _c("wave8-128", S_DUAL, 2),
-    _c("wave8-256-views", S_TINY, 3, views=True),
-    _c("tile128-round", S_DUAL, 128, cls="round", stats=False),
+    _c("auto-256x64", S_TINY, "AUTO"),
+    _c("auto-128x128", S_DUAL, "AUTO"),
+    _c("tile128-split-views", S_DUAL, "IGEMM4_128", split=64, views=True),
+    _c("tile256", S_TINY, "IGEMM4_256"),
+    _c("wave8-128", S_DUAL, "IGEMM8_128"),
+    _c("wave8-256-views", S_TINY, "IGEMM8_256", views=True),
+    _c("tile128-round", S_DUAL, "IGEMM4_128", cls="round", stats=False),
     # ping-pong
-    _c("pp256", S_PP, 4),
-    _c("pp128-split-views", S_PPD, 5, split=128, views=True),
-    _c("pp256-round", S_PP, 4, cls="round", stats=False),
+    _c("pp256", S_PP, "PP256"),
+    _c("pp128-split-views", S_PPD, "PP128", split=128, views=True),
+    _c("pp256-round", S_PP, "PP256", cls="round", stats=False),
     # split-K ping-pong (NaN-filled workspace)
-    _c("ppsk128", S_SK7, 7, ws=True),
-    _c("ppsk256-split", S_SK8, 8, ws=True, split=256),
-    _c("ppsk128-views", (4, 32, 32, 256, 0, 512), 7, ws=True, views=True),
-    _c("ppsk128-round", S_SK7, 7, ws=True, cls="round", stats=False),
+    _c("ppsk128", S_SK7, "PPSK128", ws=True),
+    _c("ppsk256-split", S_SK8, "PPSK256", ws=True, split=256),
+    _c("ppsk128-views", (4, 32, 32, 256, 0, 512), "PPSK128", ws=True, views=True),
+    _c("ppsk128-round", S_SK7, "PPSK128", ws=True, cls="round", stats=False),
     # auto split-K of the implicit GEMM (small M, long K)
-    _c("splitk-auto", (2, 7, 9, 128, 0, 64), 0, ws=True),
-    _c("splitk-auto-dual-split", (1, 8, 8, 256, 256, 256), 0, ws=True, split=128),
-    _c("splitk-auto-round", (1, 8, 8, 256, 256, 256), 0, ws=True, cls="round", stats=False),
+    _c("splitk-auto", (2, 7, 9, 128, 0, 64), "AUTO", ws=True),
+    _c("splitk-auto-dual-split", (1, 8, 8, 256, 256, 256), "AUTO", ws=True, split=128),
+    _c("splitk-auto-round", (1, 8, 8, 256, 256, 256), "AUTO", ws=True, cls="round", stats=False),
     # halo tiles 16 x 16, 64 x 4, 32 x 8
-    _c("halo16", (3, 16, 16, 64, 0, 128), 1),
-    _c("halo64-dual-views", (1, 8, 128, 64, 64, 128), 1, views=True),
-    _c("halo32", (2, 16, 32, 128, 0, 64), 1),
-    _c("halo16-round", (3, 16, 16, 64, 0, 128), 1, cls="round", stats=False),
+    _c("halo16", (3, 16, 16, 64, 0, 128), "HALO"),
+    _c("halo64-dual-views", (1, 8, 128, 64, 64, 128), "HALO", views=True),
+    _c("halo32", (2, 16, 32, 128, 0, 64), "HALO"),
+    _c("halo16-round", (3, 16, 16, 64, 0, 128), "HALO", cls="round", stats=False),
     # row ring, 64 -> 64 and 64 -> 128 (two destinations)
-    _c("ring-3seg", (3, 2, 192, 64, 0, 64), 6),
-    _c("ring-views", (2, 6, 64, 64, 0, 64), 6, views=True),
-    _c("ring-cout128-split", (2, 2, 64, 64, 0, 128), 6, split=64),
-    _c("ring-round", (2, 6, 64, 64, 0, 64), 6, cls="round", stats=False),
-    # two-source ring, 128 -> 64 (pref 14) and 128 -> 128 as halves (pref 15)
-    _c("ring2-concat", (3, 2, 192, 64, 64, 64), 14),
-    _c("ring2-one128-views", (2, 6, 64, 128, 0, 64), 14, views=True),
-    _c("ring2x2-concat", (1, 6, 64, 64, 64, 128), 15),
-    _c("ring2x2-one128-views", (2, 8, 128, 128, 0, 128), 15, views=True),
-    _c("ring2-round", (2, 6, 64, 128, 0, 64), 14, cls="round", stats=False),
+    _c("ring-3seg", (3, 2, 192, 64, 0, 64), "RING"),
+    _c("ring-views", (2, 6, 64, 64, 0, 64), "RING", views=True),
+    _c("ring-cout128-split", (2, 2, 64, 64, 0, 128), "RING", split=64),
+    _c("ring-round", (2, 6, 64, 64, 0, 64), "RING", cls="round", stats=False),
+    # two-source ring, 128 -> 64 (RING2) and 128 -> 128 as halves (RING2X2)
+    _c("ring2-concat", (3, 2, 192, 64, 64, 64), "RING2"),
+    _c("ring2-one128-views", (2, 6, 64, 128, 0, 64), "RING2", views=True),
+    _c("ring2x2-concat", (1, 6, 64, 64, 64, 128), "RING2X2"),
+    _c("ring2x2-one128-views", (2, 8, 128, 128, 0, 128), "RING2X2", views=True),
+    _c("ring2-round", (2, 6, 64, 128, 0, 64), "RING2", cls="round", stats=False),
     # first layer, packed (K = 27: the rounding case needs operands in -7..7 to reach 256)
-    _c("first", S_FIRST, 13, packed=True),
-    _c("first-views", S_FIRST2, 13, packed=True, views=True),
-    _c("first-round", S_FIRST2, 13, packed=True, cls="round", stats=False, amax=7),
+    _c("first", S_FIRST, "FIRST", packed=True),
+    _c("first-views", S_FIRST2, "FIRST", packed=True, views=True),
+    _c("first-round", S_FIRST2, "FIRST", packed=True, cls="round", stats=False, amax=7),
     # taps = 1 (the transposed decoder's GEMMs)
-    _c("taps1-auto", (1, 4, 5, 256, 0, 512), 0, taps=1),
-    _c("taps1-pp128", (3, 20, 52, 256, 0, 512), 5, taps=1, stats=False),
+    _c("taps1-auto", (1, 4, 5, 256, 0, 512), "AUTO", taps=1),
+    _c("taps1-pp128", (3, 20, 52, 256, 0, 512), "PP128", taps=1, stats=False),
 ]
 
 EVAL_CASES = [
-    _c("eval-tile128", S_DUAL, 128, evalmode=True, stats=False),
-    _c("eval-splitk-auto-pool", (1, 8, 8, 256, 256, 256), 0, ws=True, evalmode=True, pool=True, stats=False),
-    _c("eval-ppsk256-pool", S_SK8, 8, ws=True, evalmode=True, pool=True, stats=False),
-    _c("eval-halo64-views", (1, 8, 128, 64, 64, 128), 1, evalmode=True, views=True, stats=False),
-    _c("eval-ring-pool", (2, 6, 64, 64, 0, 64), 6, evalmode=True, pool=True, stats=False),
-    _c("eval-ring2", (2, 6, 64, 128, 0, 64), 14, evalmode=True, stats=False),
-    _c("eval-ring2x2", (1, 6, 64, 64, 64, 128), 15, evalmode=True, stats=False),
-    _c("eval-first", S_FIRST, 13, packed=True, evalmode=True, stats=False),
+    _c("eval-tile128", S_DUAL, "IGEMM4_128", evalmode=True, stats=False),
+    _c("eval-splitk-auto-pool", (1, 8, 8, 256, 256, 256), "AUTO", ws=True, evalmode=True, pool=True, stats=False),
+    _c("eval-ppsk256-pool", S_SK8, "PPSK256", ws=True, evalmode=True, pool=True, stats=False),
+    _c("eval-halo64-views", (1, 8, 128, 64, 64, 128), "HALO", evalmode=True, views=True, stats=False),
+    _c("eval-ring-pool", (2, 6, 64, 64, 0, 64), "RING", evalmode=True, pool=True, stats=False),
+    _c("eval-ring2", (2, 6, 64, 128, 0, 64), "RING2", evalmode=True, stats=False),
+    _c("eval-ring2x2", (1, 6, 64, 64, 64, 128), "RING2X2", evalmode=True, stats=False),
+    _c("eval-first", S_FIRST, "FIRST", packed=True, evalmode=True, stats=False),
     # row band (eval only), forced and through the fragment-major weights
-    _c("rowband-dual", (3, 16, 32, 64, 64, 96), 16, evalmode=True, stats=False),
-    _c("rowband-pool-views", (2, 16, 16, 256, 256, 128), 16, evalmode=True, pool=True, views=True, stats=False),
-    _c("rowband-round", (3, 16, 32, 64, 64, 96), 16, evalmode=True, cls="round", stats=False),
-    _c("wfrag-mode1", (1, 16, 16, 64, 0, 64), 0, evalmode=True, wfrag=1, stats=False),
-    _c("wfrag-mode2-pool", (1, 16, 16, 256, 0, 128), 0, evalmode=True, wfrag=2, pool=True, stats=False),
+    _c("rowband-dual", (3, 16, 32, 64, 64, 96), "ROWBAND", evalmode=True, stats=False),
+    _c("rowband-pool-views", (2, 16, 16, 256, 256, 128), "ROWBAND", evalmode=True, pool=True, views=True, stats=False),
+    _c("rowband-round", (3, 16, 32, 64, 64, 96), "ROWBAND", evalmode=True, cls="round", stats=False),
+    _c("wfrag-mode1", (1, 16, 16, 64, 0, 64), "AUTO", evalmode=True, wfrag=1, stats=False),
+    _c("wfrag-mode2-pool", (1, 16, 16, 256, 0, 128), "AUTO", evalmode=True, wfrag=2, pool=True, stats=False),
 ]
 
 
@@ -368,19 +369,19 @@ class Dgrad:
     Cdy: int
     Cs: int
     Cu: int
-    pref: int
+    pref: str
     ws: bool = False
     views: bool = False
     seed: int = 0
 
 
 DGRAD_CASES = [
-    Dgrad("dgrad-auto", 2, 12, 10, 64, 64, 64, 0),
-    Dgrad("dgrad-halo-views", 2, 8, 64, 128, 64, 64, 1, views=True),
-    Dgrad("dgrad-ring", 2, 2, 64, 64, 64, 64, 6),
-    Dgrad("dgrad-pp128", 1, 24, 40, 256, 128, 128, 5),
-    Dgrad("dgrad-ppsk128", 4, 32, 32, 256, 256, 256, 7, ws=True),
-    Dgrad("dgrad-splitk-auto-views", 1, 8, 8, 512, 128, 128, 0, ws=True, views=True),
+    Dgrad("dgrad-auto", 2, 12, 10, 64, 64, 64, "AUTO"),
+    Dgrad("dgrad-halo-views", 2, 8, 64, 128, 64, 64, "HALO", views=True),
+    Dgrad("dgrad-ring", 2, 2, 64, 64, 64, 64, "RING"),
+    Dgrad("dgrad-pp128", 1, 24, 40, 256, 128, 128, "PP128"),
+    Dgrad("dgrad-ppsk128", 4, 32, 32, 256, 256, 256, "PPSK128", ws=True),
+    Dgrad("dgrad-splitk-auto-views", 1, 8, 8, 512, 128, 128, "AUTO", ws=True, views=True),
 ]
 
 

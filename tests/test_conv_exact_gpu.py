@@ -56,8 +56,13 @@ def _out(shape, views, pads=(8, 24)):
     return Buf(None, shape, views, pads)
 
 
+def _kernel(C, pref):
+    """The value of the RdpConvKernel enumerator a case names."""
+    return getattr(C, "CONV_" + pref)
+
+
 def _ws(C, c_shape, taps, pref):
-    n = C.conv_ws_elems(*c_shape, taps, 0, pref)
+    n = C.conv_ws_elems(*c_shape, taps, 0, _kernel(C, pref))
     assert n > 0, "the case is meant to run split-K"
     return torch.full((n,), NAN, device=DEV)  # every slab element is written before the reduce reads it
 
@@ -102,12 +107,15 @@ def test_conv_fwd_exact(C, c):
     y2 = _out(shape + (c.Cout - c.split,), c.views, (24, 8)) if c.split else None
     stats = None
     if c.stats:
-        rows = C.conv_stats_rows(c.M, c.Cout, c.pref)
+        rows = C.conv_stats_rows(c.M, c.Cout, _kernel(C, c.pref))
         stats = torch.full((rows * 2 * c.Cout,), NAN, device=DEV)  # rows [:r] are written, never accumulated
     ws = _ws(C, (c.N, c.H, c.W, c.C1, c.C2, c.Cout), c.taps, c.pref) if c.ws else None
-    r = C.conv_fwd(x1.t, x2.t if x2 else None, wk, c.taps, int(c.packed), y1.t, y2.t if y2 else None, stats, c.pref,
-                   None, 0, ws)
+    r = C.conv_fwd(x1.t, x2.t if x2 else None, wk, c.taps, int(c.packed), y1.t, y2.t if y2 else None, stats,
+                   _kernel(C, c.pref), None, 0, ws)
     torch.cuda.synchronize()
+    plan = C.conv_plan(c.N, c.H, c.W, c.C1, c.C2, c.Cout, c.taps, int(c.packed), _kernel(C, c.pref), stats=c.stats,
+                       split=c.split, ws_elems=ws.numel() if c.ws else 0)
+    assert r == plan["stats_rows"], (r, plan)
     exp = L.expected_bf16(ref)
     got = y1.t.cpu() if y2 is None else torch.cat([y1.t.cpu(), y2.t.cpu()], -1)
     assert torch.equal(got, exp)
@@ -129,7 +137,7 @@ def test_conv_fwd_exact(C, c):
 def test_conv_eval_exact(C, c):
     """Eval epilogue relu(scale * y + shift) with scale = +-2^k and integer shift (exact in fp32, fused or
     not), and the fused MaxPool2d(2) output (max is exact): bitwise against the fp64 reference. Row-band
-    paths: forced (16) and through the fragment-major weight copy where rowband_frag_mode selects it."""
+    paths: forced (ROWBAND) and through the fragment-major weight copy where rowband_frag_mode selects it."""
     x1, x2, wk, ref = _conv_operands(c)
     L.check_conv_case(c, ref)
     sc, sh = L.eval_coef(c)
@@ -142,9 +150,12 @@ def test_conv_eval_exact(C, c):
         from robotic_discovery_platform_amd.models.unet import rowband_frag_weights
         assert C.rowband_frag_mode(c.N, c.H, c.W, c.C1, c.C2, c.Cout) == c.wfrag
         wfrag = rowband_frag_weights(wk)
-    C.conv_fwd(x1.t, x2.t if x2 else None, wk, c.taps, int(c.packed), y.t, None, None, c.pref, affine, 1, ws,
-               p.t if p else None, None, 0, 0, wfrag)
+    r = C.conv_fwd(x1.t, x2.t if x2 else None, wk, c.taps, int(c.packed), y.t, None, None, _kernel(C, c.pref), affine,
+                   1, ws, p.t if p else None, None, 0, 0, wfrag)
     torch.cuda.synchronize()
+    plan = C.conv_plan(c.N, c.H, c.W, c.C1, c.C2, c.Cout, c.taps, int(c.packed), _kernel(C, c.pref), eval=True,
+                       ws_elems=ws.numel() if c.ws else 0, pool=c.pool, wfrag=bool(c.wfrag))
+    assert r == plan["stats_rows"], (r, plan)
     exp = L.expected_bf16(L.eval_ref(c, ref))
     assert torch.equal(y.t.cpu(), exp)
     if c.pool:
@@ -170,8 +181,11 @@ def test_conv_dgrad_exact(C, c):
     d1 = _out((c.N, c.H, c.W, c.Cs), c.views)
     d2 = _out((c.N, c.H, c.W, c.Cu), c.views, (24, 8))
     ws = _ws(C, (c.N, c.H, c.W, c.Cdy, 0, Cdx), 9, c.pref) if c.ws else None
-    assert C.conv_fwd(a.t, None, wt, 9, 0, d1.t, d2.t, None, c.pref, None, 0, ws) >= 0
+    r = C.conv_fwd(a.t, None, wt, 9, 0, d1.t, d2.t, None, _kernel(C, c.pref), None, 0, ws)
     torch.cuda.synchronize()
+    plan = C.conv_plan(c.N, c.H, c.W, c.Cdy, 0, Cdx, 9, 0, _kernel(C, c.pref), split=c.Cs,
+                       ws_elems=ws.numel() if c.ws else 0)
+    assert r >= 0 and r == plan["stats_rows"], (r, plan)
     exp = L.expected_bf16(dx)
     assert torch.equal(d1.t.cpu(), exp[..., :c.Cs])
     assert torch.equal(d2.t.cpu(), exp[..., c.Cs:])
@@ -191,7 +205,7 @@ def test_conv_dgrad_bnred_exact(C, b):
     out = torch.full((b.N, b.H, b.W, b.Cdx), L.SENTINEL, dtype=L.BF16, device=DEV)
     part = torch.full((1024 * 2 * b.Cdx,), NAN, device=DEV)
     if b.splitk:
-        ws = _ws(C, (b.N, b.H, b.W, b.Cdy, 0, b.Cdx), 9, 0)
+        ws = _ws(C, (b.N, b.H, b.W, b.Cdy, 0, b.Cdx), 9, "AUTO")
         T = C.conv_dgrad_splitk_bnred(dy.to(DEV), wt, out, y.to(DEV), coef.to(DEV), part, ws)
     else:
         T = C.conv_dgrad_bnred(dy.to(DEV), wt, out, y.to(DEV), coef.to(DEV), part)
@@ -309,12 +323,12 @@ def test_upT_small_gemms_wgrad_colsum_exact(C, c):
     x, du = d["x"].to(DEV), d["du"].to(DEV)
     # forward GEMM (bias is added by the shuffle pass, not here)
     yT = torch.full((c.N, c.h, c.w, 4 * c.C), L.SENTINEL, dtype=L.BF16, device=DEV)
-    C.conv_fwd(x, None, wf.to(DEV), 1, 0, yT, None, None, 0, None, 0)
+    C.conv_fwd(x, None, wf.to(DEV), 1, 0, yT, None, None, C.CONV_AUTO, None, 0)
     assert torch.equal(yT.cpu(), L.expected_bf16(L.upT_window(c, d["u"]) - d["bias"].double().repeat(4)))
     # input gradient GEMM on the unshuffled window
     dyT = L.upT_window(c, d["du"]).to(DEV)
     dx = torch.full((c.N, c.h, c.w, c.Cin), L.SENTINEL, dtype=L.BF16, device=DEV)
-    C.conv_fwd(dyT, None, wd.to(DEV), 1, 0, dx, None, None, 0, None, 0)
+    C.conv_fwd(dyT, None, wd.to(DEV), 1, 0, dx, None, None, C.CONV_AUTO, None, 0)
     assert torch.equal(dx.cpu(), L.expected_bf16(d["dx"]))
     # weight gradient [Cin][(dh, dw, c)]
     dW = d["dW"].permute(0, 2, 3, 1).reshape(-1).float()

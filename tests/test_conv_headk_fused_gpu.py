@@ -57,7 +57,7 @@ def _pair(C, x, wk, coef, hw, hb, cls, a=None):
     N, H, W, _ = x.shape
     if a is None:
         a = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device="cuda")
-        C.conv_fwd(x, None, wk, 9, 0, a, None, None, 0, coef, 1)
+        C.conv_fwd(x, None, wk, 9, 0, a, None, None, C.CONV_AUTO, coef, 1)
     ref = torch.full((N * H * W,), SENTINEL, dtype=torch.uint8, device="cuda")
     C.headk_mask(a, hw.reshape(-1), hb, cls, ref)
     return ref, a

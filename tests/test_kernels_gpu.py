@@ -48,9 +48,9 @@ def test_conv_fwd_and_stats(C, N, H, W, C1, C2, Cout):
     x2 = bf(torch.randn(N, H, W, C2, device=dev)) if C2 else None
     w = bf(torch.randn(Cout, C1 + C2, 3, 3, device=dev) / math.sqrt(9 * (C1 + C2)))
     y = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
-    rows = C.conv_stats_rows(N * H * W, Cout, 0)
+    rows = C.conv_stats_rows(N * H * W, Cout, C.CONV_AUTO)
     stats = torch.zeros(rows * 2 * Cout, device=dev)
-    r = C.conv_fwd(x1, x2, ohwi(w).contiguous(), 9, 0, y, None, stats, 0, None, 0)
+    r = C.conv_fwd(x1, x2, ohwi(w).contiguous(), 9, 0, y, None, stats, C.CONV_AUTO, None, 0)
     assert 0 < r <= rows
     xin = nchw(x1).float() if x2 is None else torch.cat([nchw(x1), nchw(x2)], 1).float()
     ref = F.conv2d(xin, w.float(), padding=1)
@@ -65,16 +65,16 @@ def test_conv_fwd_and_stats(C, N, H, W, C1, C2, Cout):
     (2, 8, 64, 64, 0, 64), (1, 8, 128, 64, 64, 128), (2, 16, 32, 128, 0, 64), (1, 32, 32, 128, 128, 256),
     (3, 16, 16, 64, 0, 128), (2, 32, 16, 256, 0, 64)])
 def test_conv_halo_fwd_and_stats(C, N, H, W, C1, C2, Cout):
-    """Halo-tile kernel (bm_pref=1) on every tile shape (64x4, 32x8, 16x16), BN=64/128, concat input."""
+    """Halo-tile kernel (CONV_HALO) on every tile shape (64x4, 32x8, 16x16), BN=64/128, concat input."""
     torch.manual_seed(3)
     dev = "cuda"
     x1 = bf(torch.randn(N, H, W, C1, device=dev))
     x2 = bf(torch.randn(N, H, W, C2, device=dev)) if C2 else None
     w = bf(torch.randn(Cout, C1 + C2, 3, 3, device=dev) / math.sqrt(9 * (C1 + C2)))
     y = torch.full((N, H, W, Cout), float("nan"), dtype=torch.bfloat16, device=dev)
-    rows = C.conv_stats_rows(N * H * W, Cout, 0)
+    rows = C.conv_stats_rows(N * H * W, Cout, C.CONV_AUTO)
     stats = torch.zeros(rows * 2 * Cout, device=dev)
-    r = C.conv_fwd(x1, x2, ohwi(w).contiguous(), 9, 0, y, None, stats, 1, None, 0)
+    r = C.conv_fwd(x1, x2, ohwi(w).contiguous(), 9, 0, y, None, stats, C.CONV_HALO, None, 0)
     assert 0 < r <= rows
     xin = nchw(x1).float() if x2 is None else torch.cat([nchw(x1), nchw(x2)], 1).float()
     ref = F.conv2d(xin, w.float(), padding=1)
@@ -85,7 +85,7 @@ def test_conv_halo_fwd_and_stats(C, N, H, W, C1, C2, Cout):
     assert torch.allclose(s[1], (yq * yq).sum((0, 2, 3)), rtol=1e-3, atol=1e-2)
     # the halo kernel and the implicit-GEMM kernel agree to bf16 rounding
     y2 = torch.empty_like(y)
-    C.conv_fwd(x1, x2, ohwi(w).contiguous(), 9, 0, y2, None, None, 256, None, 0)
+    C.conv_fwd(x1, x2, ohwi(w).contiguous(), 9, 0, y2, None, None, C.CONV_IGEMM4_256, None, 0)
     assert relerr(y, y2) < 5e-3
 
 
@@ -100,7 +100,7 @@ def test_conv_halo_dgrad_split_and_eval_fold(C):
     wt = w.flip(2, 3).permute(1, 2, 3, 0).reshape(Cs + Cu, 9 * Cout).contiguous()
     d1 = torch.empty(N, H, W, Cs, dtype=torch.bfloat16, device=dev)
     d2 = torch.empty(N, H, W, Cu, dtype=torch.bfloat16, device=dev)
-    assert C.conv_fwd(nhwc(dy), None, wt, 9, 0, d1, d2, None, 1, None, 0) > 0
+    assert C.conv_fwd(nhwc(dy), None, wt, 9, 0, d1, d2, None, C.CONV_HALO, None, 0) > 0
     assert relerr(torch.cat([nchw(d1), nchw(d2)], 1), x.grad) < 1e-2
     # eval BN fold + ReLU epilogue
     g, b = torch.rand(Cout, device=dev) + 0.5, torch.randn(Cout, device=dev)
@@ -109,7 +109,7 @@ def test_conv_halo_dgrad_split_and_eval_fold(C):
     C.bn_eval_coef(g, b, rm, rv, 1e-5, coef)
     xb = bf(torch.randn(N, H, W, Cs + Cu, device=dev))
     a = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(xb, None, ohwi(w).contiguous(), 9, 0, a, None, None, 1, coef, 1)
+    C.conv_fwd(xb, None, ohwi(w).contiguous(), 9, 0, a, None, None, C.CONV_HALO, coef, 1)
     ref = F.relu(F.batch_norm(F.conv2d(nchw(xb).float(), w.float(), padding=1), rm, rv, g, b, False, 0.0, 1e-5))
     assert relerr(nchw(a), ref) < 1e-2
 
@@ -126,7 +126,7 @@ def test_conv_fwd_asymmetric_identity(C):
         for ci in range(Cin):
             w[co, ci, 1, 1] = float((co * 7 + ci * 3) % 11) - 5  # asymmetric, small ints (exact in bf16)
     y = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(bf(x), None, ohwi(bf(w)).contiguous(), 9, 0, y, None, None, 0, None, 0)
+    C.conv_fwd(bf(x), None, ohwi(bf(w)).contiguous(), 9, 0, y, None, None, C.CONV_AUTO, None, 0)
     ref = F.conv2d(nchw(x), w, padding=1)
     assert torch.equal(nchw(y).float(), ref)
 
@@ -142,15 +142,15 @@ def test_conv_packed_first_layer(C):
     wp = torch.zeros(Cout, 16, 8, dtype=torch.bfloat16, device=dev)
     wp[:, :9, :3] = w.permute(0, 2, 3, 1).reshape(Cout, 9, 3)
     y = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x8, None, wp.view(Cout, 128), 9, 1, y, None, None, 0, None, 0)
+    C.conv_fwd(x8, None, wp.view(Cout, 128), 9, 1, y, None, None, C.CONV_AUTO, None, 0)
     ref = F.conv2d(nchw(x8[..., :3]).float(), w.float(), padding=1)
     assert relerr(nchw(y), ref) < 1e-2
 
 
 @pytest.mark.parametrize("N,H,W", [(2, 20, 12), (3, 256, 256), (1, 7, 9), (5, 64, 96)])
 def test_conv_first_layer_kernel(C, N, H, W):
-    """conv_first.hip (bm_pref 13; auto for the packed 3-channel layer) vs the packed implicit GEMM
-    (bm_pref 256) and fp32 torch: training output + BN partial sums, eval BN fold + ReLU; ragged last
+    """conv_first.hip (CONV_FIRST; auto for the packed 3-channel layer) vs the packed implicit GEMM
+    (CONV_IGEMM4_256) and fp32 torch: training output + BN partial sums, eval BN fold + ReLU; ragged last
     segment (M % 64 != 0) and image borders."""
     torch.manual_seed(13)
     dev = "cuda"
@@ -162,9 +162,9 @@ def test_conv_first_layer_kernel(C, N, H, W):
     wp = torch.zeros(Cout, 16, 8, dtype=torch.bfloat16, device=dev)
     wp[:, :9, :3] = w.permute(0, 2, 3, 1).reshape(Cout, 9, 3)
     wk = wp.view(Cout, 128)
-    rows = C.conv_stats_rows(N * H * W, Cout, 0)
+    rows = C.conv_stats_rows(N * H * W, Cout, C.CONV_AUTO)
     ys, ss = [], []
-    for pref in (256, 13):
+    for pref in (C.CONV_IGEMM4_256, C.CONV_FIRST):
         y = torch.full((N, H, W, Cout), 5.0, dtype=torch.bfloat16, device=dev)
         st = torch.zeros(rows * 2 * Cout, device=dev)
         r = C.conv_fwd(x8, None, wk, 9, 1, y, None, st, pref, None, 0)
@@ -179,7 +179,7 @@ def test_conv_first_layer_kernel(C, N, H, W):
     assert torch.allclose(ss[1][1], (yq * yq).sum((0, 2, 3)), rtol=1e-3, atol=1e-1)
     coef = torch.randn(4 * Cout, device=dev)
     a = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x8, None, wk, 9, 1, a, None, None, 13, coef, 1)
+    C.conv_fwd(x8, None, wk, 9, 1, a, None, None, C.CONV_FIRST, coef, 1)
     sc, sh = coef[2 * Cout:3 * Cout].view(1, -1, 1, 1), coef[3 * Cout:].view(1, -1, 1, 1)
     assert relerr(nchw(a), torch.relu(ref * sc + sh)) < 1e-2
 
@@ -197,7 +197,7 @@ def test_conv_dgrad_split_output(C):
     wt = w.flip(2, 3).permute(1, 2, 3, 0).reshape(Cs + Cu, 9 * Cout).contiguous()  # [cin][tap'][cout]
     d1 = torch.empty(N, H, W, Cs, dtype=torch.bfloat16, device=dev)
     d2 = torch.empty(N, H, W, Cu, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(nhwc(dy), None, wt, 9, 0, d1, d2, None, 0, None, 0)
+    C.conv_fwd(nhwc(dy), None, wt, 9, 0, d1, d2, None, C.CONV_AUTO, None, 0)
     got = torch.cat([nchw(d1), nchw(d2)], 1)
     assert relerr(got, x.grad) < 1e-2
 
@@ -376,7 +376,7 @@ def test_conv_dgrad_bnred(C, N, H, W, Cout):
         return
     assert rows > 0
     dx_ref = torch.empty_like(dx)
-    C.conv_fwd(dy, None, wk, 9, 0, dx_ref, None, None, 6, None, 0)  # same ring kernel, no fusion
+    C.conv_fwd(dy, None, wk, 9, 0, dx_ref, None, None, C.CONV_RING, None, 0)  # same ring kernel, no fusion
     torch.cuda.synchronize()
     assert torch.equal(dx, dx_ref)
     conv = F.conv2d(nchw(dy).float(), w.float(), padding=1)
@@ -404,9 +404,9 @@ def test_conv_bnin_fwd_and_wgrad(C, N, H, W):
     w = bf(torch.randn(64, 64, 3, 3, device=dev) * 0.05)
     wk = ohwi(w).contiguous()
     y_ref, y_out = (torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev) for _ in range(2))
-    rows_cap = max(1024, C.conv_stats_rows(N * H * W, 64, 0))
+    rows_cap = max(1024, C.conv_stats_rows(N * H * W, 64, C.CONV_AUTO))
     st_ref, st = (torch.zeros(rows_cap * 2 * 64, device=dev) for _ in range(2))
-    rows_ref = C.conv_fwd(a, None, wk, 9, 0, y_ref, None, st_ref, 6, None, 0)  # ring kernel on a
+    rows_ref = C.conv_fwd(a, None, wk, 9, 0, y_ref, None, st_ref, C.CONV_RING, None, 0)  # ring kernel on a
     rows = C.conv_fwd_bnin(y_pre, wk, y_out, st, coef)
     torch.cuda.synchronize()
     assert rows == rows_ref > 0
@@ -608,7 +608,7 @@ def test_conv_transpose2x2(C, N, h, w, Cin, Cout, H2, W2):
     ref = F.pad(y, [ox, W2 - 2 * w - ox, oy, H2 - 2 * h - oy])
     wphys = W.permute(0, 2, 3, 1).reshape(Cin, 4 * Cout).contiguous()  # [ci][(dh, dw, co)]
     yT = torch.empty(N, h, w, 4 * Cout, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(nhwc(x), None, wphys.t().contiguous(), 1, 0, yT, None, None, 0, None, 0)
+    C.conv_fwd(nhwc(x), None, wphys.t().contiguous(), 1, 0, yT, None, None, C.CONV_AUTO, None, 0)
     u = torch.full((N, H2, W2, Cout), float("nan"), dtype=torch.bfloat16, device=dev)
     C.upT_shuffle(yT, b, u, oy, ox)
     assert relerr(nchw(u), ref) < 1e-2
@@ -627,7 +627,7 @@ def test_conv_transpose2x2(C, N, h, w, Cin, Cout, H2, W2):
     C.conv_wgrad(dyT, None, nhwc(x), 1, 0, 4 * Cout, slab, gw, 0, splits, 0)
     assert relerr(gw.view(Cin, 2, 2, Cout).permute(0, 3, 1, 2), Wr.grad) < 1e-2
     dx = torch.empty(N, h, w, Cin, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(dyT, None, wphys, 1, 0, dx, None, None, 0, None, 0)
+    C.conv_fwd(dyT, None, wphys, 1, 0, dx, None, None, C.CONV_AUTO, None, 0)
     assert relerr(nchw(dx), xr.grad) < 1e-2
 
 
@@ -649,7 +649,7 @@ def test_conv_upT_fwd_fused(C, N, h, w, Cin, Cout, H2, W2):
     torch.cuda.synchronize()
     assert relerr(nchw(u), ref) < 1e-2
     yT = torch.empty(N, h, w, 4 * Cout, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(nhwc(x), None, wt, 1, 0, yT, None, None, 0, None, 0)
+    C.conv_fwd(nhwc(x), None, wt, 1, 0, yT, None, None, C.CONV_AUTO, None, 0)
     u2 = torch.zeros_like(u)
     C.upT_shuffle(yT, b, u2, oy, ox)
     # one rounding of (acc + bias): within half a bf16 ulp of the fp32 result everywhere (the unfused path
@@ -688,7 +688,7 @@ def test_conv_upT_backward_in_place(C, N, h, w, Cin, Cout):
     dyT = torch.empty(N, h, w, 4 * Cout, dtype=torch.bfloat16, device=dev)
     C.upT_unshuffle(dun, dyT, 0, 0)
     dx2 = torch.empty_like(dx)
-    C.conv_fwd(dyT, None, wd, 1, 0, dx2, None, None, 4 if Cin % 256 == 0 and tiles >= 512 else 5, None, 0)
+    C.conv_fwd(dyT, None, wd, 1, 0, dx2, None, None, C.CONV_PP256 if Cin % 256 == 0 and tiles >= 512 else C.CONV_PP128, None, 0)
     if r == 0:
         assert relerr(nchw(dx), xr.grad) < 1e-2
         assert torch.equal(dx, dx2)  # same kernel, same K order: only the A operand's addresses differ
@@ -723,20 +723,20 @@ def _splitk_case(C, N, H, W, C1, C2, Cout):
     x2 = bf(torch.randn(N, H, W, C2, device=dev)) if C2 else None
     w = bf(torch.randn(Cout, C1 + C2, 3, 3, device=dev) / math.sqrt(9 * (C1 + C2)))
     wk = ohwi(w).contiguous()
-    n_ws = C.conv_ws_elems(N, H, W, C1, C2, Cout, 9, 0, 0)
+    n_ws = C.conv_ws_elems(N, H, W, C1, C2, Cout, 9, 0, C.CONV_AUTO)
     assert n_ws > 0, "shape should take the split-K path"
     ws = torch.zeros(n_ws, device=dev)
     xin = nchw(x1).float() if x2 is None else torch.cat([nchw(x1), nchw(x2)], 1).float()
     ref = F.conv2d(xin, w.float(), padding=1)
-    rows = C.conv_stats_rows(N * H * W, Cout, 0)
+    rows = C.conv_stats_rows(N * H * W, Cout, C.CONV_AUTO)
     stats = torch.zeros(rows * 2 * Cout, device=dev)
     y = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
-    r = C.conv_fwd(x1, x2, wk, 9, 0, y, None, stats, 0, None, 0, ws)
+    r = C.conv_fwd(x1, x2, wk, 9, 0, y, None, stats, C.CONV_AUTO, None, 0, ws)
     assert 0 < r <= rows
     assert relerr(nchw(y), ref) < 1e-2
     assert torch.count_nonzero(ws[:256]) == 0  # split-K arrival counters are reset by the last arriver
     yb = torch.empty_like(y)
-    C.conv_fwd(x1, x2, wk, 9, 0, yb, None, None, 0, None, 0, ws)
+    C.conv_fwd(x1, x2, wk, 9, 0, yb, None, None, C.CONV_AUTO, None, 0, ws)
     assert torch.equal(yb, y)  # slices summed in split order whichever arrives last
     yq = nchw(y).float()
     s = stats.view(rows, 2, Cout)[:r].sum(0)
@@ -748,12 +748,12 @@ def _splitk_case(C, N, H, W, C1, C2, Cout):
     coef = torch.zeros(4 * Cout, device=dev)
     C.bn_eval_coef(g, b, rm, rv, 1e-5, coef)
     a = torch.empty_like(y)
-    C.conv_fwd(x1, x2, wk, 9, 0, a, None, None, 0, coef, 1, ws)
+    C.conv_fwd(x1, x2, wk, 9, 0, a, None, None, C.CONV_AUTO, coef, 1, ws)
     assert relerr(nchw(a), F.relu(F.batch_norm(ref, rm, rv, g, b, False, 0.0, 1e-5))) < 1e-2
     # split destinations
     y1 = torch.empty(N, H, W, Cout // 2, dtype=torch.bfloat16, device=dev)
     y2 = torch.empty(N, H, W, Cout // 2, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x1, x2, wk, 9, 0, y1, y2, None, 0, None, 0, ws)
+    C.conv_fwd(x1, x2, wk, 9, 0, y1, y2, None, C.CONV_AUTO, None, 0, ws)
     assert relerr(torch.cat([nchw(y1), nchw(y2)], 1), ref) < 1e-2
 
 
@@ -773,7 +773,7 @@ def test_conv_eval_fused_pool(C, N, H, W, C1, C2, Cout):
     x2 = bf(torch.randn(N, H, W, C2, device=dev)) if C2 else None
     w = bf(torch.randn(Cout, C1 + C2, 3, 3, device=dev) / math.sqrt(9 * (C1 + C2)))
     wk = ohwi(w).contiguous()
-    n_ws = C.conv_ws_elems(N, H, W, C1, C2, Cout, 9, 0, 0)
+    n_ws = C.conv_ws_elems(N, H, W, C1, C2, Cout, 9, 0, C.CONV_AUTO)
     ws = torch.zeros(n_ws, device=dev) if n_ws else None
     g, b = torch.rand(Cout, device=dev) + 0.5, torch.randn(Cout, device=dev)
     rm, rv = torch.randn(Cout, device=dev) * 0.1, torch.rand(Cout, device=dev) + 0.5
@@ -781,9 +781,9 @@ def test_conv_eval_fused_pool(C, N, H, W, C1, C2, Cout):
     C.bn_eval_coef(g, b, rm, rv, 1e-5, coef)
     a = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
     p = torch.full((N, H // 2, W // 2, Cout), float("nan"), dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x1, x2, wk, 9, 0, a, None, None, 0, coef, 1, ws, p)
+    C.conv_fwd(x1, x2, wk, 9, 0, a, None, None, C.CONV_AUTO, coef, 1, ws, p)
     a2 = torch.empty_like(a)
-    C.conv_fwd(x1, x2, wk, 9, 0, a2, None, None, 0, coef, 1, ws)
+    C.conv_fwd(x1, x2, wk, 9, 0, a2, None, None, C.CONV_AUTO, coef, 1, ws)
     assert torch.equal(a, a2)
     assert torch.equal(p, F.max_pool2d(nchw(a).float(), 2).to(torch.bfloat16).permute(0, 2, 3, 1))
     xin = nchw(x1).float() if x2 is None else torch.cat([nchw(x1), nchw(x2)], 1).float()
@@ -805,7 +805,7 @@ def test_conv_eval_fused_upsample(C, N, H, W, C1, C2, Cout, pad):
     x2 = bf(torch.randn(N, H, W, C2, device=dev)) if C2 else None
     w = bf(torch.randn(Cout, C1 + C2, 3, 3, device=dev) / math.sqrt(9 * (C1 + C2)))
     wk = ohwi(w).contiguous()
-    n_ws = C.conv_ws_elems(N, H, W, C1, C2, Cout, 9, 0, 0)
+    n_ws = C.conv_ws_elems(N, H, W, C1, C2, Cout, 9, 0, C.CONV_AUTO)
     assert n_ws > 0
     ws = torch.zeros(n_ws, device=dev)
     g, b = torch.rand(Cout, device=dev) + 0.5, torch.randn(Cout, device=dev)
@@ -815,9 +815,9 @@ def test_conv_eval_fused_upsample(C, N, H, W, C1, C2, Cout, pad):
     Hu, Wu = 2 * H + 2 * pad, 2 * W + 2 * pad
     a = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
     u = torch.full((N, Hu, Wu, Cout), float("nan"), dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x1, x2, wk, 9, 0, a, None, None, 0, coef, 1, ws, None, u, pad, pad)
+    C.conv_fwd(x1, x2, wk, 9, 0, a, None, None, C.CONV_AUTO, coef, 1, ws, None, u, pad, pad)
     a2 = torch.empty_like(a)
-    C.conv_fwd(x1, x2, wk, 9, 0, a2, None, None, 0, coef, 1, ws)
+    C.conv_fwd(x1, x2, wk, 9, 0, a2, None, None, C.CONV_AUTO, coef, 1, ws)
     assert torch.equal(a, a2)
     u2 = torch.full_like(u, float("nan"))
     C.upsample2_fwd(a2, u2, pad, pad)
@@ -845,7 +845,7 @@ def test_conv_head_mask_fused(C, N, H, W):
     hw = torch.randn(64, device=dev) * 0.3
     hb = torch.randn(1, device=dev) * 0.1
     a = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x, None, wk, 9, 0, a, None, None, 0, coef, 1)
+    C.conv_fwd(x, None, wk, 9, 0, a, None, None, C.CONV_AUTO, coef, 1)
     ref = torch.full((N * H * W,), 7, dtype=torch.uint8, device=dev)
     C.head_mask(a, hw, hb, 0.0, ref)
     got = torch.full((N * H * W,), 7, dtype=torch.uint8, device=dev)
@@ -892,15 +892,15 @@ def test_conv_tiles_and_split_reduce(C, N, H, W, C1, C2, Cout, pref):
 
 @pytest.mark.parametrize("N,H,W,C1,C2,Cout", [(2, 16, 16, 128, 0, 128), (1, 9, 13, 64, 64, 256)])
 def test_conv_fwd_8wave_variant(C, N, H, W, C1, C2, Cout):
-    """bm_pref=2: 128x128 tiles with 8 waves (64x32 per wave) == the 4-wave kernel's result."""
+    """CONV_IGEMM8_128: 128x128 tiles with 8 waves (64x32 per wave) == the 4-wave kernel's result."""
     torch.manual_seed(7)
     dev = "cuda"
     x1 = bf(torch.randn(N, H, W, C1, device=dev))
     x2 = bf(torch.randn(N, H, W, C2, device=dev)) if C2 else None
     w = bf(torch.randn(Cout, C1 + C2, 3, 3, device=dev) / math.sqrt(9 * (C1 + C2)))
-    rows = C.conv_stats_rows(N * H * W, Cout, 0)
+    rows = C.conv_stats_rows(N * H * W, Cout, C.CONV_AUTO)
     outs = []
-    for pref in (128, 2):
+    for pref in (C.CONV_IGEMM4_128, C.CONV_IGEMM8_128):
         y = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
         st = torch.zeros(rows * 2 * Cout, device=dev)
         r = C.conv_fwd(x1, x2, ohwi(w).contiguous(), 9, 0, y, None, st, pref, None, 0)
@@ -913,13 +913,13 @@ def test_conv_fwd_8wave_variant(C, N, H, W, C1, C2, Cout):
                                                   (16, 64, 64, 64, 256, 0)])
 def test_conv_pingpong_1x1(C, N, H, W, Cin, Cout, pref):
     """The ping-pong kernel on 1x1 GEMMs (the transposed decoder's ConvTranspose2d as taps=1, dgrad of
-    it too): bitwise equal to the 128 x 128 kernel; pref 0 = auto (>= 256 tiles of 256 x 256)."""
+    it too): bitwise equal to the 128 x 128 kernel; CONV_AUTO picks it from >= 256 tiles of 256 x 256)."""
     torch.manual_seed(12)
     dev = "cuda"
     x = bf(torch.randn(N, H, W, Cin, device=dev))
     w = bf(torch.randn(Cout, Cin, device=dev) / math.sqrt(Cin))
     ys = []
-    for p in (128, pref):
+    for p in (C.CONV_IGEMM4_128, pref):
         y = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
         C.conv_fwd(x, None, w, 1, 0, y, None, None, p, None, 0)
         ys.append(y)
@@ -933,7 +933,7 @@ def test_conv_pingpong_1x1(C, N, H, W, Cin, Cout, pref):
     (1, 24, 40, 128, 128, 256, 5), (20, 64, 64, 64, 0, 128, 5), (5, 64, 64, 256, 0, 512, 4),
     (2, 16, 16, 512, 512, 1024, 4), (9, 32, 32, 64, 64, 128, 5)])
 def test_conv_pingpong_bitwise(C, N, H, W, C1, C2, Cout, pref):
-    """bm_pref 4 / 5: the ping-pong 256 x 256 / 256 x 128 kernel (one 8-wave block per CU, staggered
+    """CONV_PP256 / CONV_PP128: the ping-pong 256 x 256 / 256 x 128 kernel (one 8-wave block per CU, staggered
     wave groups, 2-3 stage ring) accumulates in the same K order as the 128 x 128 kernel: outputs
     bitwise equal, BN partial sums equal to rounding; covers persistent blocks walking several tiles
     (320 / 640 tiles), a ragged last tile (M = 3219), the concat input and 1024 couts."""
@@ -943,9 +943,9 @@ def test_conv_pingpong_bitwise(C, N, H, W, C1, C2, Cout, pref):
     x2 = bf(torch.randn(N, H, W, C2, device=dev)) if C2 else None
     w = bf(torch.randn(Cout, C1 + C2, 3, 3, device=dev) / math.sqrt(9 * (C1 + C2)))
     wk = ohwi(w).contiguous()
-    rows = C.conv_stats_rows(N * H * W, Cout, 0)
+    rows = C.conv_stats_rows(N * H * W, Cout, C.CONV_AUTO)
     outs = []
-    prefs = (128, pref)
+    prefs = (C.CONV_IGEMM4_128, pref)
     for p in prefs:
         y = torch.full((N, H, W, Cout), 7.0, dtype=torch.bfloat16, device=dev)
         st = torch.zeros(rows * 2 * Cout, device=dev)
@@ -965,7 +965,7 @@ def test_conv_pingpong_bitwise(C, N, H, W, C1, C2, Cout, pref):
         dy = bf(torch.randn(N, H, W, Cout, device=dev))
         wt = bf(torch.randn(C1 + C2, Cout * 9, device=dev) / math.sqrt(9 * Cout))
         e1, e2 = torch.empty_like(d1), torch.empty_like(d2)
-        C.conv_fwd(dy, None, wt, 9, 0, e1, e2, None, 128, None, 0)
+        C.conv_fwd(dy, None, wt, 9, 0, e1, e2, None, C.CONV_IGEMM4_128, None, 0)
         for p in prefs[1:]:
             d1.zero_()
             d2.zero_()
@@ -978,7 +978,7 @@ def test_conv_pingpong_bitwise(C, N, H, W, C1, C2, Cout, pref):
     (4, 32, 32, 512, 0, 512, 8), (4, 32, 32, 256, 0, 512, 0), (5, 37, 29, 256, 0, 512, 7),
     (4, 32, 32, 512, 0, 256, 0)])
 def test_conv_pingpong_splitk(C, N, H, W, C1, C2, Cout, pref):
-    """bm_pref 7 / 8 (and auto at the reference batch): the ping-pong kernel with K split over work
+    """CONV_PPSK128 / CONV_PPSK256 (and auto at the reference batch): the ping-pong kernel with K split over work
     items (fp32 partial tiles + conv_splitk_reduce_kernel) vs fp32 torch: output, BN partial sums, a
     ragged last tile (M = 5365), the concat input, split destinations (dgrad) and the eval BN fold;
     two launches bitwise equal."""
@@ -1010,7 +1010,7 @@ def test_conv_pingpong_splitk(C, N, H, W, C1, C2, Cout, pref):
     # split destinations (the dgrad of a concat input)
     y1 = torch.empty(N, H, W, Cout // 2, dtype=torch.bfloat16, device=dev)
     y2 = torch.empty(N, H, W, Cout // 2, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x1, x2, wk, 9, 0, y1, y2, None, pref if pref else 7, None, 0, ws)
+    C.conv_fwd(x1, x2, wk, 9, 0, y1, y2, None, pref or C.CONV_PPSK128, None, 0, ws)
     assert torch.equal(torch.cat([y1, y2], 3), y)
     # eval BN fold + ReLU through the same reduce
     if pref:
@@ -1026,16 +1026,16 @@ def test_conv_pingpong_splitk(C, N, H, W, C1, C2, Cout, pref):
 @pytest.mark.parametrize("N,H,W", [(2, 6, 64), (1, 4, 128), (3, 2, 192), (1, 10, 64)])
 def test_conv_ring_fwd_stats_eval_dgrad(C, N, H, W):
     """Row-ring kernel (64 -> 64, W % 64 == 0): forward + BN stats, eval BN fold + ReLU, and the
-    dgrad use (conv of dy with the flipped transposed weight) against torch fp32; forced (pref 6)
+    dgrad use (conv of dy with the flipped transposed weight) against torch fp32; forced (CONV_RING)
     and via the auto dispatch, which must pick it and agree bitwise."""
     torch.manual_seed(11)
     dev = "cuda"
     x = bf(torch.randn(N, H, W, 64, device=dev))
     w = bf(torch.randn(64, 64, 3, 3, device=dev) / 24)
     ref = F.conv2d(nchw(x).float(), w.float(), padding=1)
-    rows = C.conv_stats_rows(N * H * W, 64, 0)
+    rows = C.conv_stats_rows(N * H * W, 64, C.CONV_AUTO)
     outs = []
-    for pref in (6, 0):
+    for pref in (C.CONV_RING, C.CONV_AUTO):
         y = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
         stats = torch.zeros(rows * 2 * 64, device=dev)
         r = C.conv_fwd(x, None, ohwi(w).contiguous(), 9, 0, y, None, stats, pref, None, 0)
@@ -1051,7 +1051,7 @@ def test_conv_ring_fwd_stats_eval_dgrad(C, N, H, W):
     sc, sh = torch.rand(64, device=dev) + 0.5, torch.randn(64, device=dev) * 0.1
     aff = torch.cat([torch.zeros(64, device=dev), torch.ones(64, device=dev), sc, sh])
     ye = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x, None, ohwi(w).contiguous(), 9, 0, ye, None, None, 6, aff, 1)
+    C.conv_fwd(x, None, ohwi(w).contiguous(), 9, 0, ye, None, None, C.CONV_RING, aff, 1)
     refe = torch.relu(ref * sc[None, :, None, None] + sh[None, :, None, None])
     assert relerr(nchw(ye), refe) < 1e-2
     # dgrad: dX = conv(dY, flip(W)^T)
@@ -1060,7 +1060,7 @@ def test_conv_ring_fwd_stats_eval_dgrad(C, N, H, W):
     F.conv2d(xr, w.float(), padding=1).backward(nchw(dy).float())
     wt = w.flip(2, 3).permute(1, 2, 3, 0).reshape(64, 9 * 64).contiguous()
     dx = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(dy, None, wt, 9, 0, dx, None, None, 6, None, 0)
+    C.conv_fwd(dy, None, wt, 9, 0, dx, None, None, C.CONV_RING, None, 0)
     assert relerr(nchw(dx), xr.grad) < 1e-2
 
 
@@ -1069,7 +1069,7 @@ def test_conv_ring_fwd_stats_eval_dgrad(C, N, H, W):
 def test_conv_ring2_128_to_64(C, N, H, W, form):
     """Two-source row ring (128 -> 64, K split over wave pairs that meet in LDS): up4 conv0 on the concat
     [skip, up] (two 64-channel sources) and up3 conv1 on one 128-channel tensor (its two halves), forward +
-    BN partial sums and eval BN fold + ReLU, against torch fp32; forced (pref 14) == auto dispatch where
+    BN partial sums and eval BN fold + ReLU, against torch fp32; forced (CONV_RING2) == auto dispatch where
     the grid fills the chip (>= 256 row pairs) bitwise."""
     torch.manual_seed(13)
     dev = "cuda"
@@ -1082,10 +1082,10 @@ def test_conv_ring2_128_to_64(C, N, H, W, form):
     w = bf(torch.randn(64, 128, 3, 3, device=dev) / 34)
     wk = ohwi(w).contiguous()
     ref = F.conv2d(nchw(xin).float(), w.float(), padding=1)
-    rows = C.conv_stats_rows(N * H * W, 64, 0)
+    rows = C.conv_stats_rows(N * H * W, 64, C.CONV_AUTO)
     auto = N * (W // 64) * H // 2 >= 256
     outs = []
-    for pref in ((14, 0) if auto else (14,)):
+    for pref in ((C.CONV_RING2, C.CONV_AUTO) if auto else (C.CONV_RING2,)):
         y = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
         stats = torch.zeros(rows * 2 * 64, device=dev)
         r = C.conv_fwd(x1, x2, wk, 9, 0, y, None, stats, pref, None, 0)
@@ -1100,19 +1100,19 @@ def test_conv_ring2_128_to_64(C, N, H, W, form):
         assert torch.equal(outs[0], outs[1])
     # the implicit GEMM (256 x 64 tile) computes the same conv: equal up to fp32 summation order
     yi = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x1, x2, wk, 9, 0, yi, None, torch.zeros(rows * 2 * 64, device=dev), 256, None, 0)
+    C.conv_fwd(x1, x2, wk, 9, 0, yi, None, torch.zeros(rows * 2 * 64, device=dev), C.CONV_IGEMM4_256, None, 0)
     assert relerr(nchw(outs[0]), nchw(yi).float()) < 1e-2
     # eval: BN fold + ReLU in the epilogue
     sc, sh = torch.rand(64, device=dev) + 0.5, torch.randn(64, device=dev) * 0.1
     aff = torch.cat([torch.zeros(64, device=dev), torch.ones(64, device=dev), sc, sh])
     ye = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x1, x2, wk, 9, 0, ye, None, None, 14, aff, 1)
+    C.conv_fwd(x1, x2, wk, 9, 0, ye, None, None, C.CONV_RING2, aff, 1)
     assert relerr(nchw(ye), torch.relu(ref * sc[None, :, None, None] + sh[None, :, None, None])) < 1e-2
 
 
 @pytest.mark.parametrize("N,H,W,form", [(2, 8, 128, "one"), (1, 6, 64, "concat")])
 def test_conv_ring2_128_to_128_halves(C, N, H, W, form):
-    """128 -> 128 as two two-source-ring launches over the output-channel halves (bm_pref 15): output,
+    """128 -> 128 as two two-source-ring launches over the output-channel halves (CONV_RING2X2): output,
     BN partial rows ([rows][2][128], each launch filling its 64 columns) and the eval epilogue vs torch
     fp32; each half bitwise equal to the 128 -> 64 ring on that half's weights."""
     torch.manual_seed(17)
@@ -1126,10 +1126,10 @@ def test_conv_ring2_128_to_128_halves(C, N, H, W, form):
     w = bf(torch.randn(128, 128, 3, 3, device=dev) / 34)
     wk = ohwi(w).contiguous()
     ref = F.conv2d(nchw(xin).float(), w.float(), padding=1)
-    rows = C.conv_stats_rows(N * H * W, 128, 0)
+    rows = C.conv_stats_rows(N * H * W, 128, C.CONV_AUTO)
     y = torch.empty(N, H, W, 128, dtype=torch.bfloat16, device=dev)
     stats = torch.zeros(rows * 2 * 128, device=dev)
-    r = C.conv_fwd(x1, x2, wk, 9, 0, y, None, stats, 15, None, 0)
+    r = C.conv_fwd(x1, x2, wk, 9, 0, y, None, stats, C.CONV_RING2X2, None, 0)
     assert 0 < r <= rows
     assert relerr(nchw(y), ref) < 1e-2
     yq = nchw(y).float()
@@ -1138,12 +1138,12 @@ def test_conv_ring2_128_to_128_halves(C, N, H, W, form):
     assert torch.allclose(st[1], (yq * yq).sum((0, 2, 3)), rtol=1e-3, atol=1e-2)
     for h in range(2):
         yh = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
-        C.conv_fwd(x1, x2, wk[64 * h:64 * h + 64].contiguous(), 9, 0, yh, None, None, 14, None, 0)
+        C.conv_fwd(x1, x2, wk[64 * h:64 * h + 64].contiguous(), 9, 0, yh, None, None, C.CONV_RING2, None, 0)
         assert torch.equal(yh, y[..., 64 * h:64 * h + 64])
     sc, sh = torch.rand(128, device=dev) + 0.5, torch.randn(128, device=dev) * 0.1
     aff = torch.cat([torch.zeros(128, device=dev), torch.ones(128, device=dev), sc, sh])
     ye = torch.empty(N, H, W, 128, dtype=torch.bfloat16, device=dev)
-    C.conv_fwd(x1, x2, wk, 9, 0, ye, None, None, 15, aff, 1)
+    C.conv_fwd(x1, x2, wk, 9, 0, ye, None, None, C.CONV_RING2X2, aff, 1)
     assert relerr(nchw(ye), torch.relu(ref * sc[None, :, None, None] + sh[None, :, None, None])) < 1e-2
 
 
@@ -1156,9 +1156,9 @@ def test_conv_ring_cout128(C, N, H, W, split):
     x = bf(torch.randn(N, H, W, 64, device=dev))
     w = bf(torch.randn(128, 64, 3, 3, device=dev) / 24)
     ref = F.conv2d(nchw(x).float(), w.float(), padding=1)
-    rows = C.conv_stats_rows(N * H * W, 128, 0)
+    rows = C.conv_stats_rows(N * H * W, 128, C.CONV_AUTO)
     outs = []
-    for pref in (6, 0):
+    for pref in (C.CONV_RING, C.CONV_AUTO):
         stats = torch.zeros(rows * 2 * 128, device=dev)
         if split:
             y1 = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
@@ -1266,7 +1266,7 @@ def test_dgrad_splitk_bnred_matches_separate_reduce(C, N, H, Cdy, Cdx):
     gamma, beta = torch.randn(Cdx, device=dev), torch.randn(Cdx, device=dev) * 0.2
     ss = gamma * inv
     coef = torch.cat([mean, inv, ss, beta - mean * ss]).contiguous()
-    n_ws = C.conv_ws_elems(N, H, H, Cdy, 0, Cdx, 9, 0, 0)
+    n_ws = C.conv_ws_elems(N, H, H, Cdy, 0, Cdx, 9, 0, C.CONV_AUTO)
     assert n_ws > 0  # these shapes run split-K
     ws = torch.zeros(n_ws, device=dev)
     dx = torch.empty(N, H, H, Cdx, dtype=torch.bfloat16, device=dev)
@@ -1274,7 +1274,7 @@ def test_dgrad_splitk_bnred_matches_separate_reduce(C, N, H, Cdy, Cdx):
     T = C.conv_dgrad_splitk_bnred(dy, w, dx, y, coef, part, ws)
     assert T > 0
     dx_ref = torch.empty_like(dx)
-    C.conv_fwd(dy, None, w, 9, 0, dx_ref, None, None, 0, None, 0, ws)
+    C.conv_fwd(dy, None, w, 9, 0, dx_ref, None, None, C.CONV_AUTO, None, 0, ws)
     assert torch.equal(dx, dx_ref)
     part_ref = torch.zeros(1024 * 2 * Cdx, device=dev)
     T_ref = C.bn_relu_bwd_reduce(dx_ref, y, coef, 1, part_ref)
@@ -1382,9 +1382,9 @@ N, H, W = 5, 64, 64
 x1 = bf(torch.randn(N, H, W, 64, device=dev)); x2 = bf(torch.randn(N, H, W, 64, device=dev))
 w = bf(torch.randn(128, 9 * 128, device=dev) / 34.0)
 y = torch.empty(N, H, W, 128, dtype=torch.bfloat16, device=dev)
-rows = 8 * C.conv_stats_rows(N * H * W, 128, 0)  # 5 chunked launches: 5 x the per-launch floor
+rows = 8 * C.conv_stats_rows(N * H * W, 128, C.CONV_AUTO)  # 5 chunked launches: 5 x the per-launch floor
 st = torch.zeros(rows * 2 * 128, device=dev)
-r = C.conv_fwd(x1, x2, w, 9, 0, y, None, st, 0, None, 0)
+r = C.conv_fwd(x1, x2, w, 9, 0, y, None, st, C.CONV_AUTO, None, 0)
 dy = bf(torch.randn(N, H, W, 128, device=dev))
 slab = torch.zeros(C.wgrad_slab_elems(N, H, W, 128, 128, 9, 0, 64), device=dev)
 out = torch.zeros(128 * 9 * 128, device=dev)
@@ -1411,8 +1411,8 @@ torch.save({"y": y.cpu(), "s": st[: r * 256].view(r, 2, 128).sum(0).cpu(), "g": 
     (1, 64, 64, 128, 0, 256, False), (1, 64, 64, 256, 0, 256, True), (2, 16, 16, 256, 256, 128, True),
     (1, 64, 64, 256, 256, 256, False), (3, 16, 32, 64, 64, 96, False)])
 def test_conv_rowband_eval(C, N, H, W, C1, C2, Cout, pool):
-    """Row-band eval conv (bm_pref 16; auto on small maps): BN fold + ReLU, concat input, fused
-    MaxPool2d(2) -- vs fp32 torch, vs the split-K implicit GEMM (bm_pref 128) at bf16 rounding, and the
+    """Row-band eval conv (CONV_ROWBAND; auto on small maps): BN fold + ReLU, concat input, fused
+    MaxPool2d(2) -- vs fp32 torch, vs the split-K implicit GEMM (CONV_IGEMM4_128) at bf16 rounding, and the
     pool bitwise the 2x2 max of the output."""
     torch.manual_seed(12)
     dev = "cuda"
@@ -1426,23 +1426,23 @@ def test_conv_rowband_eval(C, N, H, W, C1, C2, Cout, pool):
     C.bn_eval_coef(g, b, rm, rv, 1e-5, coef)
     a = torch.full((N, H, W, Cout), float("nan"), dtype=torch.bfloat16, device=dev)
     p = torch.full((N, H // 2, W // 2, Cout), float("nan"), dtype=torch.bfloat16, device=dev) if pool else None
-    C.conv_fwd(x1, x2, wk, 9, 0, a, None, None, 16, coef, 1, None, p)
+    C.conv_fwd(x1, x2, wk, 9, 0, a, None, None, C.CONV_ROWBAND, coef, 1, None, p)
     xin = nchw(x1).float() if x2 is None else torch.cat([nchw(x1), nchw(x2)], 1).float()
     ref = F.relu(F.batch_norm(F.conv2d(xin, w.float(), padding=1), rm, rv, g, b, False, 0.0, 1e-5))
     assert not torch.isnan(a.float()).any()
     assert relerr(nchw(a), ref) < 1e-2
     if Cout % 128 == 0:
-        n_ws = C.conv_ws_elems(N, H, W, C1, C2, Cout, 9, 0, 128)
+        n_ws = C.conv_ws_elems(N, H, W, C1, C2, Cout, 9, 0, C.CONV_IGEMM4_128)
         ws = torch.zeros(max(n_ws, 1), device=dev)
         a2 = torch.empty_like(a)
-        C.conv_fwd(x1, x2, wk, 9, 0, a2, None, None, 128, coef, 1, ws)
+        C.conv_fwd(x1, x2, wk, 9, 0, a2, None, None, C.CONV_IGEMM4_128, coef, 1, ws)
         d = (a.float() - a2.float()).abs()
         assert (d <= 2 ** -6 * a2.float().abs() + 1e-2).all(), d.max()
     if pool:
         assert torch.equal(p, F.max_pool2d(nchw(a).float(), 2).to(torch.bfloat16).permute(0, 2, 3, 1))
     # deterministic: a second launch is bitwise identical
     a3 = torch.empty_like(a)
-    C.conv_fwd(x1, x2, wk, 9, 0, a3, None, None, 16, coef, 1)
+    C.conv_fwd(x1, x2, wk, 9, 0, a3, None, None, C.CONV_ROWBAND, coef, 1)
     assert torch.equal(a, a3)
 
 
@@ -1467,7 +1467,7 @@ def test_conv_rowband_chain(C, N, nl):
         refs.append(torch.empty(N, H, H, co, dtype=torch.bfloat16, device=dev))
     inp = x
     for w, r, cf in zip(ws, refs, coefs):
-        C.conv_fwd(inp, None, w, 9, 0, r, None, None, 16, cf, 1)
+        C.conv_fwd(inp, None, w, 9, 0, r, None, None, C.CONV_ROWBAND, cf, 1)
         inp = r
     cnt = torch.full((1 + nl * N * H,), 7, dtype=torch.int32, device=dev)  # poisoned: the launch zeroes it
     err = torch.zeros(1, dtype=torch.int32, device=dev)

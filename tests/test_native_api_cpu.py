@@ -1,4 +1,5 @@
-"""The native entry points (``rdp_*``, C linkage) are declared once, in csrc/rdp_api.h and csrc/rdp_host_api.h.
+"""The native entry points (``rdp_*``) are declared once: in csrc/rdp_api.h and csrc/rdp_host_api.h (C linkage) and,
+for the conv plan that rdp_api.h includes, in csrc/conv_plan.h.
 
 With C linkage neither compiler nor linker compares a hand-copied prototype with its definition, so a copy that
 drifts still links and shifts every argument after the change. The headers make the compiler compare -- as long as
@@ -9,7 +10,7 @@ import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADERS = ("rdp_api.h", "rdp_host_api.h")
+HEADERS = ("rdp_api.h", "rdp_host_api.h", "conv_plan.h")
 # `<type> rdp_name(` with nothing but type tokens before the name on its line: a declaration or a definition
 HEAD = re.compile(r'^[ \t]*(?:extern "C" )?((?:[\w:]+[ \t\*&]+)+)(rdp_\w+)[ \t]*\(', re.M)
 
@@ -43,7 +44,7 @@ def test_headers_declare_the_entry_points():
 def test_no_prototype_outside_the_two_headers():
     copies = [(os.path.relpath(p, ROOT), name) for p in _sources() for name, kind in _entries(open(p).read())
               if kind == ";"]
-    assert not copies, f"hand-written rdp_* prototypes (declare them in csrc/rdp_api.h / rdp_host_api.h): {copies}"
+    assert not copies, f"hand-written rdp_* prototypes (declare them in csrc/rdp_api.h / rdp_host_api.h / conv_plan.h): {copies}"
 
 
 def test_every_definer_includes_a_header():

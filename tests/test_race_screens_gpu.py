@@ -26,12 +26,12 @@ def _bf(shape, dev="cuda"):
 
 @pytest.mark.parametrize("N,H,W,C1,C2,Cout,pref", [
     (4, 64, 64, 64, 0, 64, 0), (2, 33, 17, 128, 64, 128, 0), (8, 16, 16, 256, 256, 256, 0),
-    (2, 32, 64, 128, 128, 64, 1), (4, 16, 16, 64, 0, 128, 1), (3, 7, 9, 64, 0, 64, 128)])
+    (2, 32, 64, 128, 128, 64, 1), (4, 16, 16, 64, 0, 128, 1), (3, 7, 9, 64, 0, 64, 3)])
 def test_conv_fwd_stats_deterministic(C, N, H, W, C1, C2, Cout, pref):
     torch.manual_seed(0)
     x1, x2 = _bf((N, H, W, C1)), (_bf((N, H, W, C2)) if C2 else None)
     w = (torch.randn(Cout, 9 * (C1 + C2), device="cuda") / math.sqrt(9 * (C1 + C2))).to(torch.bfloat16)
-    rows = C.conv_stats_rows(N * H * W, Cout, 0)
+    rows = C.conv_stats_rows(N * H * W, Cout, C.CONV_AUTO)
     outs = []
     for _ in range(REPS):
         y = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device="cuda")

@@ -34,7 +34,7 @@ def test_conv_eval_bn_fold_epilogue(C, N, H, W, C1, C2, Cout):
     coef = torch.zeros(4 * Cout, device=dev)
     C.bn_eval_coef(g, b, rm, rv, 1e-5, coef)
     a = torch.empty(N, H, W, Cout, dtype=bf, device=dev)
-    C.conv_fwd(x1, x2, w.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous(), 9, 0, a, None, None, 0, coef, 1)
+    C.conv_fwd(x1, x2, w.permute(0, 2, 3, 1).reshape(Cout, -1).contiguous(), 9, 0, a, None, None, C.CONV_AUTO, coef, 1)
     xin = torch.cat([x1, x2], -1) if C2 else x1
     y = F.conv2d(xin.permute(0, 3, 1, 2).float(), w.float(), padding=1)
     ref = F.relu(F.batch_norm(y, rm, rv, g, b, False, 0.0, 1e-5)).permute(0, 2, 3, 1)
