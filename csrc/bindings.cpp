@@ -620,31 +620,43 @@ int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w,
 }
 
 
+// The sources and dy of a weight-gradient operand block = images [n0, n0 + nn) of the tensors (an undefined Act
+// leaves its slot empty); x1 sets N / H / W, dy the output channels
+void wgrad_bind(RdpWgrad& g, const Act& x1, const Act& x2, const Act& dy, int n0, int nn) {
+  g.x1 = x1.image(n0); g.xbytes1 = x1.span_bytes(nn); g.C1 = x1.C; g.pitch1 = x1.pitch;
+  if (x2.ptr) { g.x2 = x2.image(n0); g.xbytes2 = x2.span_bytes(nn); g.C2 = x2.C; g.pitch2 = x2.pitch; }
+  if (dy.ptr) { g.dy = dy.image(n0); g.dybytes = dy.span_bytes(nn); g.dypitch = dy.pitch; g.Cout = dy.C; }
+  g.N = nn; g.H = x1.H; g.W = x1.W;
+}
+
+// the fp32 slab and the gradient a weight-gradient launch writes
+void wgrad_dest(RdpWgrad& g, const torch::Tensor& slab, const torch::Tensor& out, int accumulate) {
+  check_f32(slab, "slab");
+  check_f32(out, "out");
+  g.slab = slab.data_ptr<float>(); g.slab_elems = slab.numel();
+  g.out = out.data_ptr<float>(); g.accumulate = accumulate;
+}
+
 int conv_wgrad(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor dy, int taps, int packed, int cin_real,
                torch::Tensor slab, torch::Tensor out, int accumulate, int splits, int variant) {
   Act a1 = act(x1, "x1"), a2;
   if (x2) a2 = act(*x2, "x2");
   Act d = act(dy, "dy");
   TORCH_CHECK(d.N == a1.N && d.H == a1.H && d.W == a1.W, "dy spatial mismatch");
-  check_f32(slab, "slab");
-  check_f32(out, "out");
-  const int Cin = packed ? cin_real : a1.C + (x2 ? a2.C : 0);
+  TORCH_CHECK(variant == RDP_WGRAD_AUTO || variant == RDP_WGRAD_GENERIC || variant == RDP_WGRAD_HALO,
+              "conv_wgrad: variant must be WGRAD_AUTO, WGRAD_GENERIC or WGRAD_HALO, not ", variant);
+  RdpWgrad g;
+  wgrad_dest(g, slab, out, accumulate);
+  g.taps = taps; g.packed = packed; g.cin_real = cin_real;
+  const int Cin = packed ? cin_real : a1.C + a2.C;
   TORCH_CHECK(out.numel() == (long)d.C * taps * Cin, "wgrad out numel mismatch");
   // batch chunks below the 2 GiB buffer-offset reach (see conv_fwd), accumulated into out
   const int nc = chunk_images({a1, a2, d}, a1.N);
   int r = 0;
   for (int n0 = 0; n0 < a1.N; n0 += nc) {
-    const int nn = std::min(nc, a1.N - n0);
-    void* const px1 = a1.image(n0);
-    void* const px2 = x2 ? a2.image(n0) : nullptr;
-    void* const pdy = d.image(n0);
-    const long bx1 = a1.span_bytes(nn), bx2 = x2 ? a2.span_bytes(nn) : 0, bdy = d.span_bytes(nn);
-    const int C2 = x2 ? a2.C : 0, p2 = x2 ? a2.pitch : 0, acc = n0 > 0 ? 1 : accumulate;
-    float* const slp = slab.data_ptr<float>();
-    const long sln = slab.numel();
-    float* const outp = out.data_ptr<float>();
-    r = RDP_PLAN(rdp_conv_wgrad(px1, px2, bx1, bx2, a1.C, C2, a1.pitch, p2, pdy, bdy, d.pitch, slp, sln, outp, acc, nn,
-                                a1.H, a1.W, d.C, taps, packed, cin_real, splits, variant, st));
+    wgrad_bind(g, a1, a2, d, n0, std::min(nc, a1.N - n0));
+    if (n0 > 0) g.accumulate = 1;
+    r = RDP_PLAN(rdp_conv_wgrad(g, variant, splits, st));
     TORCH_CHECK(r >= 0, "conv_wgrad: unsupported shape or slab too small (code ", r, ")");
   }
   return r;
@@ -660,21 +672,41 @@ int wgrad_first_bn(torch::Tensor x, torch::Tensor da, torch::Tensor y, torch::Te
   TORCH_CHECK(a.C == 8 && d.C == 64 && b.C == 64, "wgrad_first_bn: x must have 8 (packed) and da / y 64 channels");
   TORCH_CHECK(d.N == a.N && d.H == a.H && d.W == a.W && b.N == a.N && b.H == a.H && b.W == a.W,
               "wgrad_first_bn: spatial mismatch");
-  check_f32(coef, "coef"); check_f32(coef2, "coef2"); check_f32(slab, "slab"); check_f32(out, "out");
+  check_f32(coef, "coef"); check_f32(coef2, "coef2");
+  RdpWgrad g;
+  wgrad_dest(g, slab, out, accumulate);
   TORCH_CHECK(coef.numel() >= 4 * 64 && coef2.numel() >= 3 * 64, "wgrad_first_bn: coef / coef2 too small");
   TORCH_CHECK(out.numel() == 64l * 9 * cin_real, "wgrad_first_bn: out numel mismatch");
   if (a.bytes >= (1l << 31) || d.bytes >= (1l << 31) || b.bytes >= (1l << 31)) return -1;
   if (((long)a.N * a.H * a.W) % 64) return -1;
-  const int r = RDP_PLAN(rdp_wgrad_first_bn(a.ptr, a.bytes, a.pitch, d.ptr, d.bytes, d.pitch, b.ptr, b.bytes, b.pitch,
-                                            coef.data_ptr<float>(), coef2.data_ptr<float>(), slab.data_ptr<float>(),
-                                            slab.numel(), out.data_ptr<float>(), accumulate, a.N, a.H, a.W, cin_real,
-                                            splits, st));
+  wgrad_bind(g, a, Act{}, Act{}, 0, a.N);
+  g.Cout = 64; g.taps = 9; g.packed = 1; g.cin_real = cin_real;
+  RdpWgradBn bn;
+  bn.da = d.ptr; bn.dabytes = d.bytes; bn.dapitch = d.pitch;
+  bn.y = b.ptr; bn.ybytes = b.bytes; bn.ypitch = b.pitch;
+  bn.coef = coef.data_ptr<float>(); bn.coef2 = coef2.data_ptr<float>();
+  const int r = RDP_PLAN(rdp_wgrad_first_bn(g, bn, splits, st));
   TORCH_CHECK(r > 0, "wgrad_first_bn: slab too small (code ", r, ")");
   return r;
 }
 
-long wgrad_slab_elems(int N, int H, int W, int Cin, int Cout, int taps, int packed, int splits) {
-  return rdp_conv_wgrad_slab_elems(N, H, W, Cin, Cout, taps, packed, splits);
+// The plan of a dense weight gradient of this shape, as a dict (kernel: the RdpWgradKernel value, -1 = unsupported;
+// status: 0, or the RdpWgradStatus the launcher would return). upT: the ConvTranspose2d form (c1 = C, cout = its
+// input channels, h / w = the low-res map); first_bn: the first layer's fused form.
+py::dict wgrad_plan(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed, int cin_real, int kernel,
+                    int splits, long slab_elems, bool upT, bool first_bn) {
+  RdpWgradQuery q;
+  q.N = N; q.H = H; q.W = W; q.C1 = C1; q.C2 = C2; q.Cout = Cout; q.taps = taps; q.packed = packed;
+  q.cin_real = cin_real; q.kernel = kernel; q.splits = splits; q.slab_elems = slab_elems; q.upT = upT;
+  q.first_bn = first_bn;
+  const RdpWgradPlan p = rdp_wgrad_plan_dense(q);
+  py::dict d;
+  d["status"] = p.status; d["kernel"] = p.kernel; d["name"] = rdp_wgrad_kernel_name(p.kernel);
+  d["bn"] = p.BN; d["multirow"] = p.multirow; d["tiles"] = p.tiles; d["splits"] = p.splits;
+  d["per_split"] = p.per_split; d["grid"] = p.grid; d["block"] = p.block; d["slab_elems"] = p.slab_elems;
+  d["reduce_groups"] = p.reduce.G; d["reduce_grid1"] = p.reduce.grid1; d["reduce_grid2"] = p.reduce.grid2;
+  d["reduce_vec"] = p.reduce.vec;
+  return d;
 }
 
 void bn_finalize(torch::Tensor stats, int T, long count, torch::Tensor gamma, torch::Tensor beta,
@@ -939,6 +971,24 @@ void upT_shuffle(torch::Tensor yT, torch::Tensor bias, torch::Tensor u, int oy, 
                               o.C, st)) == 0, "upT_shuffle");
 }
 
+// the placement of the 2h x 2w window of low-res map `low` at (oy, ox) in `big`
+RdpUpT upT_place(const Act& big, const Act& low, int oy, int ox, const char* what) {
+  TORCH_CHECK(big.N == low.N && oy >= 0 && ox >= 0 && 2 * low.H + oy <= big.H && 2 * low.W + ox <= big.W, what);
+  RdpUpT t;
+  t.H2 = big.H; t.W2 = big.W; t.oy = oy; t.ox = ox;
+  return t;
+}
+
+// host only: whether conv_upT_fwd / conv_upT_dgrad take dense tensors of this shape (else they return -1), the tile
+py::dict upT_plan(bool fwd, int N, int h, int w, int Cin, int C, int H2, int W2, int oy, int ox) {
+  RdpUpT t;
+  t.H2 = H2; t.W2 = W2; t.oy = oy; t.ox = ox;
+  const RdpUpTGeo g = rdp_upT_geo_dense(fwd, N, h, w, Cin, C, t);
+  py::dict d;
+  d["fits"] = g.fits; d["bn"] = g.BN; d["grid"] = g.grid;
+  return d;
+}
+
 // ConvTranspose2d(2, s2) + bias written straight into u at (oy, ox) by the ping-pong GEMM's epilogue
 // (w = the [4C][Cin] forward weight). Returns 0, or -1 when that kernel does not take the shape: the
 // caller then runs conv_fwd into yT + upT_shuffle. u's border outside the window is not written.
@@ -948,9 +998,14 @@ int conv_upT_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor bias, torch::Te
   TORCH_CHECK(w.scalar_type() == torch::kBFloat16 && w.is_contiguous() && w.dim() == 2 && w.size(0) == 4 * o.C &&
                   w.size(1) >= a.C, "conv_upT_fwd: w must be bf16 [4C][>= Cin]");
   TORCH_CHECK(a.N == o.N && bias.numel() == o.C, "conv_upT_fwd shapes");
-  TORCH_CHECK(oy >= 0 && ox >= 0 && 2 * a.H + oy <= o.H && 2 * a.W + ox <= o.W, "conv_upT_fwd placement");
-  return RDP_PLAN(rdp_conv_upT_fwd(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, (int)w.size(1), o.ptr,
-                                   o.bytes, o.pitch, bias.data_ptr<float>(), a.N, a.H, a.W, o.H, o.W, oy, ox, o.C, st));
+  const RdpUpT t = upT_place(o, a, oy, ox, "conv_upT_fwd placement");
+  RdpConv c;
+  conv_bind(c, kX1, a, 0, a.N);
+  conv_bind(c, kY1, o, 0, a.N);
+  conv_weights(c, w);
+  c.Cout = 4 * o.C;
+  const float* const bp = bias.data_ptr<float>();
+  return RDP_PLAN(rdp_conv_upT_fwd(c, t, bp, st));
 }
 
 // ConvTranspose2d(2, s2) input gradient dx [N,h,w,Cin] read straight from du (its 4 sub-pixels per
@@ -960,9 +1015,13 @@ int conv_upT_dgrad(torch::Tensor du, torch::Tensor wd, torch::Tensor dx, int oy,
   Act d = act(du, "du"), o = act(dx, "dx");
   TORCH_CHECK(wd.scalar_type() == torch::kBFloat16 && wd.is_contiguous() && wd.dim() == 2 && wd.size(0) == o.C &&
                   wd.size(1) >= 4 * d.C, "conv_upT_dgrad: wd must be bf16 [Cin][>= 4C]");
-  TORCH_CHECK(d.N == o.N && oy >= 0 && ox >= 0 && 2 * o.H + oy <= d.H && 2 * o.W + ox <= d.W, "conv_upT_dgrad placement");
-  return RDP_PLAN(rdp_conv_upT_dgrad(d.ptr, d.bytes, d.C, d.pitch, d.H, d.W, oy, ox, wd.data_ptr(), wd.numel() * 2,
-                                     (int)wd.size(1), o.ptr, o.bytes, o.C, o.pitch, o.N, o.H, o.W, st));
+  const RdpUpT t = upT_place(d, o, oy, ox, "conv_upT_dgrad placement");
+  RdpConv c;
+  conv_bind(c, kX1, d, 0, d.N);
+  conv_bind(c, kY1, o, 0, o.N);
+  conv_weights(c, wd);
+  c.H = o.H; c.W = o.W; c.Cout = o.C;  // the GEMM runs over the low-res map
+  return RDP_PLAN(rdp_conv_upT_dgrad(c, t, st));
 }
 
 // ConvTranspose2d(2, s2) weight gradient out [Cin][4C] (+)= from du (4 sub-pixels per pixel of x) and
@@ -970,13 +1029,13 @@ int conv_upT_dgrad(torch::Tensor du, torch::Tensor wd, torch::Tensor dx, int oy,
 int conv_wgrad_upT(torch::Tensor du, torch::Tensor x, int oy, int ox, torch::Tensor slab, torch::Tensor out,
                    int accumulate, int splits) {
   Act d = act(du, "du"), a = act(x, "x");
-  check_f32(slab, "slab");
-  check_f32(out, "out");
+  RdpWgrad g;
+  wgrad_dest(g, slab, out, accumulate);
   TORCH_CHECK(out.numel() == (long)a.C * 4 * d.C, "conv_wgrad_upT out numel");
-  TORCH_CHECK(d.N == a.N && oy >= 0 && ox >= 0 && 2 * a.H + oy <= d.H && 2 * a.W + ox <= d.W, "conv_wgrad_upT placement");
-  return RDP_PLAN(rdp_conv_wgrad_upT(d.ptr, d.bytes, d.C, d.pitch, d.H, d.W, oy, ox, a.ptr, a.bytes, a.C, a.pitch, a.N,
-                                     a.H, a.W, slab.data_ptr<float>(), slab.numel(), out.data_ptr<float>(), accumulate,
-                                     splits, st));
+  const RdpUpT t = upT_place(d, a, oy, ox, "conv_wgrad_upT placement");
+  wgrad_bind(g, d, Act{}, a, 0, a.N);
+  g.H = a.H; g.W = a.W; g.taps = 4;  // the GEMM runs over the low-res map
+  return RDP_PLAN(rdp_conv_wgrad_upT(g, t, splits, st));
 }
 
 void upT_unshuffle(torch::Tensor du, torch::Tensor dyT, int oy, int ox) {
@@ -2068,8 +2127,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_fwd_bnin", on_device(&conv_fwd_bnin), py::arg("x_pre"), py::arg("w"), py::arg("y"), py::arg("stats"),
         py::arg("in_coef"), py::arg("a_out") = py::none());
   m.def("wgrad_first_bn", on_device(&wgrad_first_bn));
-  m.def("wgrad_slab_elems", &wgrad_slab_elems);
+  m.def("wgrad_slab_elems", &rdp_conv_wgrad_slab_elems);
   m.def("wgrad_halo_slab_elems", &rdp_conv_wgrad_halo_slab_elems);
+  // the weight-gradient kernels (csrc/conv_plan.h RdpWgradKernel): conv_wgrad's variant takes AUTO, GENERIC, HALO
+  for (int i = 0; i < rdp_wgrad_kernel_count; ++i)
+    m.attr((std::string("WGRAD_") + rdp_wgrad_kernel_names[i].name).c_str()) = rdp_wgrad_kernel_names[i].kernel;
+  m.def("wgrad_plan", &wgrad_plan, py::arg("n"), py::arg("h"), py::arg("w"), py::arg("c1"), py::arg("c2"), py::arg("cout"),
+        py::arg("taps") = 9, py::arg("packed") = 0, py::arg("cin_real") = 0, py::arg("kernel") = 0,
+        py::arg("splits") = 1, py::arg("slab_elems") = 0, py::arg("upT") = false, py::arg("first_bn") = false,
+        "host only, launches nothing: what conv_wgrad / conv_wgrad_upT / wgrad_first_bn would run for a dense layer "
+        "of this shape on a slab of slab_elems (rdp_wgrad_plan)");
+  m.def("wgrad_auto_splits", &rdp_wgrad_auto_splits, py::arg("n"), py::arg("h"), py::arg("w"), py::arg("cin"),
+        py::arg("cout"), py::arg("taps"), py::arg("packed"), py::arg("target_blocks"));
   m.def("bn_finalize", on_device(&bn_finalize));
   m.def("bn_eval_coef", on_device(&bn_eval_coef));
   m.def("bn_relu_apply", on_device(&bn_relu_apply));
@@ -2086,6 +2155,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("upsample2_fwd", on_device(&upsample2_fwd), py::arg("x"), py::arg("out"), py::arg("oy"), py::arg("ox"),
         py::arg("coef") = py::none());
   m.def("upT_shuffle", on_device(&upT_shuffle));
+  m.def("upT_plan", &upT_plan, py::arg("fwd"), py::arg("n"), py::arg("h"), py::arg("w"), py::arg("cin"), py::arg("c"),
+        py::arg("h2"), py::arg("w2"), py::arg("oy"), py::arg("ox"));
   m.def("conv_upT_fwd", on_device(&conv_upT_fwd));
   m.def("conv_upT_dgrad", on_device(&conv_upT_dgrad));
   m.def("conv_wgrad_upT", on_device(&conv_wgrad_upT));

@@ -764,55 +764,31 @@ static int launch_pp(ConvArgs a, hipStream_t s, int ksplit = 1, int* pooled = nu
   return g.rows;
 }
 
-extern "C" int rdp_conv_upT_fwd(const void* x, long xbytes, int Cin, int pitch, const void* w, long wbytes, int ldw,
-                                void* u, long ubytes, int upitch, const float* bias, int N, int h, int wd, int H2,
-                                int W2, int oy, int ox, int C, hipStream_t s) {
-  // (C <= 512: the bias fits the kernel's 4 BN statistics words at BN = 128)
-  if (C < 64 || C > 512 || (C & (C - 1)) || Cin % 64 || ldw < Cin || upitch % 8 || oy < 0 || ox < 0 ||
-      2 * h + oy > H2 || 2 * wd + ox > W2)
-    return -1;
-  if (xbytes >= (1l << 31) || ubytes >= (1l << 31) || wbytes >= (1l << 31)) return -1;
-  ConvArgs a;
-  a.x1 = (const u16*)x; a.x2 = nullptr; a.xbytes1 = (uint32_t)xbytes; a.xbytes2 = 0;
-  a.C1 = Cin; a.C2 = 0; a.pitch1 = pitch; a.pitch2 = pitch;
-  a.w = (const u16*)w; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y1 = (u16*)u; a.y2 = nullptr; a.ybytes1 = (uint32_t)ubytes; a.ybytes2 = 0;
-  a.Cout = 4 * C; a.Cy1 = a.Cout; a.ypitch1 = upitch; a.ypitch2 = upitch; a.stats = nullptr;
-  a.escale = nullptr; a.eshift = nullptr; a.erelu = 0;
-  a.N = N; a.H = h; a.W = wd; a.M = N * h * wd;
-  a.taps = 1; a.packed = 0; a.cpt = Cin / 64; a.nks = a.cpt;
-  a.ksplit = 1; a.kslab = nullptr; a.pool = nullptr; a.up = nullptr;
-  const FastDiv fhw = make_fastdiv((uint32_t)(h * wd)), fw = make_fastdiv((uint32_t)wd);
-  a.fhw_m = fhw.m; a.fhw_s = fhw.s; a.fw_m = fw.m; a.fw_s = fw.s;
-  a.ubias = bias; a.tH2 = H2; a.tW2 = W2; a.toy = oy; a.tox = ox;
-  a.tlc = 0;
-  while ((1 << a.tlc) < C) ++a.tlc;
-  if (a.Cout % 256 == 0 && (long)(a.M + 255) / 256 * (a.Cout / 256) >= 256) return launch_pp<256>(a, s) >= 0 ? 0 : -1;
-  if (Cin >= 128 && (long)(a.M + 255) / 256 * (a.Cout / 128) >= 256) return launch_pp<128>(a, s) >= 0 ? 0 : -1;
-  return -1;
+static ConvArgs conv_args(const RdpConv& c, int taps, int packed, float* ws, const RdpConvFuse& fuse, int* pooled,
+                          const RdpConvBnBwd& bn, int* bnrows);
+
+// ConvArgs of a ConvTranspose2d launch: one source, one destination of all Cout GEMM columns, the placement
+static ConvArgs upT_args(const RdpConv& c, int taps, const RdpUpT& t) {
+  ConvArgs a = conv_args(c, taps, 0, nullptr, RdpConvFuse{}, nullptr, RdpConvBnBwd{}, nullptr);
+  a.pitch2 = a.pitch1; a.ypitch2 = a.ypitch1; a.Cy1 = a.Cout;
+  a.tH2 = t.H2; a.tW2 = t.W2; a.toy = t.oy; a.tox = t.ox;
+  return a;
 }
 
-extern "C" int rdp_conv_upT_dgrad(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
-                                  const void* wd, long wbytes, int ldw, void* dx, long dxbytes, int Cin, int dxpitch,
-                                  int N, int h, int wdt, hipStream_t s) {
-  if (C % 64 || Cin % 128 || ldw < 4 * C || oy < 0 || ox < 0 || 2 * h + oy > H2 || 2 * wdt + ox > W2) return -1;
-  if (dubytes >= (1l << 31) || dxbytes >= (1l << 31) || wbytes >= (1l << 31)) return -1;
-  ConvArgs a;
-  a.x1 = (const u16*)du; a.x2 = nullptr; a.xbytes1 = (uint32_t)dubytes; a.xbytes2 = 0;
-  a.C1 = C; a.C2 = 0; a.pitch1 = dupitch; a.pitch2 = dupitch;
-  a.w = (const u16*)wd; a.wbytes = (uint32_t)wbytes; a.ldw = ldw;
-  a.y1 = (u16*)dx; a.y2 = nullptr; a.ybytes1 = (uint32_t)dxbytes; a.ybytes2 = 0;
-  a.Cout = Cin; a.Cy1 = Cin; a.ypitch1 = dxpitch; a.ypitch2 = dxpitch; a.stats = nullptr;
-  a.escale = nullptr; a.eshift = nullptr; a.erelu = 0;
-  a.N = N; a.H = h; a.W = wdt; a.M = N * h * wdt;
-  a.taps = 4; a.packed = 0; a.cpt = C / 64; a.nks = 4 * a.cpt;
-  a.ksplit = 1; a.kslab = nullptr; a.pool = nullptr; a.up = nullptr;
-  const FastDiv fhw = make_fastdiv((uint32_t)(h * wdt)), fw = make_fastdiv((uint32_t)wdt);
-  a.fhw_m = fhw.m; a.fhw_s = fhw.s; a.fw_m = fw.m; a.fw_s = fw.s;
-  a.tH2 = H2; a.tW2 = W2; a.toy = oy; a.tox = ox;
-  if (Cin % 256 == 0 && (long)(a.M + 255) / 256 * (Cin / 256) >= 256) return launch_pp<256>(a, s) >= 0 ? 0 : -1;
-  if ((long)(a.M + 255) / 256 * (Cin / 128) >= 256) return launch_pp<128>(a, s) >= 0 ? 0 : -1;
-  return -1;
+int rdp_conv_upT_fwd(const RdpConv& c, const RdpUpT& t, const float* bias, hipStream_t s) {
+  const RdpUpTGeo g = rdp_upT_fwd_geo(c, t);
+  if (!g.fits) return -1;
+  ConvArgs a = upT_args(c, 1, t);
+  a.ubias = bias;
+  a.tlc = g.tlc;
+  return (g.BN == 256 ? launch_pp<256>(a, s) : launch_pp<128>(a, s)) >= 0 ? 0 : -1;
+}
+
+int rdp_conv_upT_dgrad(const RdpConv& c, const RdpUpT& t, hipStream_t s) {
+  const RdpUpTGeo g = rdp_upT_dgrad_geo(c, t);
+  if (!g.fits) return -1;
+  const ConvArgs a = upT_args(c, 4, t);
+  return (g.BN == 256 ? launch_pp<256>(a, s) : launch_pp<128>(a, s)) >= 0 ? 0 : -1;
 }
 
 

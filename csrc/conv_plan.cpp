@@ -351,6 +351,237 @@ RdpIgemmGeo rdp_pp_geo(const RdpGemmShape& g, int BN, int ksplit, bool has_ws, R
   return r;
 }
 
+// ---- ConvTranspose2d on the ping-pong kernel -------------------------------------------------------------------
+namespace {
+
+// 256-pixel tiles x BN channels on one persistent block per CU, taken only where they fill the chip
+RdpUpTGeo upT_tile(const RdpConv& c, int taps, int Cin, bool wide_only_long_k) {
+  RdpUpTGeo u;
+  RdpGemmShape g;
+  g.M = c.N * c.H * c.W; g.Cout = c.Cout; g.Cy1 = c.Cout; g.nks = taps * (Cin / 64); g.N = c.N;
+  const long mt = (long)(g.M + 255) / 256;
+  if (c.Cout % 256 == 0 && mt * (c.Cout / 256) >= 256) u.BN = 256;
+  else if ((!wide_only_long_k || Cin >= 128) && mt * (c.Cout / 128) >= 256) u.BN = 128;
+  else return u;
+  const RdpIgemmGeo r = rdp_pp_geo(g, u.BN, 1, false, RdpConvFuseOk{});
+  u.fits = r.fits;
+  u.grid = r.grid;
+  return u;
+}
+
+bool upT_placed(const RdpConv& c, const RdpUpT& t) {
+  return t.oy >= 0 && t.ox >= 0 && 2 * c.H + t.oy <= t.H2 && 2 * c.W + t.ox <= t.W2;
+}
+
+}  // namespace
+
+RdpUpTGeo rdp_upT_fwd_geo(const RdpConv& c, const RdpUpT& t) {
+  const int C = c.Cout / 4, Cin = c.C1;
+  if (c.Cout % 4 || C < 64 || C > 512 || (C & (C - 1)) || Cin % 64 || c.ldw < Cin || c.ypitch1 % 8 || !upT_placed(c, t))
+    return RdpUpTGeo{};
+  if (c.xbytes1 >= kMaxBytes || c.ybytes1 >= kMaxBytes || c.wbytes >= kMaxBytes) return RdpUpTGeo{};
+  RdpUpTGeo u = upT_tile(c, 1, Cin, true);
+  u.tlc = ilog2_exact(C);
+  return u;
+}
+
+RdpUpTGeo rdp_upT_dgrad_geo(const RdpConv& c, const RdpUpT& t) {
+  const int C = c.C1, Cin = c.Cout;
+  if (C % 64 || Cin % 128 || c.ldw < 4 * C || !upT_placed(c, t)) return RdpUpTGeo{};
+  if (c.xbytes1 >= kMaxBytes || c.ybytes1 >= kMaxBytes || c.wbytes >= kMaxBytes) return RdpUpTGeo{};
+  return upT_tile(c, 4, C, false);
+}
+
+RdpUpTGeo rdp_upT_geo_dense(bool fwd, int N, int h, int w, int Cin, int C, const RdpUpT& t) {
+  static char mark;
+  const long lo = (long)N * h * w * Cin * 2, hi = (long)N * t.H2 * t.W2 * C * 2;
+  RdpConv c;
+  c.N = N; c.H = h; c.W = w;
+  c.x1 = &mark; c.w = &mark; c.y1 = &mark;
+  c.wbytes = 4L * C * Cin * 2;
+  if (fwd) {  // x [N][h][w][Cin] -> u [N][H2][W2][C]
+    c.C1 = c.pitch1 = c.ldw = Cin; c.xbytes1 = lo;
+    c.Cout = 4 * C; c.Cy1 = c.ypitch1 = C; c.ybytes1 = hi;
+    return rdp_upT_fwd_geo(c, t);
+  }
+  c.C1 = c.pitch1 = C; c.ldw = 4 * C; c.xbytes1 = hi;  // du [N][H2][W2][C] -> dx [N][h][w][Cin]
+  c.Cout = c.Cy1 = c.ypitch1 = Cin; c.ybytes1 = lo;
+  return rdp_upT_dgrad_geo(c, t);
+}
+
+// ---- the weight gradients --------------------------------------------------------------------------------------
+const RdpConvKernelName rdp_wgrad_kernel_names[] = {
+    {RDP_WGRAD_AUTO, "AUTO"},       {RDP_WGRAD_RING, "RING"}, {RDP_WGRAD_PACKED, "PACKED"},     {RDP_WGRAD_UPT, "UPT"},
+    {RDP_WGRAD_GENERIC, "GENERIC"}, {RDP_WGRAD_HALO, "HALO"}, {RDP_WGRAD_FIRST_BN, "FIRST_BN"},
+};
+const int rdp_wgrad_kernel_count = sizeof(rdp_wgrad_kernel_names) / sizeof(rdp_wgrad_kernel_names[0]);
+
+const char* rdp_wgrad_kernel_name(int kernel) {
+  for (int i = 0; i < rdp_wgrad_kernel_count; ++i)
+    if (rdp_wgrad_kernel_names[i].kernel == kernel) return rdp_wgrad_kernel_names[i].name;
+  return "UNSUPPORTED";
+}
+
+bool rdp_wgrad_halo_shape(int H, int W, bool forced) {
+  return W % 64 == 0 || (W >= (forced ? 8 : 32) && 64 % W == 0 && (H * W) % 64 == 0);
+}
+
+RdpWgradSplit rdp_wgrad_pixel_split(long M, int splits) {
+  RdpWgradSplit s;
+  s.want = std::max(1, splits);
+  const long pps = ((M + s.want - 1) / s.want + 63) / 64 * 64;
+  s.per_split = (int)pps;
+  s.splits = pps > 0 ? (int)((M + pps - 1) / pps) : 0;
+  return s;
+}
+
+RdpWgradSplit rdp_wgrad_halo_split(int nseg, int tiles, int BN, long max_splits) {
+  RdpWgradSplit s;
+  const int target = BN == 64 ? 512 : 256;
+  s.want = std::max(1, (target + tiles - 1) / tiles);
+  s.want = std::min<long>(s.want, std::max(1, nseg));
+  s.want = std::min(s.want, max_splits);
+  if (s.want < 1) return s;
+  s.per_split = (int)((nseg + s.want - 1) / s.want);
+  s.splits = s.per_split > 0 ? (nseg + s.per_split - 1) / s.per_split : 0;
+  return s;
+}
+
+RdpWgradReduce rdp_wgrad_reduce_geo(int splits, int Cout, int ncols_pad, int taps, int cin_pad, int cin_real) {
+  RdpWgradReduce r;
+  const long E = (long)Cout * ncols_pad;  // multiple of 4 (Cout % 64 == 0)
+  const long chunks = (E / 4 + 255) / 256;
+  r.G = (int)std::min<long>(std::min<long>(splits, 32), std::max<long>(1, (1024 + chunks - 1) / std::max(1L, chunks)));
+  if (splits <= 8) r.G = splits;
+  r.grid1 = r.G < splits ? (int)chunks : 0;
+  const long total = (long)Cout * taps * cin_real;
+  r.vec = cin_real % 4 == 0 && cin_pad % 4 == 0 ? 4 : 1;
+  r.grid2 = (int)std::min<long>((total / r.vec + 255) / 256, 4096);
+  return r;
+}
+
+namespace {
+
+// the shared tail of every plan: the slab the splits use against the slab offered, the grid, the reduce
+RdpWgradPlan wgrad_finish(RdpWgradPlan p, const RdpWgradSplit& s, long offered) {
+  p.splits = s.splits;
+  p.per_split = s.per_split;
+  p.slab_elems = (long)s.splits * p.Cout * p.ncols_pad;
+  p.grid = p.tiles * s.splits;
+  p.status = p.slab_elems > offered             ? RDP_WGRAD_SLAB_SMALL
+             : p.slab_elems * 4 >= kMaxBytes ? RDP_WGRAD_SLAB_2GIB
+                                              : RDP_WGRAD_OK;
+  p.reduce = rdp_wgrad_reduce_geo(s.splits, p.Cout, p.ncols_pad, p.taps, p.cin_pad, p.cin_out);
+  return p;
+}
+
+}  // namespace
+
+RdpWgradPlan rdp_wgrad_plan(const RdpWgrad& g, int kernel, int splits, const RdpUpT& upT, const RdpWgradBn& bn) {
+  RdpWgradPlan p;
+  const long M = (long)g.N * g.H * g.W;
+  if (M < 1 || M >= kMaxBytes) return p;
+  if (bn.da) {  // the first layer with its BN backward: one block per split, 64 couts x 80 columns
+    if (kernel != RDP_WGRAD_AUTO || M % 64 || g.cin_real > 8 || g.cin_real < 1) return p;
+    if (g.xbytes1 >= kMaxBytes || bn.dabytes >= kMaxBytes || bn.ybytes >= kMaxBytes) return p;
+    if (g.pitch1 % 8 || bn.dapitch % 8 || bn.ypitch % 8) return p;
+    p.kernel = RDP_WGRAD_FIRST_BN;
+    p.BN = p.Cout = 64; p.taps = 9; p.tiles = 1; p.block = 256;
+    p.ncols = 72; p.ncols_pad = RDP_WGRAD_FIRST_NCOLS; p.cin_pad = 8; p.cin_out = g.cin_real;
+    return wgrad_finish(p, rdp_wgrad_pixel_split(M, splits), g.slab_elems);
+  }
+  int Cin = g.C1 + g.C2;
+  p.Cout = g.Cout; p.taps = g.taps;
+  if (upT.H2 > 0) {
+    if (kernel != RDP_WGRAD_AUTO || g.taps != 4 || g.packed || g.C2 || g.C1 % 64 || g.Cout % 64 || g.C1 == 0) return p;
+    if (upT.oy < 0 || upT.ox < 0 || 2 * g.H + upT.oy > upT.H2 || 2 * g.W + upT.ox > upT.W2) return p;
+    if (g.xbytes1 >= kMaxBytes || g.dybytes >= kMaxBytes) return p;
+    p.kernel = RDP_WGRAD_UPT;
+  } else {
+    if (kernel != RDP_WGRAD_AUTO && kernel != RDP_WGRAD_GENERIC && kernel != RDP_WGRAD_HALO) return p;
+    if (g.packed) {
+      if (g.C1 != 8 || g.C2 != 0 || g.taps != 9) return p;
+      Cin = 8;
+    } else if (g.C1 % 64 || g.C2 % 64 || Cin == 0) {
+      return p;
+    }
+    if (g.Cout % 64 || g.Cout == 0 || g.taps < 1) return p;
+    if (g.xbytes1 >= kMaxBytes || g.xbytes2 >= kMaxBytes || g.dybytes >= kMaxBytes) return p;
+    // halo reuse: 3x3, whole 64-pixel row segments
+    const bool forced = kernel == RDP_WGRAD_HALO;
+    const bool halo = !g.packed && g.taps == 9 && kernel != RDP_WGRAD_GENERIC && rdp_wgrad_halo_shape(g.H, g.W, forced);
+    if (forced && !halo) return p;
+    if (halo) {
+      p.BN = g.Cout % 128 == 0 ? 128 : 64;
+      // the row ring: same split of the positions; only where the dispatcher chooses (a forced HALO is the halo kernel)
+      const bool ring = kernel == RDP_WGRAD_AUTO && g.W % 64 == 0 && p.BN == 64;
+      p.kernel = ring ? RDP_WGRAD_RING : RDP_WGRAD_HALO;
+      p.multirow = !ring && g.W < 64;
+      p.block = p.BN * 4;
+      p.tiles = (Cin / 64) * (g.Cout / p.BN);
+      p.ncols = p.ncols_pad = 9 * Cin;
+      p.cin_pad = p.cin_out = Cin;
+      const long row = (long)g.Cout * p.ncols;
+      const RdpWgradSplit s = rdp_wgrad_halo_split((int)(M / 64), p.tiles, p.BN, g.slab_elems / row);
+      if (s.want < 1) {
+        p.status = RDP_WGRAD_SLAB_SMALL;
+        return p;
+      }
+      return wgrad_finish(p, s, g.slab_elems);
+    }
+    p.kernel = g.packed ? RDP_WGRAD_PACKED : RDP_WGRAD_GENERIC;
+  }
+  // the generic kernel: 256 (tap, cin) columns x 64 couts per block, 8 waves
+  p.BN = 64; p.block = 512;
+  p.ncols = g.packed ? 72 : g.taps * Cin;
+  p.ncols_pad = (p.ncols + 255) / 256 * 256;
+  p.tiles = p.ncols_pad / 256 * (g.Cout / 64);
+  p.cin_pad = Cin;
+  p.cin_out = g.packed ? g.cin_real : Cin;
+  return wgrad_finish(p, rdp_wgrad_pixel_split(M, splits), g.slab_elems);
+}
+
+RdpWgradPlan rdp_wgrad_plan_dense(const RdpWgradQuery& q) {
+  static char mark;
+  static float fmark;
+  auto bytes = [&](int C) { return (long)q.N * q.H * q.W * C * 2; };
+  RdpWgrad g;
+  g.x1 = &mark; g.C1 = q.C1; g.pitch1 = q.C1; g.xbytes1 = bytes(q.C1);
+  if (q.C2) { g.x2 = &mark; g.C2 = q.C2; g.pitch2 = q.C2; g.xbytes2 = bytes(q.C2); }
+  g.dy = &mark; g.dypitch = q.Cout; g.dybytes = bytes(q.Cout);
+  g.slab = &fmark; g.slab_elems = q.slab_elems; g.out = &fmark;
+  g.N = q.N; g.H = q.H; g.W = q.W; g.Cout = q.Cout; g.taps = q.taps; g.packed = q.packed; g.cin_real = q.cin_real;
+  RdpUpT t;
+  if (q.upT) {  // du = the dense [N][2H][2W][C1] map
+    t.H2 = 2 * q.H; t.W2 = 2 * q.W;
+    g.xbytes1 = 4 * bytes(q.C1);
+  }
+  RdpWgradBn bn;
+  if (q.first_bn) {
+    bn.da = &mark; bn.y = &mark; bn.dapitch = bn.ypitch = 64; bn.dabytes = bn.ybytes = bytes(64);
+    bn.coef = bn.coef2 = &fmark;
+  }
+  return rdp_wgrad_plan(g, q.kernel, q.splits, t, bn);
+}
+
+int rdp_wgrad_auto_splits(int N, int H, int W, int Cin, int Cout, int taps, int packed, int target_blocks) {
+  const long M = (long)N * H * W;
+  const long tiles = std::max(1L, (long)((packed ? 72 : taps * Cin) + 255) / 256 * (Cout / 64));
+  return (int)std::max(1L, std::min((target_blocks + tiles - 1) / tiles, M / 2048));
+}
+
+extern "C" long rdp_conv_wgrad_slab_elems(int N, int H, int W, int Cin, int Cout, int taps, int packed, int splits) {
+  const int ncols_pad = ((packed ? 72 : taps * Cin) + 255) / 256 * 256;
+  return (long)rdp_wgrad_pixel_split((long)N * H * W, splits).splits * Cout * ncols_pad;
+}
+
+extern "C" long rdp_conv_wgrad_halo_slab_elems(int N, int H, int W, int Cin, int Cout) {
+  if (Cin % 64 || Cout % 64 || Cin == 0 || Cout == 0 || !rdp_wgrad_halo_shape(H, W, false)) return 0;
+  const int BN = Cout % 128 == 0 ? 128 : 64;
+  const long nseg = (long)N * H * W / 64;
+  return rdp_wgrad_halo_split((int)nseg, (Cin / 64) * (Cout / BN), BN, 1L << 40).want * Cout * 9L * Cin;
+}
+
 // ---- the plan --------------------------------------------------------------------------------------------------
 RdpConvPlan rdp_conv_plan(const RdpConv& c, int taps, int packed, int kernel, bool has_ws, long ws_elems,
                           const RdpConvFuse& fuse, bool want_fused, const RdpConvBnBwd& bn, long wfrag_bytes) {

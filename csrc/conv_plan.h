@@ -2,7 +2,9 @@
 // blocks, the kernel names, one predicate + geometry function per kernel family, and rdp_conv_plan, which picks
 // the kernel for a conv and says what its launch will look like. The launchers (csrc/conv_*.hip) call the same
 // family functions the plan used, then fill their argument struct once and launch; sizing (workspace, stats
-// rows) is asked of the plan, never re-derived. tests/test_conv_plan_cpu.py drives this file without a GPU.
+// rows) is asked of the plan, never re-derived. The weight gradients (RdpWgrad, rdp_wgrad_plan) and the
+// ConvTranspose2d launchers' geometry follow the conv plan below. tests/test_conv_plan_cpu.py and
+// tests/test_wgrad_plan_cpu.py drive this file without a GPU.
 #pragma once
 
 // ---- the conv family's operand blocks ----------------------------------------------------------------------------
@@ -254,3 +256,154 @@ long rdp_conv_ws_elems(int N, int H, int W, int C1, int C2, int Cout, int taps, 
 // with room for batch-chunked launches. Allocation sizes are behaviour: tests/test_conv_plan_cpu.py holds every
 // plan's stats_rows against it.
 int rdp_conv_stats_rows(long M, int Cout, int kernel);
+
+// ---- ConvTranspose2d(k=2, s=2) on the ping-pong kernel ---------------------------------------------------------
+// Where the 2h x 2w window of a low-res h x w map sits in the [N][H2][W2] map it is scattered to / gathered from
+struct RdpUpT {
+  int H2 = 0, W2 = 0, oy = 0, ox = 0;
+};
+// The whole launch predicate (channel multiples, placement, extents) and the tile: the 256-wide tile where its
+// grid fills the chip (>= 256 tiles of 256 pixels), else the 128-wide one on the same condition, else no fit
+// and the caller takes the GEMM + shuffle path.
+struct RdpUpTGeo {
+  bool fits = false;
+  int BN = 0, tlc = 0, grid = 0;  // tlc: log2 of the output channels C (forward)
+};
+// c: x1 = the input [N][h][w][Cin], w = [4C][ldw], y1 = the output map u (ypitch1), Cout = 4C, N / H / W = the
+// low-res map. C a power of two in 64..512: the bias fits the kernel's 4 BN statistics words at BN = 128
+RdpUpTGeo rdp_upT_fwd_geo(const RdpConv& c, const RdpUpT& t);
+// c: x1 = the output gradient du [N][H2][W2][C], w = the [Cin][ldw >= 4C] dgrad weight, y1 = dx, Cout = Cin,
+// N / H / W = the low-res map
+RdpUpTGeo rdp_upT_dgrad_geo(const RdpConv& c, const RdpUpT& t);
+// Either one for dense tensors described by their shape (the upT_plan binding, the CPU test): Cin -> C channels,
+// an h x w input map
+RdpUpTGeo rdp_upT_geo_dense(bool fwd, int N, int h, int w, int Cin, int C, const RdpUpT& t);
+
+// ---- the weight gradients (conv_wgrad.hip) ---------------------------------------------------------------------
+// dW[cout][tap][cin] (+)= sum over pixels of x[pixel + tap][cin] * dy[pixel][cout], x = cat(x1, x2). Every kernel
+// splits the pixels over blocks that write fp32 partial results [split][Cout][row] into slab; the shared two-level
+// reduce sums them into out (OHWI). Same conventions as RdpConv: values only, zero defaults, extents < 2 GiB.
+struct RdpWgrad {
+  const void* x1 = nullptr;
+  const void* x2 = nullptr;
+  long xbytes1 = 0, xbytes2 = 0;
+  int C1 = 0, C2 = 0, pitch1 = 0, pitch2 = 0;
+  const void* dy = nullptr;
+  long dybytes = 0;
+  int dypitch = 0;
+  float* slab = nullptr;
+  long slab_elems = 0;
+  float* out = nullptr;
+  int accumulate = 0;
+  int N = 0, H = 0, W = 0, Cout = 0, taps = 0, packed = 0;
+  int cin_real = 0;  // packed: the input channels out holds (<= 8)
+};
+// rdp_wgrad_first_bn: the first layer's BN backward applied on the fly instead of a stored dy. da = the gradient
+// of the post-ReLU activation, y = the pre-BN output (64 channels each), coef = [mean | invstd | scale | shift],
+// coef2 = [A | B | K] (bn_bwd_finalize)
+struct RdpWgradBn {
+  const void* da = nullptr;
+  const void* y = nullptr;
+  long dabytes = 0, ybytes = 0;
+  int dapitch = 0, ypitch = 0;
+  const float* coef = nullptr;
+  const float* coef2 = nullptr;
+};
+
+// AUTO, GENERIC and HALO may be asked of rdp_conv_wgrad (the bindings export every value as _C.WGRAD_<name>); the
+// others are what a plan can come out as. A forced kernel that does not fit is an error, as is any other request.
+enum RdpWgradKernel : int {
+  RDP_WGRAD_UNSUPPORTED = -1,
+  // halo / row ring where whole 64-pixel row segments exist (3x3), the generic kernel for the rest. (A ping-pong
+  // 256 x 256 implicit-GEMM wgrad was built and measured 2x slower than the halo kernel: profiles/dead_ends.md.)
+  RDP_WGRAD_AUTO = 0,
+  // conv_wgrad_ring_kernel<64>: only on the auto path, W % 64 == 0 and Cout % 128 != 0 (the ring at 128 output
+  // channels measured neutral)
+  RDP_WGRAD_RING = 1,
+  RDP_WGRAD_PACKED = 2,    // conv_wgrad_kernel<PACKED>: the 3-channel first layer stored as 8 channels
+  RDP_WGRAD_UPT = 3,       // conv_wgrad_kernel<false, UTR>: rdp_conv_wgrad_upT
+  RDP_WGRAD_GENERIC = 4,   // conv_wgrad_kernel: any taps, channels in 64s
+  // conv_wgrad_halo_kernel<BN, MULTIROW>; forced: never the ring, and maps down to W = 8 (auto: W >= 32)
+  RDP_WGRAD_HALO = 5,
+  RDP_WGRAD_FIRST_BN = 6,  // wgrad_first_bn_kernel: rdp_wgrad_first_bn
+};
+extern const RdpConvKernelName rdp_wgrad_kernel_names[];
+extern const int rdp_wgrad_kernel_count;
+const char* rdp_wgrad_kernel_name(int kernel);  // "UNSUPPORTED" for anything else
+
+constexpr int RDP_WGRAD_FIRST_NCOLS = 80;  // FIRST_BN's slab row: 9 taps x 8 channels, padded to 5 MFMA fragments
+
+// what the launchers return instead of a split count
+enum RdpWgradStatus : int {
+  RDP_WGRAD_OK = 0,
+  RDP_WGRAD_NO_FIT = -1,      // shape / request not this launcher's (nothing launched)
+  RDP_WGRAD_SLAB_SMALL = -2,  // the slab does not hold the splits (generic) / a single split (halo, ring)
+  RDP_WGRAD_SLAB_2GIB = -3,   // the slab extent used would reach 2 GiB (buffer offsets)
+};
+
+// Halo / ring shape rule: whole 64-pixel segments, i.e. rows of 64s, or 64 / W whole rows per segment. The auto
+// dispatch takes the multi-row form from W = 32, a forced HALO from W = 8.
+bool rdp_wgrad_halo_shape(int H, int W, bool forced);
+// A split of `total` units over blocks: want = the count before rounding, then per_split = ceil(total / want)
+// (rounded up as the kernel needs) and splits = ceil(total / per_split), so no split is empty.
+struct RdpWgradSplit {
+  long want = 0;
+  int splits = 0, per_split = 0;
+};
+// generic / packed / upT / first-BN: `splits` (>= 1) pixel ranges in multiples of 64 pixels
+RdpWgradSplit rdp_wgrad_pixel_split(long M, int splits);
+// halo / ring: one resident wave of blocks (2 per CU at BN = 64, 1 at BN = 128; other grid targets and a minimum
+// segment count per split measured neutral) over `tiles` channel tiles, at most one split per 64-pixel segment
+// and what max_splits (the slab) holds. want < 1: the slab holds no split.
+RdpWgradSplit rdp_wgrad_halo_split(int nseg, int tiles, int BN, long max_splits);
+// rdp_wgrad_reduce's two launches over a slab [splits][Cout][ncols_pad]: level 1 (grid1 x G blocks; grid1 = 0:
+// not run) sums G groups of splits in place, level 2 (grid2 blocks, vec = 4 or 1 outputs per thread) sums the
+// group rows into out. ~1000 level-1 blocks, at most 32 group rows; <= 8 splits need no level 1.
+struct RdpWgradReduce {
+  int G = 0, grid1 = 0, grid2 = 0, vec = 0;
+};
+RdpWgradReduce rdp_wgrad_reduce_geo(int splits, int Cout, int ncols_pad, int taps, int cin_pad, int cin_real);
+
+struct RdpWgradPlan {
+  int status = RDP_WGRAD_NO_FIT;
+  int kernel = RDP_WGRAD_UNSUPPORTED;  // the kernel that runs (never AUTO)
+  int BN = 0;                          // output channels per block
+  bool multirow = false;               // halo: a 64-pixel segment spans 64 / W image rows
+  int tiles = 0;                       // channel tiles; grid = tiles * splits
+  int splits = 0, per_split = 0;       // per_split: pixels (generic family) or 64-pixel segments (halo, ring)
+  int grid = 0, block = 0;
+  int ncols = 0, ncols_pad = 0;        // (tap, cin) columns and the slab's row length
+  int cin_pad = 0, cin_out = 0;        // channels per tap in the slab row / in out
+  int Cout = 0, taps = 0;              // out is [Cout][taps][cin_out]
+  long slab_elems = 0;                 // fp32 slab elements the launch writes and the reduce reads
+  RdpWgradReduce reduce;
+};
+// The dispatcher's decision, launching nothing. kernel: RDP_WGRAD_AUTO / GENERIC / HALO; splits: the pixel splits
+// asked of the generic family (the halo / ring kernels choose their own, within g.slab_elems). upT.H2 > 0: the
+// ConvTranspose2d form (x1 = du, dy = the ConvT input, Cout = its channels, taps = 4); bn.da: the first-layer form.
+RdpWgradPlan rdp_wgrad_plan(const RdpWgrad& g, int kernel, int splits, const RdpUpT& upT = RdpUpT{},
+                            const RdpWgradBn& bn = RdpWgradBn{});
+// The same for a dense layer described by its shape alone (sizing, the wgrad_plan binding, the CPU test)
+struct RdpWgradQuery {
+  int N = 0, H = 0, W = 0, C1 = 0, C2 = 0, Cout = 0, taps = 9, packed = 0, cin_real = 0;
+  int kernel = RDP_WGRAD_AUTO, splits = 1;
+  long slab_elems = 0;
+  bool upT = false, first_bn = false;
+};
+RdpWgradPlan rdp_wgrad_plan_dense(const RdpWgradQuery& q);
+// The executor's split request for the generic family: target_blocks over the kernel's 256-column x 64-cout tiles,
+// but at least 2048 pixels per split.
+int rdp_wgrad_auto_splits(int N, int H, int W, int Cin, int Cout, int taps, int packed, int target_blocks);
+
+extern "C" {
+// Slab size (elements) for the generic kernel's `splits` pixel splits. The halo / row-ring kernels choose
+// their own split count, capped by the slab they are given: the training step shares one slab of the
+// largest generic size, which caps the deep layers' halo wgrads at 4-15 splits (~120 blocks). That is
+// deliberate: sized for a full wave of halo blocks (rdp_conv_wgrad_halo_slab_elems) the wgrads run ~1.8x
+// faster alone but the step got slower -- bs 64 3,120-3,131 vs 3,160-3,181 img/s, bs 4 1,405-1,409 vs
+// 1,591 (same box, 2 rounds): the side-stream wgrads then take every CU from the main stream's convs.
+long rdp_conv_wgrad_slab_elems(int N, int H, int W, int Cin, int Cout, int taps, int packed, int splits);
+// Slab the halo / row-ring wgrad needs for one resident wave of blocks (its own split choice
+// unconstrained); 0 where the auto dispatch does not pick those kernels. (conv_microbench.py sizes with it.)
+long rdp_conv_wgrad_halo_slab_elems(int N, int H, int W, int Cin, int Cout);
+}

@@ -720,151 +720,95 @@ static int ablate_flags() {
   return f;
 }
 
-extern "C" void rdp_wgrad_reduce(float* slab, float* out, int splits, int Cout, int ncols_pad, int taps, int cin_pad,
-                                 int cin_real, int accumulate, hipStream_t s) {
+// The two-level reduce of a planned weight gradient's slab into g.out (geometry: rdp_wgrad_reduce_geo)
+void rdp_wgrad_reduce(const RdpWgrad& g, const RdpWgradPlan& p, hipStream_t s) {
   if (ablate_flags() & 2) return;
-  const long E = (long)Cout * ncols_pad;  // multiple of 4 (Cout % 64 == 0)
-  const long chunks = (E / 4 + 255) / 256;
-  // ~1000 level-1 blocks, at most 32 group rows for level 2; few splits (deep layers) need no level 1
-  int G = (int)std::min<long>(std::min<long>(splits, 32), std::max<long>(1, (1024 + chunks - 1) / chunks));
-  if (splits <= 8) G = splits;
-  if (G < splits && !(ablate_flags() & 1)) hipLaunchKernelGGL(wgrad_group_sum_kernel, dim3((unsigned)chunks, G), dim3(256), 0, s, slab, E, splits, G);
-  const long total = (long)Cout * taps * cin_real;
-  if (cin_real % 4 == 0 && cin_pad % 4 == 0) {
-    const int rb = (int)std::min<long>((total / 4 + 255) / 256, 4096);
-    hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3(rb), dim3(256), 0, s, slab, out, splits, G, Cout, ncols_pad, taps,
-                       cin_pad, cin_real, accumulate);
-  } else {
-    const int rb = (int)std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3(rb), dim3(256), 0, s, slab, out, splits, G, Cout, ncols_pad, taps,
-                       cin_pad, cin_real, accumulate);
-  }
+  const RdpWgradReduce& r = p.reduce;
+  const long E = (long)p.Cout * p.ncols_pad;
+  if (r.grid1 && !(ablate_flags() & 1))
+    hipLaunchKernelGGL(wgrad_group_sum_kernel, dim3(r.grid1, r.G), dim3(256), 0, s, g.slab, E, p.splits, r.G);
+  if (r.vec == 4)
+    hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3(r.grid2), dim3(256), 0, s, g.slab, g.out, p.splits, r.G, p.Cout,
+                       p.ncols_pad, p.taps, p.cin_pad, p.cin_out, g.accumulate);
+  else
+    hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3(r.grid2), dim3(256), 0, s, g.slab, g.out, p.splits, r.G, p.Cout,
+                       p.ncols_pad, p.taps, p.cin_pad, p.cin_out, g.accumulate);
 }
 
-// Which weight-gradient kernel the auto dispatch (variant 0) runs for a 3x3 layer: halo / row-ring where
-// whole 64-pixel row segments exist, the generic implicit GEMM for the rest (16^2 maps, packed first
-// layer). variant: 0 = auto, 4 = force the generic kernel, 5 = force the halo kernel. (A ping-pong
-// 256 x 256 implicit-GEMM wgrad was built and measured 2x slower than the halo kernel: profiles/dead_ends.md.)
+// the fields WgradArgs, WgradHaloArgs and WgradRingArgs share
+template <class Args>
+static void wgrad_operands(Args& a, const RdpWgrad& g) {
+  a.x1 = (const u16*)g.x1; a.x2 = (const u16*)g.x2;
+  a.xbytes1 = (uint32_t)g.xbytes1; a.xbytes2 = (uint32_t)g.xbytes2;
+  a.C1 = g.C1; a.C2 = g.C2; a.pitch1 = g.pitch1; a.pitch2 = g.pitch2;
+  a.dy = (const u16*)g.dy; a.dybytes = (uint32_t)g.dybytes; a.dypitch = g.dypitch;
+  a.slab = g.slab; a.H = g.H; a.W = g.W; a.Cout = g.Cout;
+}
 
-extern "C" int rdp_conv_wgrad(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2, int pitch1,
-                              int pitch2, const void* dy, long dybytes, int dypitch, float* slab, long slab_elems,
-                              float* out, int accumulate, int N, int H, int W, int Cout, int taps, int packed,
-                              int cin_real, int splits, int variant, hipStream_t s) {
+// conv_wgrad_kernel's arguments for a plan of the generic family (GENERIC, PACKED, UPT)
+static WgradArgs wgrad_generic_args(const RdpWgrad& g, const RdpWgradPlan& p) {
   WgradArgs a;
-  a.x1 = (const u16*)x1; a.x2 = (const u16*)x2;
-  a.xbytes1 = (uint32_t)xbytes1; a.xbytes2 = (uint32_t)xbytes2;
-  a.C1 = C1; a.C2 = C2; a.pitch1 = pitch1; a.pitch2 = pitch2;
-  a.dy = (const u16*)dy; a.dybytes = (uint32_t)dybytes; a.dypitch = dypitch;
-  a.slab = slab; a.H = H; a.W = W; a.M = N * H * W; a.Cout = Cout;
-  a.taps = taps; a.packed = packed;
-  if (packed) {
-    if (C1 != 8 || C2 != 0 || taps != 9) return -1;
-    a.Cin = 8; a.ncols = 72;
-  } else {
-    if (C1 % 64 || C2 % 64) return -1;
-    a.Cin = C1 + C2; a.ncols = taps * a.Cin;
-  }
-  if (Cout % 64) return -1;
-  if (xbytes1 >= (1l << 31) || xbytes2 >= (1l << 31) || dybytes >= (1l << 31)) return -1;
-  // halo-reuse kernel: 3x3, whole 64-pixel row segments
-  const bool halo_ok = !packed && taps == 9 && (W % 64 == 0 || (W >= 32 && 64 % W == 0 && (H * W) % 64 == 0)) &&
-                       variant != 4;
-  if (variant == 5 && !(!packed && taps == 9 && (W % 64 == 0 || (W >= 8 && 64 % W == 0 && (H * W) % 64 == 0))))
-    return -1;
-  if (halo_ok || variant == 5) {
-    WgradHaloArgs h;
-    h.x1 = a.x1; h.x2 = a.x2; h.xbytes1 = a.xbytes1; h.xbytes2 = a.xbytes2;
-    h.C1 = C1; h.C2 = C2; h.pitch1 = pitch1; h.pitch2 = pitch2;
-    h.dy = a.dy; h.dybytes = a.dybytes; h.dypitch = dypitch;
-    h.slab = slab; h.H = H; h.W = W; h.Cout = Cout; h.ncols = 9 * a.Cin;
-    const int BN = Cout % 128 == 0 ? 128 : 64;
-    h.cinTiles = a.Cin / 64; h.coutTiles = Cout / BN;
-    const int tiles = h.cinTiles * h.coutTiles;
-    h.nseg = a.M / 64;
-    // one resident wave of blocks (2/CU at BN = 64, 1/CU at BN = 128), within the slab. (Other grid
-    // targets, a minimum segment count per split and the row ring at BN = 128 measured neutral.)
-    const int target = BN == 64 ? 512 : 256;
-    int sp = std::max(1, (target + tiles - 1) / tiles);
-    sp = std::min(sp, std::max(1, h.nseg));
-    const long per_split = (long)Cout * h.ncols;
-    sp = (int)std::min<long>(sp, slab_elems / per_split);
-    if (sp < 1) return -2;
-    h.segs_per_split = (h.nseg + sp - 1) / sp;
-    h.splits = (h.nseg + h.segs_per_split - 1) / h.segs_per_split;
-    if ((long)h.splits * per_split * 4l >= (1l << 31)) return -3;
-    h.slab_bytes = (uint32_t)(h.splits * per_split * 4l);
-    FastDiv fw = make_fastdiv(W), fh = make_fastdiv(H);
-    h.fw_m = fw.m; h.fw_s = fw.s; h.fh_m = fh.m; h.fh_s = fh.s;
-    const int nblk = tiles * h.splits;
-    if (variant == 0 && W % 64 == 0 && BN == 64) {  // row-ring variant: same split of the positions
-      WgradRingArgs g;
-      g.x1 = h.x1; g.x2 = h.x2; g.xbytes1 = h.xbytes1; g.xbytes2 = h.xbytes2;
-      g.C1 = C1; g.C2 = C2; g.pitch1 = pitch1; g.pitch2 = pitch2;
-      g.dy = h.dy; g.dybytes = h.dybytes; g.dypitch = dypitch;
-      g.slab = slab; g.slab_bytes = h.slab_bytes; g.H = H; g.W = W; g.Cout = Cout; g.ncols = h.ncols;
-      g.cinTiles = h.cinTiles; g.coutTiles = h.coutTiles; g.splits = h.splits;
-      g.pos_per_split = h.segs_per_split; g.npos = h.nseg; g.WS = W / 64;
-      FastDiv fs = make_fastdiv(W / 64);
-      g.fh_m = fh.m; g.fh_s = fh.s; g.fs_m = fs.m; g.fs_s = fs.s;
-      hipLaunchKernelGGL((conv_wgrad_ring_kernel<64>), dim3(nblk), dim3(256), 0, s, g);
-    } else {
-      const bool mr = W < 64;
-      if (BN == 128 && mr) hipLaunchKernelGGL((conv_wgrad_halo_kernel<128, true>), dim3(nblk), dim3(512), 0, s, h);
-      else if (BN == 128) hipLaunchKernelGGL((conv_wgrad_halo_kernel<128, false>), dim3(nblk), dim3(512), 0, s, h);
-      else if (mr) hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, true>), dim3(nblk), dim3(256), 0, s, h);
-      else hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, false>), dim3(nblk), dim3(256), 0, s, h);
+  wgrad_operands(a, g);
+  a.M = g.N * g.H * g.W; a.Cin = p.cin_pad;
+  a.taps = g.taps; a.packed = g.packed;
+  a.ncols = p.ncols; a.ncols_pad = p.ncols_pad;
+  a.colTiles = p.ncols_pad / 256; a.coutTiles = g.Cout / 64;
+  a.splits = p.splits; a.pix_per_split = p.per_split;
+  const FastDiv fw = make_fastdiv(g.W), fh = make_fastdiv(g.H);
+  a.fw_m = fw.m; a.fw_s = fw.s; a.fh_m = fh.m; a.fh_s = fh.s;
+  return a;
+}
+
+int rdp_conv_wgrad(const RdpWgrad& g, int kernel, int splits, hipStream_t s) {
+  const RdpWgradPlan p = rdp_wgrad_plan(g, kernel, splits);
+  if (p.status != RDP_WGRAD_OK) return p.status;
+  const FastDiv fw = make_fastdiv(g.W), fh = make_fastdiv(g.H);
+  switch (p.kernel) {
+    case RDP_WGRAD_RING: {
+      WgradRingArgs a;
+      wgrad_operands(a, g);
+      a.slab_bytes = (uint32_t)(p.slab_elems * 4); a.ncols = p.ncols;
+      a.cinTiles = p.cin_pad / 64; a.coutTiles = g.Cout / p.BN; a.splits = p.splits;
+      a.pos_per_split = p.per_split; a.npos = g.N * g.H * g.W / 64; a.WS = g.W / 64;
+      const FastDiv fs = make_fastdiv(g.W / 64);
+      a.fh_m = fh.m; a.fh_s = fh.s; a.fs_m = fs.m; a.fs_s = fs.s;
+      hipLaunchKernelGGL((conv_wgrad_ring_kernel<64>), dim3(p.grid), dim3(p.block), 0, s, a);
+      break;
     }
-    rdp_wgrad_reduce(slab, out, h.splits, Cout, h.ncols, 9, a.Cin, a.Cin, accumulate, s);
-    return h.splits;
+    case RDP_WGRAD_HALO: {
+      WgradHaloArgs a;
+      wgrad_operands(a, g);
+      a.slab_bytes = (uint32_t)(p.slab_elems * 4); a.ncols = p.ncols;
+      a.cinTiles = p.cin_pad / 64; a.coutTiles = g.Cout / p.BN; a.splits = p.splits;
+      a.segs_per_split = p.per_split; a.nseg = g.N * g.H * g.W / 64;
+      a.fw_m = fw.m; a.fw_s = fw.s; a.fh_m = fh.m; a.fh_s = fh.s;
+      if (p.BN == 128 && p.multirow) hipLaunchKernelGGL((conv_wgrad_halo_kernel<128, true>), dim3(p.grid), dim3(p.block), 0, s, a);
+      else if (p.BN == 128) hipLaunchKernelGGL((conv_wgrad_halo_kernel<128, false>), dim3(p.grid), dim3(p.block), 0, s, a);
+      else if (p.multirow) hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, true>), dim3(p.grid), dim3(p.block), 0, s, a);
+      else hipLaunchKernelGGL((conv_wgrad_halo_kernel<64, false>), dim3(p.grid), dim3(p.block), 0, s, a);
+      break;
+    }
+    case RDP_WGRAD_PACKED:
+      hipLaunchKernelGGL((conv_wgrad_kernel<true>), dim3(p.grid), dim3(p.block), 0, s, wgrad_generic_args(g, p));
+      break;
+    case RDP_WGRAD_GENERIC:
+      hipLaunchKernelGGL((conv_wgrad_kernel<false>), dim3(p.grid), dim3(p.block), 0, s, wgrad_generic_args(g, p));
+      break;
+    default: return RDP_WGRAD_NO_FIT;
   }
-  a.colTiles = (a.ncols + 255) / 256;
-  a.ncols_pad = a.colTiles * 256;
-  a.coutTiles = Cout / 64;
-  if (splits < 1) splits = 1;
-  int pps = (a.M + splits - 1) / splits;
-  pps = (pps + 63) / 64 * 64;
-  a.pix_per_split = pps;
-  a.splits = (a.M + pps - 1) / pps;
-  if ((long)a.splits * Cout * a.ncols_pad > slab_elems) return -2;
-  if ((long)a.splits * Cout * a.ncols_pad * 4l >= (1l << 31)) return -3;
-  FastDiv fw = make_fastdiv(W), fh = make_fastdiv(H);
-  a.fw_m = fw.m; a.fw_s = fw.s; a.fh_m = fh.m; a.fh_s = fh.s;
-  const int nblk = a.colTiles * a.coutTiles * a.splits;
-  if (packed) hipLaunchKernelGGL((conv_wgrad_kernel<true>), dim3(nblk), dim3(512), 0, s, a);
-  else hipLaunchKernelGGL((conv_wgrad_kernel<false>), dim3(nblk), dim3(512), 0, s, a);
-  rdp_wgrad_reduce(slab, out, a.splits, Cout, a.ncols_pad, taps, packed ? 8 : a.Cin, packed ? cin_real : a.Cin,
-                   accumulate, s);
-  return a.splits;
+  rdp_wgrad_reduce(g, p, s);
+  return p.splits;
 }
 
-extern "C" int rdp_conv_wgrad_upT(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
-                                  const void* x, long xbytes, int Cin, int xpitch, int N, int h, int w, float* slab,
-                                  long slab_elems, float* out, int accumulate, int splits, hipStream_t s) {
-  if (C % 64 || Cin % 64 || oy < 0 || ox < 0 || 2 * h + oy > H2 || 2 * w + ox > W2) return -1;
-  if (dubytes >= (1l << 31) || xbytes >= (1l << 31)) return -1;
-  WgradArgs a;
-  a.x1 = (const u16*)du; a.x2 = nullptr; a.xbytes1 = (uint32_t)dubytes; a.xbytes2 = 0;
-  a.C1 = C; a.C2 = 0; a.pitch1 = dupitch; a.pitch2 = dupitch;
-  a.dy = (const u16*)x; a.dybytes = (uint32_t)xbytes; a.dypitch = xpitch;
-  a.slab = slab; a.H = h; a.W = w; a.M = N * h * w; a.Cout = Cin;
-  a.taps = 4; a.packed = 0; a.Cin = C; a.ncols = 4 * C;
-  a.uH2 = H2; a.uW2 = W2; a.uoy = oy; a.uox = ox;
-  a.colTiles = (a.ncols + 255) / 256;
-  a.ncols_pad = a.colTiles * 256;
-  a.coutTiles = Cin / 64;
-  if (splits < 1) splits = 1;
-  int pps = (a.M + splits - 1) / splits;
-  pps = (pps + 63) / 64 * 64;
-  a.pix_per_split = pps;
-  a.splits = (a.M + pps - 1) / pps;
-  if ((long)a.splits * a.Cout * a.ncols_pad > slab_elems) return -2;
-  if ((long)a.splits * a.Cout * a.ncols_pad * 4l >= (1l << 31)) return -3;
-  FastDiv fw = make_fastdiv(w), fh = make_fastdiv(h);
-  a.fw_m = fw.m; a.fw_s = fw.s; a.fh_m = fh.m; a.fh_s = fh.s;
-  const int nblk = a.colTiles * a.coutTiles * a.splits;
-  hipLaunchKernelGGL((conv_wgrad_kernel<false, true>), dim3(nblk), dim3(512), 0, s, a);
-  rdp_wgrad_reduce(slab, out, a.splits, Cin, a.ncols_pad, 4, C, C, accumulate, s);
-  return a.splits;
+int rdp_conv_wgrad_upT(const RdpWgrad& g, const RdpUpT& t, int splits, hipStream_t s) {
+  const RdpWgradPlan p = rdp_wgrad_plan(g, RDP_WGRAD_AUTO, splits, t);
+  if (p.status != RDP_WGRAD_OK) return p.status;
+  WgradArgs a = wgrad_generic_args(g, p);
+  a.pitch2 = g.pitch1;
+  a.uH2 = t.H2; a.uW2 = t.W2; a.uoy = t.oy; a.uox = t.ox;
+  hipLaunchKernelGGL((conv_wgrad_kernel<false, true>), dim3(p.grid), dim3(p.block), 0, s, a);
+  rdp_wgrad_reduce(g, p, s);
+  return p.splits;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -901,7 +845,7 @@ struct FirstWgradArgs {
   int H, W, M, pix_per_split;
   uint32_t fw_m, fw_s, fh_m, fh_s;
 };
-constexpr int FWG_NCOLS = 80;
+constexpr int FWG_NCOLS = RDP_WGRAD_FIRST_NCOLS;
 
 RDP_DEV void fw_unpack8(const uint4& v, float* f) {
   const uint32_t w[4] = {v.x, v.y, v.z, v.w};
@@ -1038,53 +982,20 @@ __global__ __launch_bounds__(256, 2) void wgrad_first_bn_kernel(const FirstWgrad
   }
 }
 
-extern "C" int rdp_wgrad_first_bn(const void* x, long xbytes, int xpitch, const void* da, long dabytes, int dapitch,
-                                  const void* y, long ybytes, int ypitch, const float* coef, const float* coef2,
-                                  float* slab, long slab_elems, float* out, int accumulate, int N, int H, int W,
-                                  int cin_real, int splits, hipStream_t s) {
-  const long M = (long)N * H * W;
-  if (M % 64 || cin_real > 8 || cin_real < 1) return -1;
-  if (xbytes >= (1l << 31) || dabytes >= (1l << 31) || ybytes >= (1l << 31)) return -1;
-  if (xpitch % 8 || dapitch % 8 || ypitch % 8) return -1;
-  splits = (int)std::max(1L, std::min<long>(splits, M / 64));
-  long pps = (M + splits - 1) / splits;
-  pps = (pps + 63) / 64 * 64;
-  splits = (int)((M + pps - 1) / pps);
-  const long per_split = 64l * FWG_NCOLS;
-  if ((long)splits * per_split > slab_elems) return -2;
-  if ((long)splits * per_split * 4l >= (1l << 31)) return -3;
+int rdp_wgrad_first_bn(const RdpWgrad& g, const RdpWgradBn& bn, int splits, hipStream_t s) {
+  const RdpWgradPlan p = rdp_wgrad_plan(g, RDP_WGRAD_AUTO, splits, RdpUpT{}, bn);
+  if (p.status != RDP_WGRAD_OK) return p.status;
   FirstWgradArgs a;
-  a.x = (const u16*)x; a.xbytes = (uint32_t)xbytes; a.xpitch = xpitch;
-  a.da = (const u16*)da; a.dabytes = (uint32_t)dabytes; a.dapitch = dapitch;
-  a.y = (const u16*)y; a.ybytes = (uint32_t)ybytes; a.ypitch = ypitch;
-  a.coef = coef; a.coef2 = coef2;
-  a.slab = slab; a.slab_bytes = (uint32_t)(splits * per_split * 4l);
-  a.H = H; a.W = W; a.M = (int)M; a.pix_per_split = (int)pps;
-  FastDiv fw = make_fastdiv(W), fh = make_fastdiv(H);
+  a.x = (const u16*)g.x1; a.xbytes = (uint32_t)g.xbytes1; a.xpitch = g.pitch1;
+  a.da = (const u16*)bn.da; a.dabytes = (uint32_t)bn.dabytes; a.dapitch = bn.dapitch;
+  a.y = (const u16*)bn.y; a.ybytes = (uint32_t)bn.ybytes; a.ypitch = bn.ypitch;
+  a.coef = bn.coef; a.coef2 = bn.coef2;
+  a.slab = g.slab; a.slab_bytes = (uint32_t)(p.slab_elems * 4);
+  a.H = g.H; a.W = g.W; a.M = g.N * g.H * g.W; a.pix_per_split = p.per_split;
+  const FastDiv fw = make_fastdiv(g.W), fh = make_fastdiv(g.H);
   a.fw_m = fw.m; a.fw_s = fw.s; a.fh_m = fh.m; a.fh_s = fh.s;
-  hipLaunchKernelGGL(wgrad_first_bn_kernel, dim3(splits), dim3(256), 0, s, a);
-  rdp_wgrad_reduce(slab, out, splits, 64, FWG_NCOLS, 9, 8, cin_real, accumulate, s);
-  return splits;
+  hipLaunchKernelGGL(wgrad_first_bn_kernel, dim3(p.grid), dim3(p.block), 0, s, a);
+  rdp_wgrad_reduce(g, p, s);
+  return p.splits;
 }
 
-extern "C" long rdp_conv_wgrad_slab_elems(int N, int H, int W, int Cin, int Cout, int taps, int packed, int splits) {
-  const int ncols = packed ? 72 : taps * Cin;
-  const int ncols_pad = (ncols + 255) / 256 * 256;
-  const long M = (long)N * H * W;
-  long pps = (M + splits - 1) / splits;
-  pps = (pps + 63) / 64 * 64;
-  const long sp = (M + pps - 1) / pps;
-  return sp * Cout * ncols_pad;
-}
-
-extern "C" long rdp_conv_wgrad_halo_slab_elems(int N, int H, int W, int Cin, int Cout) {
-  const long M = (long)N * H * W;
-  const bool halo = Cin % 64 == 0 && Cout % 64 == 0 && (W % 64 == 0 || (W >= 32 && 64 % W == 0 && (H * W) % 64 == 0));
-  if (!halo) return 0;
-  const int BN = Cout % 128 == 0 ? 128 : 64;
-  const long tiles = (long)(Cin / 64) * (Cout / BN);
-  const long target = BN == 64 ? 512 : 256;
-  long hsp = std::max<long>(1, (target + tiles - 1) / tiles);
-  hsp = std::min<long>(hsp, std::max<long>(1, M / 64));
-  return hsp * Cout * 9L * Cin;
-}

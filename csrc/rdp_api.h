@@ -6,7 +6,8 @@
 
 #include "rdp_host_api.h"
 
-// The conv family's operand blocks (RdpConv, RdpConvFuse, RdpConvBnBwd, RdpRingFuse), the kernel names and the plan
+// The conv family's operand blocks (RdpConv, RdpConvFuse, RdpConvBnBwd, RdpRingFuse, RdpWgrad, RdpWgradBn, RdpUpT), the
+// kernel names and the plans
 #include "conv_plan.h"
 
 extern "C" {
@@ -26,23 +27,20 @@ int rdp_conv_first(const RdpConv& c, hipStream_t s);
 int rdp_conv_halo(const RdpConv& c, hipStream_t s);
 
 // ---- csrc/conv_igemm.hip --------------------------------------------------------------------------------------
-// ConvTranspose2d(k=2, s=2) + bias straight into its (padded) output map u [N][H2][W2][upitch]: the
+// ConvTranspose2d(k=2, s=2) + bias straight into its (padded) output map u [N][t.H2][t.W2][ypitch1]: the
 // 1x1 GEMM yT[px][sub * C + c] = sum_ci x[px][ci] Wt[sub * C + c][ci] on the ping-pong kernel with the
-// sub-pixel scatter + bias in its epilogue (no yT round trip and no upT_shuffle pass). u's border
-// outside the 2h x 2w window at (oy, ox) is not written (the caller zeroes it once). Returns 0, or -1
-// where the ping-pong grid would not fill the chip / the shape does not fit (the caller then runs the
-// GEMM + upT_shuffle).
-int rdp_conv_upT_fwd(const void* x, long xbytes, int Cin, int pitch, const void* w, long wbytes, int ldw, void* u,
-                     long ubytes, int upitch, const float* bias, int N, int h, int wd, int H2, int W2, int oy,
-                     int ox, int C, hipStream_t s);
-// ConvTranspose2d(k=2, s=2) input gradient straight from the output gradient du [N][H2][W2][C] (the
-// window 2h x 2w at (oy, ox)): dx[px][ci] = sum_(sub, c) du[sub-pixel sub of px][c] Wd[ci][sub * C + c]
+// sub-pixel scatter + bias in its epilogue (no yT round trip and no upT_shuffle pass). c: x1 = x, w = Wt,
+// y1 = u, Cout = 4C, N / H / W = the low-res map (rdp_upT_fwd_geo). u's border outside the 2h x 2w window at
+// (t.oy, t.ox) is not written (the caller zeroes it once). Returns 0, or -1 where the ping-pong grid would not
+// fill the chip / the shape does not fit (the caller then runs the GEMM + upT_shuffle).
+int rdp_conv_upT_fwd(const RdpConv& c, const RdpUpT& t, const float* bias, hipStream_t s);
+// ConvTranspose2d(k=2, s=2) input gradient straight from the output gradient du [N][t.H2][t.W2][C] (the
+// window 2h x 2w at (t.oy, t.ox)): dx[px][ci] = sum_(sub, c) du[sub-pixel sub of px][c] Wd[ci][sub * C + c]
 // on the ping-pong kernel, its A operand DMA'd from the 4 sub-pixels as 4 "taps" (no unshuffled copy
-// of du). wd = the [Cin][4C] dgrad weight. Returns 0, or -1 where the ping-pong grid would not fill
-// the chip / the shape does not fit (the caller unshuffles and runs the 1x1 GEMM).
-int rdp_conv_upT_dgrad(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
-                       const void* wd, long wbytes, int ldw, void* dx, long dxbytes, int Cin, int dxpitch, int N,
-                       int h, int wdt, hipStream_t s);
+// of du). c: x1 = du, w = the [Cin][4C] dgrad weight, y1 = dx, Cout = Cin, N / H / W = the low-res map
+// (rdp_upT_dgrad_geo). Returns 0, or -1 where the ping-pong grid would not fill the chip / the shape does not
+// fit (the caller unshuffles and runs the 1x1 GEMM).
+int rdp_conv_upT_dgrad(const RdpConv& c, const RdpUpT& t, hipStream_t s);
 // The conv dispatcher: launches what rdp_conv_plan (conv_plan.h) picks. Returns the number of stats-slab rows
 // written, or -1 (nothing launched) where the plan is unsupported. kernel: RDP_CONV_AUTO, or the RdpConvKernel to
 // force. ws: the split-K fp32 slab of ws_elems elements (rdp_conv_ws_elems), or nullptr. wfrag / wfrag_bytes: the
@@ -96,35 +94,21 @@ int rdp_conv_rowband_chain(int nl, const void* x, long xbytes, int C0, int xpitc
                            const float* const* eshift, int N, int H, int W, int* cnt, int* err, hipStream_t s);
 
 // ---- csrc/conv_wgrad.hip --------------------------------------------------------------------------------------
-void rdp_wgrad_reduce(float* slab, float* out, int splits, int Cout, int ncols_pad, int taps, int cin_pad,
-                      int cin_real, int accumulate, hipStream_t s);
-int rdp_conv_wgrad(const void* x1, const void* x2, long xbytes1, long xbytes2, int C1, int C2, int pitch1,
-                   int pitch2, const void* dy, long dybytes, int dypitch, float* slab, long slab_elems, float* out,
-                   int accumulate, int N, int H, int W, int Cout, int taps, int packed, int cin_real, int splits,
-                   int variant, hipStream_t s);
-// ConvTranspose2d(k=2, s=2) weight gradient straight from its output gradient du [N][H2][W2][C] (the
-// window 2h x 2w at (oy, ox)) and its input x [N][h][w][Cin]: out[ci][(sub, c)] (+)= sum_px
+// Each launches what rdp_wgrad_plan (conv_plan.h) says, then the slab reduce into g.out, and returns the split
+// count, or an RdpWgradStatus < 0 (nothing launched). Slab sizing: rdp_conv_wgrad_slab_elems and
+// rdp_conv_wgrad_halo_slab_elems, declared with the plan.
+// kernel: RDP_WGRAD_AUTO, GENERIC or HALO; splits: asked of the generic kernels (the halo / ring kernels choose)
+int rdp_conv_wgrad(const RdpWgrad& g, int kernel, int splits, hipStream_t s);
+// ConvTranspose2d(k=2, s=2) weight gradient straight from its output gradient du [N][t.H2][t.W2][C] (the
+// window 2h x 2w at (t.oy, t.ox)) and its input x [N][h][w][Cin]: out[ci][(sub, c)] (+)= sum_px
 // x[px][ci] du[sub-pixel sub of px][c] -- the generic kernel's role-swapped GEMM (columns = the 4
 // sub-pixels x C, "couts" = Cin) reading du at the sub-pixels instead of an unshuffled copy.
-// Returns the split count, or < 0 if the shape does not fit.
-int rdp_conv_wgrad_upT(const void* du, long dubytes, int C, int dupitch, int H2, int W2, int oy, int ox,
-                       const void* x, long xbytes, int Cin, int xpitch, int N, int h, int w, float* slab,
-                       long slab_elems, float* out, int accumulate, int splits, hipStream_t s);
-// Returns the number of splits, or < 0 (nothing launched) when the shape does not fit this kernel.
-int rdp_wgrad_first_bn(const void* x, long xbytes, int xpitch, const void* da, long dabytes, int dapitch,
-                       const void* y, long ybytes, int ypitch, const float* coef, const float* coef2, float* slab,
-                       long slab_elems, float* out, int accumulate, int N, int H, int W, int cin_real, int splits,
-                       hipStream_t s);
-// Slab size (elements) for the generic kernel's `splits` pixel splits. The halo / row-ring kernels choose
-// their own split count, capped by the slab they are given: the training step shares one slab of the
-// largest generic size, which caps the deep layers' halo wgrads at 4-15 splits (~120 blocks). That is
-// deliberate: sized for a full wave of halo blocks (rdp_conv_wgrad_halo_slab_elems) the wgrads run ~1.8x
-// faster alone but the step got slower -- bs 64 3,120-3,131 vs 3,160-3,181 img/s, bs 4 1,405-1,409 vs
-// 1,591 (same box, 2 rounds): the side-stream wgrads then take every CU from the main stream's convs.
-long rdp_conv_wgrad_slab_elems(int N, int H, int W, int Cin, int Cout, int taps, int packed, int splits);
-// Slab the halo / row-ring wgrad needs for one resident wave of blocks (its own split choice
-// unconstrained); 0 where the dispatch does not pick those kernels. (conv_microbench.py sizes with it.)
-long rdp_conv_wgrad_halo_slab_elems(int N, int H, int W, int Cin, int Cout);
+// g: x1 = du (C1 = C), dy = x, Cout = Cin, taps = 4, N / H / W = the low-res map.
+int rdp_conv_wgrad_upT(const RdpWgrad& g, const RdpUpT& t, int splits, hipStream_t s);
+// The first layer with its BN backward applied on the fly. g: x1 = the packed 8-channel input, no dy.
+int rdp_wgrad_first_bn(const RdpWgrad& g, const RdpWgradBn& bn, int splits, hipStream_t s);
+// The two-level reduce of a planned weight gradient's slab g.slab into g.out (p.reduce)
+void rdp_wgrad_reduce(const RdpWgrad& g, const RdpWgradPlan& p, hipStream_t s);
 
 // ---- csrc/data_kernels.hip ------------------------------------------------------------------------------------
 // exactly one of tgt_f (one-class: fp32 mask value) / tgt_u (K-class: u8 id, 255 outside the frame) is set

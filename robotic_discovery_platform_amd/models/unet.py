@@ -755,26 +755,22 @@ class UNetExecutor:
         # wgrad split-K choice + shared slab (one grid target for every layer: giving the first encoder
         # level -- the last side-stream work of the step -- the wide 2048-block grid to shorten the
         # tail measured 1.3% slower, 2900 / 2909 vs 2938 / 2950 img/s at bs64)
-        slab = 0
+        def split_slab(shape, cin, cout, taps, packed):
+            """The generic kernel's splits for the grid target and the slab they need (csrc/conv_plan.h)."""
+            n, h, w, _ = shape
+            sp_ = C.wgrad_auto_splits(n, h, w, cin, cout, taps, packed, self.wgrad_blocks)
+            return sp_, C.wgrad_slab_elems(n, h, w, cin, cout, taps, packed, sp_)
+
+        slabs = []
         for L in self.layers:
-            n, h, w, _ = L.x1.shape
-            M = n * h * w
-            cin = L.spec.cin if not L.spec.packed else 8
-            ncols = 72 if L.spec.packed else L.spec.taps * cin
-            tiles = ((ncols + 255) // 256) * (L.spec.cout // 64)
-            L.splits = int(max(1, min((self.wgrad_blocks + tiles - 1) // tiles, M // 2048)))
-            slab = max(slab, C.wgrad_slab_elems(n, h, w, cin, L.spec.cout, L.spec.taps, int(L.spec.packed), L.splits))
+            L.splits, e = split_slab(L.x1.shape, 8 if L.spec.packed else L.spec.cin, L.spec.cout, L.spec.taps,
+                                     int(L.spec.packed))
+            slabs.append(e)
         self.dyTs: List[torch.Tensor] = [like(y) for y in self.yTs]
-        self.upT_splits: List[int] = []
-        for i, us in enumerate(self.m.up_specs):
-            n, h, w, _ = self.yTs[i].shape
-            M = n * h * w
-            tiles = ((4 * us.cout + 255) // 256) * (us.cin // 64)
-            sp_ = int(max(1, min((self.wgrad_blocks + tiles - 1) // tiles, max(1, M // 2048))))
-            self.upT_splits.append(sp_)
-            # roles swapped in conv_wgrad: "x" = dyT (4*cout ch), "dy" = the ConvT input (cin ch)
-            slab = max(slab, C.wgrad_slab_elems(n, h, w, 4 * us.cout, us.cin, 1, 0, sp_))
-        self.slab = torch.zeros(slab, dtype=torch.float32, device=dev)
+        # roles swapped in conv_wgrad: "x" = dyT (4*cout ch), "dy" = the ConvT input (cin ch)
+        ups = [split_slab(self.yTs[i].shape, 4 * us.cout, us.cin, 1, 0) for i, us in enumerate(self.m.up_specs)]
+        self.upT_splits: List[int] = [s for s, _ in ups]
+        self.slab = torch.zeros(max(slabs + [e for _, e in ups]), dtype=torch.float32, device=dev)
         # The first layer's wgrad is the step's last gradient; the side stream is still working off
         # its backlog then while the main stream idles, so it runs on the main stream with its own slab
         # (moving the second-to-last layer's wgrad there too measured 1.3 % slower)
@@ -1212,7 +1208,8 @@ class UNetExecutor:
                 r = C.wgrad_first_bn(L.x1, L.da, L.y, L.coef, L.coef2, slab, gw, sp.cin_real, 0, L.splits)
                 if r < 0:  # shape outside the kernel (e.g. tensors past 2 GiB): separate passes
                     C.bn_relu_bwd_apply(L.da, L.y, L.coef, L.coef2, L.dy, 1)
-                    C.conv_wgrad(L.x1, L.x2, L.dy, sp.taps, int(sp.packed), sp.cin_real, slab, gw, 0, L.splits, 0)
+                    C.conv_wgrad(L.x1, L.x2, L.dy, sp.taps, int(sp.packed), sp.cin_real, slab, gw, 0, L.splits,
+                                 C.WGRAD_AUTO)
 
             if self.slab_main is not None:
                 fused(self.slab_main)
@@ -1228,11 +1225,12 @@ class UNetExecutor:
         # all wgrads share the slab, so they stay serialized on the one side stream
         wstream = self.side if self.side is not None else main
         if self.slab_main is not None and L is self.down_layers[0][0]:
-            C.conv_wgrad(L.x1, L.x2, L.dy, sp.taps, int(sp.packed), sp.cin_real, self.slab_main, gw, 0, L.splits, 0)
+            C.conv_wgrad(L.x1, L.x2, L.dy, sp.taps, int(sp.packed), sp.cin_real, self.slab_main, gw, 0, L.splits,
+                         C.WGRAD_AUTO)
             wstream = main
         else:
             self._on_wgrad_stream(lambda slab: C.conv_wgrad(L.x1, L.x2, L.dy, sp.taps, int(sp.packed), sp.cin_real,
-                                                            slab, gw, 0, L.splits, 0))
+                                                            slab, gw, 0, L.splits, C.WGRAD_AUTO))
         # dgrad into the da of a BN layer: where the row-ring kernel runs it (64 -> 64 channels), its
         # epilogue also produces that layer's BN-backward partial sums (no bn_relu_bwd_reduce pass)
         owner = L.dx1_owner
@@ -1344,7 +1342,7 @@ class UNetExecutor:
                     C.upT_unshuffle(du, dyT, oy, ox)
                     C.colsum_bf16(dyT, 4, self.colsum_ws, bgrad, 0)
                     self._on_wgrad_stream(lambda slab, dyT=dyT, xa=low_layer.a, us=us, ns=ns, g=wgrad:
-                                          C.conv_wgrad(dyT, None, xa, 1, 0, 4 * us.cout, slab, g, 0, ns, 0))
+                                          C.conv_wgrad(dyT, None, xa, 1, 0, 4 * us.cout, slab, g, 0, ns, C.WGRAD_AUTO))
                     C.conv_fwd(dyT, None, self.m.upT_dgrad_weight(us), 1, 0, low_layer.da, None, None, C.CONV_AUTO,
                                None, 0, self.kws)
                 if grad_hook is not None:  # bias (main) + weight (side, forked after the bias)

@@ -28,7 +28,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--variants", default="AUTO,HALO",
-                    help="conv kernels by name (the extension's CONV_<name>) or number; 9 / 10: the BN-on-input ring")
+                    help="kernels by name (the extension's CONV_<name>; with --wgrad WGRAD_<name>: AUTO, GENERIC, "
+                         "HALO) or number; 9 / 10: the BN-on-input ring")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--wgrad", action="store_true")
@@ -41,7 +42,8 @@ def main():
     a = ap.parse_args()
     C = native()
     dev = torch.device("cuda")
-    variants = [int(v) if v.isdigit() else getattr(C, "CONV_" + v.upper()) for v in a.variants.split(",")]
+    variants = [int(v) if v.isdigit() else getattr(C, ("WGRAD_" if a.wgrad else "CONV_") + v.upper())
+                for v in a.variants.split(",")]
     results = []
     shapes = SHAPES if a.shapes is None else [SHAPES[int(i)] for i in a.shapes.split(",")]
     for (H, C1, C2, Co) in shapes:
@@ -60,10 +62,9 @@ def main():
             ws = torch.zeros(max(n_ws, 1), device=dev) if n_ws else None
         if a.wgrad:
             dy = torch.randn(N, H, H, Co, device=dev).to(torch.bfloat16)
-            tiles = ((9 * Cin + 255) // 256) * (Co // 64)
-            splits = max(1, min((a.wgrad_blocks + tiles - 1) // tiles, N * H * H // 2048))
+            splits = C.wgrad_auto_splits(N, H, H, Cin, Co, 9, 0, a.wgrad_blocks)
             # sized for the halo kernel's own full-occupancy split choice too (the training step gives it
-            # less on purpose: csrc/conv_wgrad.hip rdp_conv_wgrad_slab_elems)
+            # less on purpose: csrc/conv_plan.h rdp_conv_wgrad_slab_elems)
             slab = torch.zeros(max(C.wgrad_slab_elems(N, H, H, Cin, Co, 9, 0, splits),
                                    C.wgrad_halo_slab_elems(N, H, H, Cin, Co) if a.halo_slab else 0), device=dev)
             out = torch.zeros(Co * 9 * Cin, device=dev)
@@ -76,7 +77,7 @@ def main():
         a_st = torch.empty_like(x1)
 
         def run(v):
-            if a.wgrad:  # v = variant (0 auto, 4 generic, 5 halo)
+            if a.wgrad:  # v = C.WGRAD_AUTO / GENERIC / HALO
                 C.conv_wgrad(x1, x2, dy, 9, 0, 0, slab, out, 0, splits, v)
             elif v in (9, 10):  # 10: BN-on-input forward that also stores the activation
                 if C.conv_fwd_bnin(x1, w, y, stats, coef, a_st if v == 10 else None) <= 0:

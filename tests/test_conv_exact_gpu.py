@@ -221,25 +221,33 @@ def test_conv_dgrad_bnred_exact(C, b):
 # 4. weight gradients
 # ---------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("c", L.WGRAD_CASES, ids=lambda c: c.name)
-def test_conv_wgrad_exact(C, c):
-    """conv_wgrad (auto / generic / halo, split counts 1 .. 512, every layout regime, dual source, packed
-    first layer, accumulate): the fp32 result equals the fp64 autograd weight gradient exactly."""
+def _wgrad_plan(C, c, slab_elems):
+    """What the plan says conv_wgrad will run for lattice case c on a slab of slab_elems."""
+    return C.wgrad_plan(c.N, c.H, c.W, 8 if c.packed else c.C1, c.C2, c.Cout, taps=9, packed=int(c.packed),
+                        cin_real=3 if c.packed else 0, kernel=c.variant, splits=c.splits, slab_elems=slab_elems)
+
+
+def _slab(used, tail=0):
+    """NaN where the launch may write (every slab element the reduce reads was written by the gradient kernel of
+    the same call -- each split stores its whole [Cout][ncols] tile -- so NaN shows a read before the write), then
+    `tail` sentinel floats it must leave alone. Returns (the slab to pass, the tail)."""
+    buf = torch.full((used + tail,), NAN, device=DEV)
+    buf[used:] = L.SENTINEL
+    return buf[:used], buf[used:]
+
+
+def _run_wgrad(C, c, slab):
     x, dy, dw = L.wgrad_data(c)
     M = c.N * c.H * c.W
     L.check_wgrad_ref(dw, M)
     if c.packed:
         x8 = torch.zeros(c.N, c.H, c.W, 8, dtype=L.BF16)
         x8[..., :3] = x
-        x1, x2, cin = _inp(x8, c.views, (8, 0)), None, 8
+        x1, x2 = _inp(x8, c.views, (8, 0)), None
     else:
         x1 = _inp(x[..., :c.C1].contiguous(), c.views)
         x2 = _inp(x[..., c.C1:].contiguous(), c.views, (8, 16)) if c.C2 else None
-        cin = c.C1 + c.C2
     d = _inp(dy, c.views, (24, 8))
-    # every slab element the reduce reads was written by the gradient kernel of the same call (each split
-    # stores its whole [Cout][ncols] tile): NaN here shows that nothing is read before it is written
-    slab = torch.full((C.wgrad_slab_elems(c.N, c.H, c.W, cin, c.Cout, 9, int(c.packed), c.splits),), NAN, device=DEV)
     if c.accumulate:
         init = L.wgrad_init(dw.numel(), c.seed)
         out, exp = init.to(DEV), (dw + init.double()).float()
@@ -249,21 +257,26 @@ def test_conv_wgrad_exact(C, c):
                      int(c.accumulate), c.splits, c.variant)
     torch.cuda.synchronize()
     assert r > 0
+    assert r == _wgrad_plan(C, c, slab.numel())["splits"]
     assert torch.equal(out.cpu(), exp)
     _check_inputs(x1, x2, d)
 
 
-@pytest.mark.parametrize("c", L.FIRSTBN_CASES, ids=lambda c: c.name)
-def test_wgrad_first_bn_exact(C, c):
-    """wgrad_first_bn forms dz = A * g + B * y + Cc (g = da * [scale * y + shift > 0]) in registers; with
-    A = +-2^k and small integer B, Cc on ternary da / y, dz is exact in bf16 and the weight gradient must
-    equal the fp64 gradient of that dz exactly."""
+@pytest.mark.parametrize("c", L.WGRAD_CASES, ids=lambda c: c.name)
+def test_conv_wgrad_exact(C, c):
+    """conv_wgrad (auto / generic / halo, split counts 1 .. 512, every layout regime, dual source, packed
+    first layer, accumulate): the fp32 result equals the fp64 autograd weight gradient exactly, on the split count
+    the plan states."""
+    cin = 8 if c.packed else c.C1 + c.C2
+    _run_wgrad(C, c, _slab(C.wgrad_slab_elems(c.N, c.H, c.W, cin, c.Cout, 9, int(c.packed), c.splits))[0])
+
+
+def _run_first_bn(C, c, slab):
     x, da, y, coef, coef2, dz, dw = L.firstbn_data(c)
     L.check_firstbn_case(dz, dw)
     x8 = torch.zeros(c.N, c.H, c.W, 8, dtype=L.BF16)
     x8[..., :3] = x
     bx, bda, by = _inp(x8, c.views, (8, 0)), _inp(da, c.views), _inp(y, c.views, (24, 8))
-    slab = torch.full((C.wgrad_slab_elems(c.N, c.H, c.W, 8, 64, 9, 1, c.splits),), NAN, device=DEV)
     if c.accumulate:
         init = L.wgrad_init(dw.numel(), c.seed)
         out, exp = init.to(DEV), (dw + init.double()).float()
@@ -272,13 +285,64 @@ def test_wgrad_first_bn_exact(C, c):
     r = C.wgrad_first_bn(bx.t, bda.t, by.t, coef.to(DEV), coef2.to(DEV), slab, out, 3, int(c.accumulate), c.splits)
     torch.cuda.synchronize()
     assert r >= 1
+    assert r == _first_bn_plan(C, c, slab.numel())["splits"]
     assert torch.equal(out.cpu(), exp)
     _check_inputs(bx, bda, by)
+
+
+def _first_bn_plan(C, c, slab_elems):
+    return C.wgrad_plan(c.N, c.H, c.W, 8, 0, 64, packed=1, cin_real=3, splits=c.splits, slab_elems=slab_elems,
+                        first_bn=True)
+
+
+@pytest.mark.parametrize("c", L.FIRSTBN_CASES, ids=lambda c: c.name)
+def test_wgrad_first_bn_exact(C, c):
+    """wgrad_first_bn forms dz = A * g + B * y + Cc (g = da * [scale * y + shift > 0]) in registers; with
+    A = +-2^k and small integer B, Cc on ternary da / y, dz is exact in bf16 and the weight gradient must
+    equal the fp64 gradient of that dz exactly."""
+    _run_first_bn(C, c, _slab(C.wgrad_slab_elems(c.N, c.H, c.W, 8, 64, 9, 1, c.splits))[0])
+
+
+def _case(cases, name):
+    return next(c for c in cases if c.name == name)
+
+
+# one case per weight-gradient code path: ring, halo<64>, halo<128, multirow>, generic with two sources, packed
+SLAB_CASES = ["w64-ring-v0", "w64-halo-v5-acc", "w8-v5", "generic-dual-v0", "packed-5"]
+SLAB_KERNELS = ["RING", "HALO", "HALO", "GENERIC", "PACKED"]
+
+
+@pytest.mark.parametrize("name,kernel", list(zip(SLAB_CASES, SLAB_KERNELS)))
+def test_wgrad_touches_the_planned_slab_only(C, name, kernel):
+    """The plan's slab_elems is what the kernels and the reduce touch: given exactly that much (NaN) in front of
+    4096 sentinel floats, the result is exact and the sentinels are intact."""
+    c = _case(L.WGRAD_CASES, name)
+    cin = 8 if c.packed else c.C1 + c.C2
+    p = _wgrad_plan(C, c, C.wgrad_slab_elems(c.N, c.H, c.W, cin, c.Cout, 9, int(c.packed), c.splits))
+    assert (p["status"], p["name"]) == (0, kernel)
+    assert (p["bn"], p["multirow"]) == {"w64-halo-v5-acc": (64, False), "w8-v5": (128, True)}.get(name, (64, False))
+    assert _wgrad_plan(C, c, p["slab_elems"])["slab_elems"] == p["slab_elems"]  # the same plan on exactly its slab
+    slab, tail = _slab(p["slab_elems"], 4096)
+    _run_wgrad(C, c, slab)
+    assert (tail == L.SENTINEL).all()
+
+
+def test_wgrad_first_bn_touches_the_planned_slab_only(C):
+    c = _case(L.FIRSTBN_CASES, "firstbn-5")
+    p = _first_bn_plan(C, c, C.wgrad_slab_elems(c.N, c.H, c.W, 8, 64, 9, 1, c.splits))
+    assert (p["status"], p["name"]) == (0, "FIRST_BN")
+    slab, tail = _slab(p["slab_elems"], 4096)
+    _run_first_bn(C, c, slab)
+    assert (tail == L.SENTINEL).all()
 
 
 # ---------------------------------------------------------------------------------------------
 # transposed decoder
 # ---------------------------------------------------------------------------------------------
+
+def _upT_fits(C, c, fwd):
+    return C.upT_plan(fwd, c.N, c.h, c.w, c.Cin, c.C, c.H2, c.W2, c.oy, c.ox)["fits"]
+
 
 @pytest.mark.parametrize("c", L.UPT_FWD_CASES, ids=lambda c: c.name)
 def test_conv_upT_fwd_exact(C, c):
@@ -289,6 +353,7 @@ def test_conv_upT_fwd_exact(C, c):
     L.assert_exact_class(d["u"])
     wf, _ = L.upT_weights(d["W"])
     u = torch.full((c.N, c.H2, c.W2, c.C), L.SENTINEL, dtype=L.BF16, device=DEV)
+    assert _upT_fits(C, c, True)
     assert C.conv_upT_fwd(d["x"].to(DEV), wf.to(DEV), d["bias"].to(DEV), u, c.oy, c.ox) == 0
     torch.cuda.synchronize()
     exp = L.expected_bf16(d["u"])
@@ -305,6 +370,7 @@ def test_conv_upT_dgrad_exact(C, c):
     L.assert_exact_class(d["dx"])
     _, wd = L.upT_weights(d["W"])
     dx = torch.full((c.N, c.h, c.w, c.Cin), L.SENTINEL, dtype=L.BF16, device=DEV)
+    assert _upT_fits(C, c, False)
     assert C.conv_upT_dgrad(d["du"].to(DEV), wd.to(DEV), dx, c.oy, c.ox) == 0
     torch.cuda.synchronize()
     assert torch.equal(dx.cpu(), L.expected_bf16(d["dx"]))
@@ -321,6 +387,13 @@ def test_upT_small_gemms_wgrad_colsum_exact(C, c):
     wf, wd = L.upT_weights(d["W"])
     M = c.N * c.h * c.w
     x, du = d["x"].to(DEV), d["du"].to(DEV)
+    # the fused launchers decline these maps (fewer than 256 ping-pong tiles), as the plan says, and write nothing
+    assert not _upT_fits(C, c, True) and not _upT_fits(C, c, False)
+    u = torch.full((c.N, c.H2, c.W2, c.C), L.SENTINEL, dtype=L.BF16, device=DEV)
+    assert C.conv_upT_fwd(x, wf.to(DEV), d["bias"].to(DEV), u, c.oy, c.ox) == -1
+    dx = torch.full((c.N, c.h, c.w, c.Cin), L.SENTINEL, dtype=L.BF16, device=DEV)
+    assert C.conv_upT_dgrad(du, wd.to(DEV), dx, c.oy, c.ox) == -1
+    assert (u == L.SENTINEL).all() and (dx == L.SENTINEL).all()
     # forward GEMM (bias is added by the shuffle pass, not here)
     yT = torch.full((c.N, c.h, c.w, 4 * c.C), L.SENTINEL, dtype=L.BF16, device=DEV)
     C.conv_fwd(x, None, wf.to(DEV), 1, 0, yT, None, None, C.CONV_AUTO, None, 0)
@@ -335,13 +408,18 @@ def test_upT_small_gemms_wgrad_colsum_exact(C, c):
     splits = max(1, M // 64)
     n_slab = C.wgrad_slab_elems(c.N, c.h, c.w, 4 * c.C, c.Cin, 1, 0, splits)
     for fused in (True, False):
-        slab = torch.full((n_slab,), NAN, device=DEV)
+        p = (C.wgrad_plan(c.N, c.h, c.w, c.C, 0, c.Cin, taps=4, splits=splits, slab_elems=n_slab, upT=True) if fused else
+             C.wgrad_plan(c.N, c.h, c.w, 4 * c.C, 0, c.Cin, taps=1, splits=splits, slab_elems=n_slab))
+        assert (p["status"], p["name"]) == (0, "UPT" if fused else "GENERIC")
+        # exactly the planned slab (NaN: written before it is read) in front of a tail the launch must not touch
+        slab, tail = _slab(p["slab_elems"], 4096 if c.name == "upT-small" else 0)
         gw = torch.full((c.Cin * 4 * c.C,), L.SENTINEL, device=DEV)
         if fused:
-            assert C.conv_wgrad_upT(du, x, c.oy, c.ox, slab, gw, 0, splits) > 0
+            assert C.conv_wgrad_upT(du, x, c.oy, c.ox, slab, gw, 0, splits) == p["splits"]
         else:
-            assert C.conv_wgrad(dyT, None, x, 1, 0, 4 * c.C, slab, gw, 0, splits, 0) > 0
+            assert C.conv_wgrad(dyT, None, x, 1, 0, 4 * c.C, slab, gw, 0, splits, C.WGRAD_AUTO) == p["splits"]
         assert torch.equal(gw.cpu(), dW)
+        assert (tail == L.SENTINEL).all()
     # bias gradient: column sums over the window's 4 sub-pixel groups, then accumulated once more
     db = torch.full((c.C,), L.SENTINEL, device=DEV)
     part = torch.full(((1024 * 4 + 64) * c.C,), NAN, device=DEV)

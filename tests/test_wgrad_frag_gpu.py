@@ -37,10 +37,6 @@ def C():
     return native()
 
 
-def takes_halo(H, W, variant):
-    return variant == 5 or W % 64 == 0 or (W >= 32 and 64 % W == 0 and (H * W) % 64 == 0)
-
-
 def run_wgrad(C, x1, x2, dy, splits, variant):
     N, H, W, C1 = x1.shape
     Cin, Cout = C1 + (x2.shape[3] if x2 is not None else 0), dy.shape[3]
@@ -48,7 +44,9 @@ def run_wgrad(C, x1, x2, dy, splits, variant):
     # and the segment count); the generic kernel takes the argument. One more than the segments is "more
     # splits than segments" to both, and keeps the slab small.
     splits = min(splits, N * H * W // 64 + 1)
-    elems = splits * Cout * 9 * Cin if takes_halo(H, W, variant) else C.wgrad_slab_elems(N, H, W, Cin, Cout, 9, 0, splits)
+    plan = C.wgrad_plan(N, H, W, C1, Cin - C1, Cout, kernel=variant, splits=splits, slab_elems=1 << 40)
+    halo = plan["name"] in ("HALO", "RING")
+    elems = splits * Cout * 9 * Cin if halo else C.wgrad_slab_elems(N, H, W, Cin, Cout, 9, 0, splits)
     slab = torch.zeros(elems, device="cuda")
     out = torch.full((Cout * 9 * Cin,), 3.0, device="cuda")
     used = C.conv_wgrad(x1, x2, dy, 9, 0, 0, slab, out, 0, splits, variant)
