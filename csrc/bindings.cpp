@@ -23,6 +23,7 @@
 #include <vector>
 #include <array>
 
+#include "bn_dev.h"
 #include "rdp_api.h"
 
 namespace {
@@ -542,11 +543,11 @@ int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w,
   }
   const float* esc = nullptr;
   const float* esh = nullptr;
-  if (affine) {  // BN coefficient block [mean | invstd | scale | shift] (4*Cout floats)
+  if (affine) {  // BN coefficient block (bn_dev.h layout, BN_ROWS * Cout floats)
     check_f32(*affine, "affine");
-    TORCH_CHECK(affine->numel() >= 4l * Cout, "affine must hold 4*Cout floats");
-    esc = affine->data_ptr<float>() + 2 * Cout;
-    esh = affine->data_ptr<float>() + 3 * Cout;
+    TORCH_CHECK(affine->numel() >= (long)BN_ROWS * Cout, "affine must hold 4*Cout floats");
+    esc = affine->data_ptr<float>() + bn_off(BN_SCALE, Cout);
+    esh = affine->data_ptr<float>() + bn_off(BN_SHIFT, Cout);
   }
   if (ws) check_f32(*ws, "ws");
   // pool (eval): MaxPool2d(2) of y1 -> pool [N][H/2][W/2][Cout]; fused into the split-K reduce when
@@ -675,7 +676,7 @@ int wgrad_first_bn(torch::Tensor x, torch::Tensor da, torch::Tensor y, torch::Te
   check_f32(coef, "coef"); check_f32(coef2, "coef2");
   RdpWgrad g;
   wgrad_dest(g, slab, out, accumulate);
-  TORCH_CHECK(coef.numel() >= 4 * 64 && coef2.numel() >= 3 * 64, "wgrad_first_bn: coef / coef2 too small");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * 64 && coef2.numel() >= BN2_ROWS * 64, "wgrad_first_bn: coef / coef2 too small");
   TORCH_CHECK(out.numel() == 64l * 9 * cin_real, "wgrad_first_bn: out numel mismatch");
   if (a.bytes >= (1l << 31) || d.bytes >= (1l << 31) || b.bytes >= (1l << 31)) return -1;
   if (((long)a.N * a.H * a.W) % 64) return -1;
@@ -715,7 +716,7 @@ void bn_finalize(torch::Tensor stats, int T, long count, torch::Tensor gamma, to
                  c10::optional<torch::Tensor> ws) {
   const int C = gamma.numel();
   check_f32(stats, "stats"); check_f32(gamma, "gamma"); check_f32(beta, "beta"); check_f32(coef, "coef");
-  TORCH_CHECK(stats.numel() >= (long)T * 2 * C && coef.numel() >= 4 * C, "bn_finalize sizes");
+  TORCH_CHECK(stats.numel() >= (long)T * 2 * C && coef.numel() >= (long)BN_ROWS * C, "bn_finalize sizes");
   float* rm = nullptr; float* rv = nullptr; long long* nb = nullptr;
   if (rmean) { check_f32(*rmean, "rmean"); rm = rmean->data_ptr<float>(); }
   if (rvar) { check_f32(*rvar, "rvar"); rv = rvar->data_ptr<float>(); }
@@ -735,7 +736,7 @@ void bn_eval_coef(torch::Tensor gamma, torch::Tensor beta, torch::Tensor rmean, 
 void bn_relu_apply(torch::Tensor y, torch::Tensor out, torch::Tensor coef, int relu) {
   Act a = act(y, "y"), o = act(out, "out");
   TORCH_CHECK(a.N == o.N && a.H == o.H && a.W == o.W && a.C == o.C, "bn_relu_apply shape");
-  TORCH_CHECK(coef.numel() >= 4 * a.C, "coef");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * a.C, "coef");
   TORCH_CHECK(RDP_PLAN(rdp_bn_relu_apply(a.ptr, a.pitch, o.ptr, o.pitch, coef.data_ptr<float>(), a.N * a.H * a.W, a.C, relu,
                                 st)) == 0, "bn_relu_apply");
 }
@@ -753,7 +754,7 @@ int conv_dgrad_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, torch:
   TORCH_CHECK(w.size(0) == o.C, "w rows != Cout");
   check_f32(coef, "coef");
   check_f32(partial, "partial");
-  TORCH_CHECK(coef.numel() >= 4l * o.C, "coef must hold 4*C floats");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * o.C, "coef must hold 4*C floats");
   // ring grid <= 256 blocks x 4 pixel groups (64 couts) or 2 (128): <= 1024 rows of 2*C
   TORCH_CHECK(partial.numel() >= 1024l * 2 * o.C, "partial too small");
   // batches past the 2 GiB buffer-offset reach: the caller's chunked conv_fwd + bn_relu_bwd_reduce
@@ -784,7 +785,7 @@ int conv_dgrad_splitk_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx,
   TORCH_CHECK(w.size(0) == o.C && w.size(1) >= 9l * a.C, "conv_dgrad_splitk_bnred: w must be [Cout][9 * Cin]");
   check_f32(coef, "coef");
   check_f32(partial, "partial");
-  TORCH_CHECK(coef.numel() >= 4l * o.C, "coef must hold 4*C floats");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * o.C, "coef must hold 4*C floats");
   TORCH_CHECK(partial.numel() >= 512l * 2 * o.C, "partial too small");  // the split-K reduce: <= 512 rows
   if (ws) check_f32(*ws, "ws");
   if (chunk_images({a, o, b}, a.N) < a.N) return -1;
@@ -824,7 +825,7 @@ int conv_fwd_bnin(torch::Tensor x_pre, torch::Tensor w, torch::Tensor y, torch::
   TORCH_CHECK(o.N == a.N && o.H == a.H && o.W == a.W && w.size(0) == o.C, "conv_fwd_bnin: shape mismatch");
   check_f32(stats, "stats");
   check_f32(in_coef, "in_coef");
-  TORCH_CHECK(in_coef.numel() >= 4l * a.C, "in_coef: [4 C] f32");
+  TORCH_CHECK(in_coef.numel() >= (long)BN_ROWS * a.C, "in_coef: [4 C] f32");
   // (the ring grid writes <= 256 blocks x 4 pixel-group rows of 2 * C)
   if (a.C != 64 || o.C != 64 || a.W % 64 || a.H % 2 || stats.numel() < 1024l * 2 * o.C) return -1;
   if (chunk_images({a, o}, a.N) < a.N) return -1;
@@ -834,8 +835,8 @@ int conv_fwd_bnin(torch::Tensor x_pre, torch::Tensor w, torch::Tensor y, torch::
   conv_weights(c, w);
   c.Cout = o.C;
   c.stats = stats.data_ptr<float>();
-  f.iscale = in_coef.data_ptr<float>() + 2 * a.C;
-  f.ishift = in_coef.data_ptr<float>() + 3 * a.C;
+  f.iscale = in_coef.data_ptr<float>() + bn_off(BN_SCALE, a.C);
+  f.ishift = in_coef.data_ptr<float>() + bn_off(BN_SHIFT, a.C);
   return RDP_PLAN(rdp_conv_ring_ex(c, 256, f, st));
 }
 
@@ -892,7 +893,7 @@ void bn_relu_apply_pool(torch::Tensor y, c10::optional<torch::Tensor> out, torch
   }
   TORCH_CHECK(p.N == a.N && p.H == a.H / 2 && p.W == a.W / 2 && p.C == a.C, "bn_relu_apply_pool pool shape");
   check_f32(coef, "coef");
-  TORCH_CHECK(coef.numel() >= 4 * a.C, "coef");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * a.C, "coef");
   TORCH_CHECK(RDP_PLAN(rdp_bn_relu_apply_pool(a.ptr, a.pitch, out ? o.ptr : nullptr, out ? o.pitch : 0, p.ptr, p.pitch, coef.data_ptr<float>(), a.N, a.H,
                                      a.W, a.C, st)) == 0, "bn_relu_apply_pool: channels must be 2^k in [8, 2048]");
 }
@@ -908,7 +909,7 @@ int maxpool2_bwd_bn_reduce(torch::Tensor dp, torch::Tensor x, c10::optional<torc
   TORCH_CHECK(yy.N == a.N && yy.H == a.H && yy.W == a.W && yy.C == a.C, "maxpool bwd y shape");
   check_f32(coef, "coef");
   check_f32(partial, "partial");
-  TORCH_CHECK(coef.numel() >= 4 * a.C, "coef");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * a.C, "coef");
   const int maxb = partial.numel() / (2 * a.C);
   TORCH_CHECK(maxb >= 1, "partial too small");
   const int T = RDP_PLAN(rdp_maxpool2_bwd_bn_reduce(p.ptr, p.pitch, a.ptr, a.pitch, dskip ? s.ptr : nullptr, dskip ? s.pitch : 0,
@@ -925,7 +926,7 @@ void upsample2_fwd(torch::Tensor x, torch::Tensor out, int oy, int ox, c10::opti
   TORCH_CHECK(2 * a.H + oy <= o.H && 2 * a.W + ox <= o.W && oy >= 0 && ox >= 0, "upsample fwd placement");
   const float* cp = nullptr;
   if (coef && coef->defined()) {
-    TORCH_CHECK(coef->is_cuda() && coef->scalar_type() == torch::kFloat32 && coef->numel() >= 4 * a.C, "coef [4C] f32");
+    TORCH_CHECK(coef->is_cuda() && coef->scalar_type() == torch::kFloat32 && coef->numel() >= (long)BN_ROWS * a.C, "coef [4C] f32");
     cp = coef->data_ptr<float>();
   }
   TORCH_CHECK(RDP_PLAN(rdp_upsample2_fwd(a.ptr, a.pitch, o.ptr, o.pitch, a.N, a.H, a.W, o.H, o.W, oy, ox, a.C, cp,
@@ -949,7 +950,7 @@ int upsample2_bwd(torch::Tensor dout, torch::Tensor dx, int oy, int ox, c10::opt
     TORCH_CHECK(yy.N == o.N && yy.H == o.H && yy.W == o.W && yy.C == o.C, "upsample bwd y shape");
     check_f32(*coef, "coef");
     check_f32(*partial, "partial");
-    TORCH_CHECK(coef->numel() >= 4 * o.C, "coef");
+    TORCH_CHECK(coef->numel() >= (long)BN_ROWS * o.C, "coef");
     maxb = std::min<long>(partial->numel() / (2 * o.C), 4096);
     TORCH_CHECK(maxb >= 1, "partial too small");
     cf = coef->data_ptr<float>();
@@ -1072,7 +1073,7 @@ void head_fwd(torch::Tensor a, torch::Tensor w, torch::Tensor b, torch::Tensor t
   TORCH_CHECK(partial.numel() >= (long)rdp_head_partial_blocks(M) * 65, "head partial too small");
   const float* cf = nullptr;
   if (coef) {
-    TORCH_CHECK(coef->numel() >= 4 * 64 && coef->scalar_type() == torch::kFloat, "head coef");
+    TORCH_CHECK(coef->numel() >= (long)BN_ROWS * 64 && coef->scalar_type() == torch::kFloat, "head coef");
     cf = coef->data_ptr<float>();
   }
   float* gp = nullptr;
@@ -1114,7 +1115,7 @@ int head_bwd(torch::Tensor a, torch::Tensor w, torch::Tensor logits, torch::Tens
   float* bp = nullptr;
   if (coef) {
     TORCH_CHECK(bnpart && bnpart->numel() >= (long)rdp_head_partial_blocks(M) * 128, "head bnpart too small");
-    TORCH_CHECK(coef->numel() >= 4 * 64 && coef->scalar_type() == torch::kFloat, "head coef");
+    TORCH_CHECK(coef->numel() >= (long)BN_ROWS * 64 && coef->scalar_type() == torch::kFloat, "head coef");
     cf = coef->data_ptr<float>();
     bp = bnpart->data_ptr<float>();
   } else {
@@ -1137,7 +1138,7 @@ void head_bn_bwd_apply(torch::Tensor y, torch::Tensor w, torch::Tensor logits, t
   const long M = (long)x.N * x.H * x.W;
   TORCH_CHECK(x.C == 64 && d.C == 64 && (long)d.N * d.H * d.W == M, "head_bn_bwd_apply shapes");
   TORCH_CHECK(logits.numel() == M && target.numel() == M, "head_bn_bwd_apply logits/target numel");
-  TORCH_CHECK(coef.numel() >= 4 * 64 && coef2.numel() >= 3 * 64, "head_bn_bwd_apply coef sizes");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * 64 && coef2.numel() >= BN2_ROWS * 64, "head_bn_bwd_apply coef sizes");
   TORCH_CHECK(RDP_PLAN(rdp_head_bn_bwd_apply(x.ptr, x.pitch, w.data_ptr<float>(), logits.data_ptr<float>(),
                                     target.data_ptr<float>(), sums.data_ptr<float>(), coef.data_ptr<float>(),
                                     coef2.data_ptr<float>(), d.ptr, d.pitch, M, (float)dice_w, (float)dice_eps,
@@ -1154,12 +1155,12 @@ bool conv_head_mask(torch::Tensor x, torch::Tensor w, torch::Tensor coef, torch:
   check_f32(coef, "coef");
   check_f32(hw, "head_w");
   check_f32(hb, "head_b");
-  TORCH_CHECK(coef.numel() >= 4l * w.size(0) && hw.numel() == w.size(0) && hb.numel() >= 1, "coef / head sizes");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * w.size(0) && hw.numel() == w.size(0) && hb.numel() >= 1, "coef / head sizes");
   TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kUInt8 && mask.is_contiguous() &&
               mask.numel() >= (long)a.N * a.H * a.W, "mask: u8 [N*H*W]");
   const int Co = (int)w.size(0);
   const int r = RDP_PLAN(rdp_conv_ring_head(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, w.size(1), Co, a.N, a.H,
-                                   a.W, coef.data_ptr<float>() + 2 * Co, coef.data_ptr<float>() + 3 * Co,
+                                   a.W, coef.data_ptr<float>() + bn_off(BN_SCALE, Co), coef.data_ptr<float>() + bn_off(BN_SHIFT, Co),
                                    hw.data_ptr<float>(), hb.data_ptr<float>(), (float)thr, mask.data_ptr(),
                                    st));
   return r == 0;
@@ -1175,7 +1176,7 @@ int conv_rowband(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tenso
   Act o = act(y, "y");
   TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.is_contiguous(), "w: bf16 contiguous");
   check_f32(coef, "coef");
-  TORCH_CHECK(coef.numel() >= 4l * o.C, "coef size");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * o.C, "coef size");
   Act po;
   if (pool) po = act(*pool, "pool");
   RdpConv c;
@@ -1184,7 +1185,7 @@ int conv_rowband(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tenso
   conv_bind(c, kY1, o, 0, a1.N);
   c.w = w.data_ptr(); c.wbytes = w.numel() * 2; c.ldw = wfrag ? 0 : (int)w.size(1);
   c.Cout = o.C;
-  c.escale = coef.data_ptr<float>() + 2 * o.C; c.eshift = coef.data_ptr<float>() + 3 * o.C; c.erelu = 1;
+  c.escale = coef.data_ptr<float>() + bn_off(BN_SCALE, o.C); c.eshift = coef.data_ptr<float>() + bn_off(BN_SHIFT, o.C); c.erelu = 1;
   void* const pp = pool ? po.ptr : nullptr;
   const long pb = pool ? po.bytes : 0;
   const int ppit = pool ? po.pitch : 0;
@@ -1211,10 +1212,10 @@ bool conv_rowband_chain(torch::Tensor x, std::vector<torch::Tensor> ws, std::vec
     Act o = act(ys[l], "y");
     TORCH_CHECK(o.N == a.N && o.H == a.H && o.W == a.W && o.C == ws[l].size(0), "y shape");
     check_f32(coefs[l], "coef");
-    TORCH_CHECK(coefs[l].numel() >= 4l * o.C, "coef size");
+    TORCH_CHECK(coefs[l].numel() >= (long)BN_ROWS * o.C, "coef size");
     wp[l] = ws[l].data_ptr(); wb[l] = ws[l].numel() * 2; ldw[l] = (int)ws[l].size(1);
     yp[l] = o.ptr; yb[l] = o.bytes; ypit[l] = o.pitch; co[l] = o.C;
-    sc[l] = coefs[l].data_ptr<float>() + 2 * o.C; sh[l] = coefs[l].data_ptr<float>() + 3 * o.C;
+    sc[l] = coefs[l].data_ptr<float>() + bn_off(BN_SCALE, o.C); sh[l] = coefs[l].data_ptr<float>() + bn_off(BN_SHIFT, o.C);
   }
   int* const cp = cnt.data_ptr<int>();
   int* const ep = err.data_ptr<int>();
@@ -1345,7 +1346,7 @@ bool conv_headk_mask(torch::Tensor x, torch::Tensor w, torch::Tensor coef, torch
   check_w(w);
   check_f32(coef, "coef");
   const int K = headk_classes(hw, hb, "conv_headk_mask");
-  TORCH_CHECK(coef.numel() >= 4l * w.size(0), "coef size");
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * w.size(0), "coef size");
   TORCH_CHECK(cls >= 0 && cls < K, "conv_headk_mask: class ", cls, " outside 0..", K - 1);
   const long M = (long)a.N * a.H * a.W;
   TORCH_CHECK(M > 0 && M < (1L << 31), "conv_headk_mask: pixel count");
@@ -1353,7 +1354,7 @@ bool conv_headk_mask(torch::Tensor x, torch::Tensor w, torch::Tensor coef, torch
               "mask: u8 [N*H*W]");
   const int Co = (int)w.size(0);
   const int r = RDP_PLAN(rdp_conv_ring_headk(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, w.size(1), Co, a.N,
-                                             a.H, a.W, coef.data_ptr<float>() + 2 * Co, coef.data_ptr<float>() + 3 * Co,
+                                             a.H, a.W, coef.data_ptr<float>() + bn_off(BN_SCALE, Co), coef.data_ptr<float>() + bn_off(BN_SHIFT, Co),
                                              hw.data_ptr<float>(), hb.data_ptr<float>(), K, cls, mask.data_ptr(), st));
   return r == 0;
 }

@@ -112,9 +112,15 @@ static inline FastDiv make_fastdiv(uint32_t d) {
   f.m = (uint32_t)((((uint64_t)1 << 32) * (((uint64_t)1 << s) - d)) / d + 1);
   return f;
 }
-RDP_DEV uint32_t fdiv(uint32_t n, const FastDiv& f) {
-  return (__umulhi(n, f.m) + n) >> f.s;
-}
+RDP_DEV uint32_t fdiv(uint32_t n, uint32_t m, uint32_t s) { return (__umulhi(n, m) + n) >> s; }
+RDP_DEV uint32_t fdiv(uint32_t n, const FastDiv& f) { return fdiv(n, f.m, f.s); }
+
+// 3x3 tap index (row-major, 0..8) -> (dr, ds) in {-1, 0, 1} without a division
+RDP_DEV int tap_dr(int tap) { return ((tap * 11) >> 5) - 1; }
+RDP_DEV int tap_ds(int tap) { return tap - 3 * ((tap * 11) >> 5) - 1; }
+
+// channel counts the 8-channels-per-thread pass kernels index with shifts and masks
+static inline bool pow2_channels(int C) { return C >= 8 && C <= 2048 && (C & (C - 1)) == 0; }
 
 // branch-free 0 <= v < n (no short-circuit control flow around LDS-DMA issue)
 RDP_DEV bool inb(int v, int n) { return (unsigned)v < (unsigned)n; }

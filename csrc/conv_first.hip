@@ -17,7 +17,7 @@
 //   * a wave owns 64 consecutive pixels x 64 couts per step (4 x 4 accumulators) and walks the
 //     pixel segments grid-stride; BN partial sums stay in registers until the wave's last segment,
 //     then the block's 4 wave rows are summed through LDS into ONE stats row per block.
-#include "common.h"
+#include "bn_dev.h"
 #include "rdp_api.h"
 
 struct FirstArgs {
@@ -36,9 +36,6 @@ struct FirstArgs {
   int H, W, M, nseg;
   uint32_t fhw_m, fhw_s, fw_m, fw_s;
 };
-
-RDP_DEV int ftap_dr(int tap) { return ((tap * 11) >> 5) - 1; }
-RDP_DEV int ftap_ds(int tap) { return tap - 3 * ((tap * 11) >> 5) - 1; }
 
 __global__ __launch_bounds__(256) void conv_first_kernel(const FirstArgs a) {
   __shared__ float red[4][2][64];
@@ -94,7 +91,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const FirstArgs a) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {  // taps 2g, 2g + 1 (step 0), 8 + 2g, 9 + 2g (step 1)
         const int tap = (q >> 1) * 8 + 2 * g + (q & 1);
-        const int dr = ftap_dr(tap), ds = ftap_ds(tap);
+        const int dr = tap_dr(tap), ds = tap_ds(tap);
         const bool ok = valid && tap < 9 && inb(h + dr, a.H) && inb(w + ds, a.W);
         const uint32_t off = ok ? (uint32_t)((m + dr * a.W + ds) * a.pitch) * 2u : RDP_OOB;
         v[q] = bload8(rx, off);
@@ -139,12 +136,7 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const FirstArgs a) {
           v[hh].x = pack2bf(o[0], o[1]);
           v[hh].y = pack2bf(o[2], o[3]);
           if (a.stats) {  // rows past M hold zeros (all taps read zeros): no contribution
-            const float q0 = __uint_as_float(v[hh].x << 16), q1 = __uint_as_float(v[hh].x & 0xffff0000u);
-            const float q2 = __uint_as_float(v[hh].y << 16), q3 = __uint_as_float(v[hh].y & 0xffff0000u);
-            s1[j][0] += q0; s2[j][0] += q0 * q0;
-            s1[j][1] += q1; s2[j][1] += q1 * q1;
-            s1[j][2] += q2; s2[j][2] += q2 * q2;
-            s1[j][3] += q3; s2[j][3] += q3 * q3;
+            bn_stats4(v[hh], s1[j], s2[j]);
           }
         }
         const auto rxs = __builtin_amdgcn_permlane16_swap(v[0].x, v[1].x, false, false);

@@ -23,7 +23,8 @@
 // pipeline (one raw s_barrier per K step), so tile t+1's first DMA lands under tile t's last
 // MFMAs and epilogue. This removes the per-tile prologue that dominated the small-K (K = 576)
 // 64-channel layers. The epilogue uses no LDS and no block barrier.
-#include "common.h"
+#include "bn_dev.h"
+#include "pool_dev.h"
 #include "rdp_api.h"
 
 struct ConvArgs {
@@ -75,10 +76,6 @@ struct ConvArgs {
   int bnypitch = 0;
   int* bnrows = nullptr;  // host cell: the partial rows written (set when the split-K reduce ran)
 };
-
-// tap (0..8) -> (dr, ds) without division: dr + 1 = (tap * 11) >> 5
-RDP_DEV int tap_dr(int tap) { return ((tap * 11) >> 5) - 1; }
-RDP_DEV int tap_ds(int tap) { return tap - 3 * ((tap * 11) >> 5) - 1; }
 
 template <int N>
 RDP_DEV void vm_wait() {
@@ -324,12 +321,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_igemm_kernel(const ConvArgs 
           v[h].y = pack2bf(o[2], o[3]);
           acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
           if (a.stats) {
-            const float q0 = __uint_as_float(v[h].x << 16), q1 = __uint_as_float(v[h].x & 0xffff0000u);
-            const float q2 = __uint_as_float(v[h].y << 16), q3 = __uint_as_float(v[h].y & 0xffff0000u);
-            s1[j][0] += q0; s2[j][0] += q0 * q0;
-            s1[j][1] += q1; s2[j][1] += q1 * q1;
-            s1[j][2] += q2; s2[j][2] += q2 * q2;
-            s1[j][3] += q3; s2[j][3] += q3 * q3;
+            bn_stats4(v[h], s1[j], s2[j]);
           }
         }
         const auto rxs = __builtin_amdgcn_permlane16_swap(v[0].x, v[1].x, false, false);
@@ -606,12 +598,7 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const ConvArgs a) {
           v[h].y = pack2bf(o[2], o[3]);
           acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
           if (a.stats && m < a.M) {
-            const float q0 = __uint_as_float(v[h].x << 16), q1 = __uint_as_float(v[h].x & 0xffff0000u);
-            const float q2 = __uint_as_float(v[h].y << 16), q3 = __uint_as_float(v[h].y & 0xffff0000u);
-            s1[j][0] += q0; s2[j][0] += q0 * q0;
-            s1[j][1] += q1; s2[j][1] += q1 * q1;
-            s1[j][2] += q2; s2[j][2] += q2 * q2;
-            s1[j][3] += q3; s2[j][3] += q3 * q3;
+            bn_stats4(v[h], s1[j], s2[j]);
           }
         }
         const auto rxs = __builtin_amdgcn_permlane16_swap(v[0].x, v[1].x, false, false);
@@ -622,9 +609,9 @@ __global__ __launch_bounds__(512, 1) void conv_pp_kernel(const ConvArgs a) {
           // on the (wave-uniform) first pixel; else per lane
           const bool row16 = (a.W & 15) == 0;
           const uint32_t mm = row16 ? (uint32_t)(m0 + wpx + i * 16) : (uint32_t)m;
-          const uint32_t img = (__umulhi(mm, a.fhw_m) + mm) >> a.fhw_s;
+          const uint32_t img = fdiv(mm, a.fhw_m, a.fhw_s);
           const uint32_t hw = mm - img * (uint32_t)(a.H * a.W);
-          const uint32_t hh = (__umulhi(hw, a.fw_m) + hw) >> a.fw_s;
+          const uint32_t hh = fdiv(hw, a.fw_m, a.fw_s);
           const uint32_t ww = hw - hh * (uint32_t)a.W + (row16 ? (uint32_t)(lane & 15) : 0u);
           pix = ((img * (uint32_t)a.tH2 + 2u * hh + (uint32_t)a.toy) * (uint32_t)a.tW2 + 2u * ww + (uint32_t)a.tox) *
                     (uint32_t)yp + (uint32_t)subo;
@@ -813,7 +800,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvArgs 
   const int yp = d2 ? a.ypitch2 : a.ypitch1;
   const auto rk = make_rsrc(a.kslab, (uint32_t)((long)a.ksplit * a.M * a.Cout * 4));
   const uint32_t sstride = (uint32_t)a.M * (uint32_t)a.Cout * 4u;  // bytes between slices
-  f32x4 s1 = f32x4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
+  float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   // sum of the slices + epilogue for pixel m -> 4 bf16 (packed), stored to y
   auto pixel = [&](int m) -> uint2 {
     f32x4 acc[4];
@@ -851,14 +838,14 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvArgs 
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const uint32_t wd = k < 2 ? q[0].x : q[0].y;
-        mx[k] = __uint_as_float((k & 1) ? (wd & 0xffff0000u) : (wd << 16));
+        mx[k] = (k & 1) ? bfhi(wd) : bflo(wd);
       }
 #pragma unroll
       for (int t = 1; t < 4; ++t)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const uint32_t wd = k < 2 ? q[t].x : q[t].y;
-          mx[k] = fmaxf(mx[k], __uint_as_float((k & 1) ? (wd & 0xffff0000u) : (wd << 16)));
+          mx[k] = fmaxf(mx[k], (k & 1) ? bfhi(wd) : bflo(wd));
         }
       *(uint2*)(a.pool + (long)wi * a.ppitch + n) = make_uint2(pack2bf(mx[0], mx[1]), pack2bf(mx[2], mx[3]));
     }
@@ -870,29 +857,21 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvArgs 
   if (bnr) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      bmean[k] = a.bncoef[n + k];
-      binv[k] = a.bncoef[a.Cout + n + k];
-      bsc[k] = a.bncoef[2 * a.Cout + n + k];
-      bsh[k] = a.bncoef[3 * a.Cout + n + k];
+      bmean[k] = a.bncoef[bn_off(BN_MEAN, a.Cout) + n + k];
+      binv[k] = a.bncoef[bn_off(BN_INVSTD, a.Cout) + n + k];
+      bsc[k] = a.bncoef[bn_off(BN_SCALE, a.Cout) + n + k];
+      bsh[k] = a.bncoef[bn_off(BN_SHIFT, a.Cout) + n + k];
     }
   }
   for (int m = blockIdx.x * RPB + r; m < a.M; m += nrow_blocks * RPB) {
     const uint2 w = pixel(m);
-    const float q[4] = {__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u),
-                        __uint_as_float(w.y << 16), __uint_as_float(w.y & 0xffff0000u)};
     if (a.stats) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { s1[k] += q[k]; s2[k] += q[k] * q[k]; }
-    } else if (bnr) {  // q = dL/da (as stored, bf16) of the owner's post-ReLU activation
-      const uint2 yv = *(const uint2*)(a.bny + (long)m * a.bnypitch + n);
-      const float fy[4] = {__uint_as_float(yv.x << 16), __uint_as_float(yv.x & 0xffff0000u),
-                           __uint_as_float(yv.y << 16), __uint_as_float(yv.y & 0xffff0000u)};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float g = fmaf(fy[k], bsc[k], bsh[k]) > 0.f ? q[k] : 0.f;
-        s1[k] += g;
-        s2[k] += g * (fy[k] - bmean[k]) * binv[k];
-      }
+      bn_stats4(w, s1, s2);
+    } else if (bnr) {  // w = dL/da (as stored, bf16) of the owner's post-ReLU activation
+      float q[4], fy[4];
+      unpack4(w, q);
+      unpack4(*(const uint2*)(a.bny + (long)m * a.bnypitch + n), fy);
+      bn_acc_n(q, fy, bmean, binv, bsc, bsh, s1, s2);
     }
   }
   float* const rows_out = a.stats ? a.stats : (bnr ? a.bnpart : nullptr);
@@ -917,12 +896,6 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_kernel(const ConvArgs 
 // never re-read from memory and the upsample launch disappears.
 #define UP_TY RDP_UP_TY
 #define UP_CG RDP_UP_CG
-RDP_DEV void up_src_f(int u, int in, float r, int& i0, int& i1, float& l1) {  // = up_src (pool_up.hip)
-  const float sv = r * (float)u;
-  i0 = (int)sv;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = sv - (float)i0;
-}
 __global__ __launch_bounds__(256) void conv_splitk_reduce_up_kernel(const ConvArgs a) {
   extern __shared__ uint32_t srcs[];  // [source row][W][UP_CG / 2] packed bf16 pairs
   const int nb = (a.uH + UP_TY - 1) / UP_TY;
@@ -935,7 +908,7 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_up_kernel(const ConvAr
     if (uy < 0 || uy >= 2 * a.H) continue;
     int y0, y1;
     float ly;
-    up_src_f(uy, a.H, a.urh, y0, y1, ly);
+    up_src(uy, a.H, a.urh, y0, y1, ly);
     sy_lo = min(sy_lo, y0);
     sy_hi = max(sy_hi, y1);
   }
@@ -983,13 +956,11 @@ __global__ __launch_bounds__(256) void conv_splitk_reduce_up_kernel(const ConvAr
     if (!(uy < 0 || ux < 0 || uy >= 2 * a.H || ux >= 2 * a.W)) {
       int y0, y1, x0, x1;
       float ly, lx;
-      up_src_f(uy, a.H, a.urh, y0, y1, ly);
-      up_src_f(ux, a.W, a.urw, x0, x1, lx);
+      up_src(uy, a.H, a.urh, y0, y1, ly);
+      up_src(ux, a.W, a.urw, x0, x1, lx);
       auto ld = [&](int yy, int xx, float* f) {
         const int i = (((yy - sy_lo) * a.W + xx) * NQ + q) * 2;
-        const uint32_t lo = srcs[i], hi = srcs[i + 1];
-        f[0] = __uint_as_float(lo << 16); f[1] = __uint_as_float(lo & 0xffff0000u);
-        f[2] = __uint_as_float(hi << 16); f[3] = __uint_as_float(hi & 0xffff0000u);
+        unpack4(make_uint2(srcs[i], srcs[i + 1]), f);
       };
       float pa[4], pb[4], pc[4], pd[4];
       ld(y0, x0, pa); ld(y0, x1, pb); ld(y1, x0, pc); ld(y1, x1, pd);

@@ -19,7 +19,7 @@
 // At a column's first / last row the dr = -1 / +1 taps read an all-zero slot instead (the ring slot
 // holds another column's row there: the zero padding row of this one). Epilogue: bf16 store (permlane16-widened, 16 B
 // per lane), optional training BN statistics (per-block partial rows) or eval BN fold + ReLU.
-#include "common.h"
+#include "bn_dev.h"
 #include "head_multi_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
@@ -73,8 +73,6 @@ struct RingArgs {
   int pairs_per_block;
   uint32_t fh_m, fh_s, fs_m, fs_s;  // fast division by H and by WS
 };
-
-RDP_DEV uint32_t rdiv(uint32_t n, uint32_t m, uint32_t s) { return (__umulhi(n, m) + n) >> s; }
 
 // COUT = 64: 8 waves = 2 channel groups x 4 pixel groups (32 px); COUT = 128: 4 x 2 (64 px).
 // BNR: dgrad epilogue fused with the owner layer's BN-backward reduction (a separate instantiation:
@@ -164,9 +162,9 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
   const int gch = (lane & 7) ^ (lane >> 3);  // global 16-B chunk (LDS row & 7 == lane >> 3)
   auto row_base = [&](int R, int& m0, int& w0) {  // first pixel of the row segment; -1: no such row
     if (R < 0 || R >= a.nrows) { m0 = -1; w0 = 0; return; }
-    const uint32_t col = rdiv((uint32_t)R, a.fh_m, a.fh_s);
+    const uint32_t col = fdiv((uint32_t)R, a.fh_m, a.fh_s);
     const int h = R - (int)col * a.H;
-    const uint32_t n = rdiv(col, a.fs_m, a.fs_s);
+    const uint32_t n = fdiv(col, a.fs_m, a.fs_s);
     const int ws = (int)col - (int)n * a.WS;
     w0 = ws * 64;
     m0 = ((int)n * a.H + h) * a.W + w0;
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
     for (int c = threadIdx.x; c < COUT; c += 512) { efold[c] = a.escale[c]; efold[COUT + c] = a.eshift[c]; }
   }
   if constexpr (BNR) {
-    for (int c = threadIdx.x; c < 4 * COUT; c += 512) efold[c] = a.bncoef[c];
+    for (int c = threadIdx.x; c < BN_ROWS * COUT; c += 512) efold[c] = a.bncoef[c];
   }
   if constexpr (HK > 0) {  // visible after the first step's barrier, long before the first finish
     for (int c = threadIdx.x; c < HK * 64 + 8; c += 512) hkw[c] = c < HK * 64 ? a.hw[c] : (c - HK * 64 < HK ? a.hb[c - HK * 64] : 0.f);
@@ -245,8 +243,8 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
     uint32_t o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float lo = fmaxf(fmaf(__uint_as_float(wv[k] << 16), sc[2 * k], sh[2 * k]), 0.f);
-      const float hi = fmaxf(fmaf(__uint_as_float(wv[k] & 0xffff0000u), sc[2 * k + 1], sh[2 * k + 1]), 0.f);
+      const float lo = bn_relu(bflo(wv[k]), sc[2 * k], sh[2 * k]);
+      const float hi = bn_relu(bfhi(wv[k]), sc[2 * k + 1], sh[2 * k + 1]);
       o[k] = pack2bf(lo, hi);
     }
     const uint4 ov = make_uint4(o[0], o[1], o[2], o[3]);
@@ -318,8 +316,8 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
       uint32_t o[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float lo = fmaxf(__uint_as_float(w0[k] << 16), __uint_as_float(w1[k] << 16));
-        const float hi = fmaxf(__uint_as_float(w0[k] & 0xffff0000u), __uint_as_float(w1[k] & 0xffff0000u));
+        const float lo = fmaxf(bflo(w0[k]), bflo(w1[k]));
+        const float hi = fmaxf(bfhi(w0[k]), bfhi(w1[k]));
         o[k] = pack2bf(lo, hi);
       }
       u16* dst = a.pool + (size_t)(pb_prev + ((px0 + 16 * i + (lane & 15)) >> 1)) * a.ppitch + 32 * cg + 4 * gq;
@@ -354,7 +352,7 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
       for (int q = 0; q < 2; ++q) {
         const int t = q * 64 + px;
         float f[8], d[KP];
-        rdp_headk::unpack8h(*(const uint4*)(htile + par * (128 * 128) + t * 128 + 16 * (sub ^ (t & 7))), f);
+        unpack8(*(const uint4*)(htile + par * (128 * 128) + t * 128 + 16 * (sub ^ (t & 7))), f);
 #pragma unroll
         for (int k = 0; k < KP; ++k) {
           d[k] = 0.f;
@@ -425,7 +423,7 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
     if (dma_next) issue(P + 2);
 
     const int R0 = 2 * P + orow;  // this wave's output row (column order)
-    const int h = R0 - (int)rdiv((uint32_t)R0, a.fh_m, a.fh_s) * a.H;
+    const int h = R0 - (int)fdiv((uint32_t)R0, a.fh_m, a.fh_s) * a.H;
     const bool top = h == 0, bottom = h == a.H - 1;
     // software-pipelined over the 9 taps: the 4 B fragments of tap t + 1 are read while tap t's 8
     // MFMAs run (with only 2 waves per SIMD, a read -> wait -> MFMA chain per tap leaves the
@@ -542,25 +540,16 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
         v[j].x = pack2bf(o[0], o[1]);
         v[j].y = pack2bf(o[2], o[3]);
         if (HK == 0 && a.stats) {
-          const float q0 = __uint_as_float(v[j].x << 16), q1 = __uint_as_float(v[j].x & 0xffff0000u);
-          const float q2 = __uint_as_float(v[j].y << 16), q3 = __uint_as_float(v[j].y & 0xffff0000u);
-          if constexpr (BNR) {
+          if constexpr (BNR) {  // efold = the owner layer's coefficient block: q = dL/da as stored
             const int c = 32 * cg + 16 * j + 4 * gq;
-            const float4 mu = *(const float4*)(efold + c), iv = *(const float4*)(efold + COUT + c);
-            const float4 sc = *(const float4*)(efold + 2 * COUT + c), sh = *(const float4*)(efold + 3 * COUT + c);
-            const float y0 = __uint_as_float(yb[i][j].x << 16), y1 = __uint_as_float(yb[i][j].x & 0xffff0000u);
-            const float y2 = __uint_as_float(yb[i][j].y << 16), y3 = __uint_as_float(yb[i][j].y & 0xffff0000u);
-            const float g0 = fmaf(y0, sc.x, sh.x) > 0.f ? q0 : 0.f, g1 = fmaf(y1, sc.y, sh.y) > 0.f ? q1 : 0.f;
-            const float g2 = fmaf(y2, sc.z, sh.z) > 0.f ? q2 : 0.f, g3 = fmaf(y3, sc.w, sh.w) > 0.f ? q3 : 0.f;
-            s1[j][0] += g0; s2[j][0] += g0 * (y0 - mu.x) * iv.x;
-            s1[j][1] += g1; s2[j][1] += g1 * (y1 - mu.y) * iv.y;
-            s1[j][2] += g2; s2[j][2] += g2 * (y2 - mu.z) * iv.z;
-            s1[j][3] += g3; s2[j][3] += g3 * (y3 - mu.w) * iv.w;
+            float q[4], fy[4], mu[4], iv[4], sc[4], sh[4];
+            unpack4(v[j], q);
+            unpack4(yb[i][j], fy);
+            bn_ld4(efold, BN_MEAN, COUT, c, mu); bn_ld4(efold, BN_INVSTD, COUT, c, iv);
+            bn_ld4(efold, BN_SCALE, COUT, c, sc); bn_ld4(efold, BN_SHIFT, COUT, c, sh);
+            bn_acc_n(q, fy, mu, iv, sc, sh, s1[j], s2[j]);
           } else {
-            s1[j][0] += q0; s2[j][0] += q0 * q0;
-            s1[j][1] += q1; s2[j][1] += q1 * q1;
-            s1[j][2] += q2; s2[j][2] += q2 * q2;
-            s1[j][3] += q3; s2[j][3] += q3 * q3;
+            bn_stats4(v[j], s1[j], s2[j]);
           }
         }
       }
@@ -569,8 +558,8 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const uint32_t nb = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hw4[k], 0xB1, 0xf, 0xf, false);
-          const float lo = fmaxf(__uint_as_float(hw4[k] << 16), __uint_as_float(nb << 16));
-          const float hi = fmaxf(__uint_as_float(hw4[k] & 0xffff0000u), __uint_as_float(nb & 0xffff0000u));
+          const float lo = fmaxf(bflo(hw4[k]), bflo(nb));
+          const float hi = fmaxf(bfhi(hw4[k]), bfhi(nb));
           hw4[k] = pack2bf(lo, hi);
         }
         if (!(lane & 1))
@@ -804,9 +793,9 @@ __global__ __launch_bounds__(512, 2) void conv_ring2_kernel(const Ring2Args a) {
   const int lofs0 = lrow * a.pitch0 + gch * 8, lofs1 = lrow * a.pitch1 + gch * 8;
   auto row_base = [&](int R, int& m0, int& w0) {
     if (R < 0 || R >= a.nrows) { m0 = -1; w0 = 0; return; }
-    const uint32_t col = rdiv((uint32_t)R, a.fh_m, a.fh_s);
+    const uint32_t col = fdiv((uint32_t)R, a.fh_m, a.fh_s);
     const int h = R - (int)col * a.H;
-    const uint32_t n = rdiv(col, a.fs_m, a.fs_s);
+    const uint32_t n = fdiv(col, a.fs_m, a.fs_s);
     const int ws = (int)col - (int)n * a.WS;
     w0 = ws * 64;
     m0 = ((int)n * a.H + h) * a.W + w0;
@@ -880,7 +869,7 @@ __global__ __launch_bounds__(512, 2) void conv_ring2_kernel(const Ring2Args a) {
     if (ks + 1 < nks) issue(P + 1);
 
     const int R0 = 2 * P + orow;
-    const int h = R0 - (int)rdiv((uint32_t)R0, a.fh_m, a.fh_s) * a.H;
+    const int h = R0 - (int)fdiv((uint32_t)R0, a.fh_m, a.fh_s) * a.H;
     const bool top = h == 0, bottom = h == a.H - 1;
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -950,12 +939,7 @@ __global__ __launch_bounds__(512, 2) void conv_ring2_kernel(const Ring2Args a) {
           v[j].x = pack2bf(o[0], o[1]);
           v[j].y = pack2bf(o[2], o[3]);
           if (a.stats) {
-            const float q0 = __uint_as_float(v[j].x << 16), q1 = __uint_as_float(v[j].x & 0xffff0000u);
-            const float q2 = __uint_as_float(v[j].y << 16), q3 = __uint_as_float(v[j].y & 0xffff0000u);
-            s1[j][0] += q0; s2[j][0] += q0 * q0;
-            s1[j][1] += q1; s2[j][1] += q1 * q1;
-            s1[j][2] += q2; s2[j][2] += q2 * q2;
-            s1[j][3] += q3; s2[j][3] += q3 * q3;
+            bn_stats4(v[j], s1[j], s2[j]);
           }
         }
         const auto rxs = __builtin_amdgcn_permlane16_swap(v[0].x, v[1].x, false, false);

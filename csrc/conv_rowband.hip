@@ -26,7 +26,7 @@
 //     tile in LDS for all 9 taps (the serving default wherever the input has 128 or 256k channels);
 //   * conv_rowband_chain_kernel: the persistent multi-layer experiment (measured slower, kept tested).
 // Where the eval dispatch takes them is conv_plan.h's business (rdp_rowband_auto, rdp_rowband_frag_mode).
-#include "common.h"
+#include "vec_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
@@ -57,10 +57,6 @@ struct RowbandArgs {
   int wfrag;   // 1: w is fragment-major (models/unet.py rowband_frag_weights): 16 couts x 1 k-step = 1 KiB
   int segs;    // activation-staged variant: row segments of WB pixels per image row
 };
-
-// tap (0..8) -> (dr, ds) without division
-RDP_DEV int rb_dr(int tap) { return ((tap * 11) >> 5) - 1; }
-RDP_DEV int rb_ds(int tap) { return tap - 3 * ((tap * 11) >> 5) - 1; }
 
 template <int NF, int NPG>
 struct RbFrag {
@@ -113,7 +109,7 @@ RDP_DEV void rowband_tile(const RowbandArgs& a, uint32_t lid, RbSmem<NF, NPG>& s
     const bool live = ks < ks1;
     const int tap = ks >> a.cshift;
     const int cbase = (ks - (tap << a.cshift)) << 5;  // first channel of the k-step (wave-uniform)
-    const int dr = rb_dr(tap), ds = rb_ds(tap);
+    const int dr = tap_dr(tap), ds = tap_ds(tap);
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
       const uint32_t off = live ? wrow[f] + (uint32_t)ks * wstep : RDP_OOB;
@@ -208,14 +204,14 @@ RDP_DEV void rowband_tile(const RowbandArgs& a, uint32_t lid, RbSmem<NF, NPG>& s
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const uint32_t wd = e < 2 ? q[0].x : q[0].y;
-      mx[e] = __uint_as_float((e & 1) ? (wd & 0xffff0000u) : (wd << 16));
+      mx[e] = (e & 1) ? bfhi(wd) : bflo(wd);
     }
 #pragma unroll
     for (int t = 1; t < 4; ++t)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const uint32_t wd = e < 2 ? q[t].x : q[t].y;
-        mx[e] = fmaxf(mx[e], __uint_as_float((e & 1) ? (wd & 0xffff0000u) : (wd << 16)));
+        mx[e] = fmaxf(mx[e], (e & 1) ? bfhi(wd) : bflo(wd));
       }
     const int mo = (img * (a.H >> 1) + (h0 >> 1)) * Wo + wo;
     bstore8(rp, (uint32_t)(mo * a.ppitch + cout0 + 4 * cq) * 2u, make_uint2(pack2bf(mx[0], mx[1]), pack2bf(mx[2], mx[3])));
@@ -414,14 +410,14 @@ __global__ __launch_bounds__(512, 2) void conv_rowband_x_kernel(const RowbandArg
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const uint32_t wd = e < 2 ? qv[0].x : qv[0].y;
-      mx[e] = __uint_as_float((e & 1) ? (wd & 0xffff0000u) : (wd << 16));
+      mx[e] = (e & 1) ? bfhi(wd) : bflo(wd);
     }
 #pragma unroll
     for (int t = 1; t < 4; ++t)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const uint32_t wd = e < 2 ? qv[t].x : qv[t].y;
-        mx[e] = fmaxf(mx[e], __uint_as_float((e & 1) ? (wd & 0xffff0000u) : (wd << 16)));
+        mx[e] = fmaxf(mx[e], (e & 1) ? bfhi(wd) : bflo(wd));
       }
     const int mo = (img * (a.H >> 1) + (h0 >> 1)) * (a.W >> 1) + (w0 >> 1) + wo;
     bstore8(rp, (uint32_t)(mo * a.ppitch + cout0 + 4 * cq) * 2u, make_uint2(pack2bf(mx[0], mx[1]), pack2bf(mx[2], mx[3])));

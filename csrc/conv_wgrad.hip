@@ -23,7 +23,7 @@
 //     the padded MFMAs are not on the critical path of this latency-bound loop.
 // PMC (256^2 x 64ch): ~48 % of wave cycles in s_waitcnt/barrier, i.e. latency-bound on x/dY
 // streamed from HBM with only one K step of lookahead.
-#include "common.h"
+#include "bn_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
@@ -51,8 +51,6 @@ struct WgradArgs {
 };
 
 RDP_DEV int swz(int p) { return (((p >> 1) & 1) << 1) | (((p >> 3) & 1) << 2); }
-
-RDP_DEV uint32_t fdiv2(uint32_t n, uint32_t m, uint32_t s) { return (__umulhi(n, m) + n) >> s; }
 
 // BKP = 64 pixels per K step, double-buffered; 8 waves: waves 2s, 2s+1 split x-subtile s into two
 // 32-column halves (twice the waves per SIMD of a 4-wave block, same LDS footprint).
@@ -117,9 +115,9 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const WgradArgs a) {
       const int g = cpos ^ swz(p);  // global 16-B chunk this lane fetches
       const int m = pbeg + ks * BKP + p;
       const bool mv = m < pend;
-      const uint32_t q = fdiv2((uint32_t)m, a.fw_m, a.fw_s);
+      const uint32_t q = fdiv((uint32_t)m, a.fw_m, a.fw_s);
       const int w = m - (int)q * a.W;
-      const int h = (int)q - (int)fdiv2(q, a.fh_m, a.fh_s) * a.H;
+      const int h = (int)q - (int)fdiv(q, a.fh_m, a.fh_s) * a.H;
       // dY piece
       {
         const uint32_t off = mv ? (uint32_t)(m * a.dypitch + cout0 + g * 8) * 2u : RDP_OOB;
@@ -138,7 +136,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_kernel(const WgradArgs a) {
           dma16_async(rx1, (lds_void*)(buf + sub * SUB + s * 1024), off);
         } else if constexpr (UTR) {  // sub-pixel (dr, ds) of the (2h + uoy, 2w + uox) pixel of du
           ch = s_ch[sub] + g * 8;
-          const int img = (int)fdiv2(q, a.fh_m, a.fh_s);
+          const int img = (int)fdiv(q, a.fh_m, a.fh_s);
           const int px = (img * a.uH2 + 2 * h + a.uoy + dr) * a.uW2 + 2 * w + a.uox + ds;
           const uint32_t off = mv & (bool)s_ok[sub] ? (uint32_t)(px * a.pitch1 + ch) * 2u : RDP_OOB;
           dma16_async(rx1, (lds_void*)(buf + sub * SUB + s * 1024), off);
@@ -435,9 +433,9 @@ __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_halo_kernel(const WgradH
 
   auto issue = [&](int ks, char* buf) {
     const int m0 = (s0 + ks) * 64;  // first pixel of the segment
-    const uint32_t q = fdiv2((uint32_t)m0, a.fw_m, a.fw_s);
+    const uint32_t q = fdiv((uint32_t)m0, a.fw_m, a.fw_s);
     const int w0 = m0 - (int)q * a.W;
-    const int h = (int)q - (int)fdiv2(q, a.fh_m, a.fh_s) * a.H;
+    const int h = (int)q - (int)fdiv(q, a.fh_m, a.fh_s) * a.H;
 #pragma unroll
     for (int t = 0; t < PPW; ++t) {
       const int piece = wave + t * NWV;  // wave-uniform
@@ -449,7 +447,7 @@ __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_halo_kernel(const WgradH
         // keep only pixels of row h + dr (the rest is the zero halo); multi-row segments (W | 64)
         // keep every in-image row and mask the row-crossing taps on the dY side instead.
         const int wj = w0 - 1 + j;
-        const int wq = wj < 0 ? -1 : (int)fdiv2((uint32_t)wj, a.fw_m, a.fw_s);
+        const int wq = wj < 0 ? -1 : (int)fdiv((uint32_t)wj, a.fw_m, a.fw_s);
         const bool ok = (j < 66) & (MULTIROW || wq == 0) & inb(h + r - 1 + wq, a.H);
         const uint32_t off = ok ? (uint32_t)((m0 + (r - 1) * a.W + j - 1) * pitch + ch0 + g * 8) * 2u : RDP_OOB;
         dma16_async(rx, (lds_void*)(buf + r * XREG + pj * 1024), off);
@@ -562,9 +560,9 @@ __global__ __launch_bounds__(BN * 4, 2) void conv_wgrad_ring_kernel(const WgradR
   // position -> (first pixel of the segment, row h); P may be -1 or npos (loads read zeros)
   auto locate = [&](int P, int& m0, int& h, int& w0) {
     const uint32_t up = (uint32_t)max(P, 0);
-    const uint32_t col = fdiv2(up, a.fh_m, a.fh_s);
+    const uint32_t col = fdiv(up, a.fh_m, a.fh_s);
     h = (int)(up - col * (uint32_t)a.H);
-    const uint32_t n = fdiv2(col, a.fs_m, a.fs_s);
+    const uint32_t n = fdiv(col, a.fs_m, a.fs_s);
     const int wseg = (int)(col - n * (uint32_t)a.WS);
     m0 = (((int)n * a.H + h) * a.WS + wseg) * 64;
     w0 = wseg * 64;
@@ -847,15 +845,6 @@ struct FirstWgradArgs {
 };
 constexpr int FWG_NCOLS = RDP_WGRAD_FIRST_NCOLS;
 
-RDP_DEV void fw_unpack8(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
-  }
-}
-
 __global__ __launch_bounds__(256, 2) void wgrad_first_bn_kernel(const FirstWgradArgs a) {
   constexpr int SUB = 64 * 128;  // [64 px][64 bf16]
   constexpr int BUF = 3 * SUB;   // x taps 0..7 | x tap 8 | dz
@@ -875,8 +864,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_first_bn_kernel(const FirstWgrad
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int c = 8 * tc + k;
-    ss[k] = a.coef[128 + c]; hh[k] = a.coef[192 + c];
-    cA[k] = a.coef2[c]; cB[k] = a.coef2[64 + c]; cK[k] = a.coef2[128 + c];
+    ss[k] = a.coef[bn_off(BN_SCALE, 64) + c]; hh[k] = a.coef[bn_off(BN_SHIFT, 64) + c];
+    cA[k] = a.coef2[bn_off(BN2_A, 64) + c]; cB[k] = a.coef2[bn_off(BN2_B, 64) + c];
+    cK[k] = a.coef2[bn_off(BN2_K, 64) + c];
   }
   uint4 vd[2], vy[2];
   auto load_dz = [&](int ks) {
@@ -892,15 +882,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_first_bn_kernel(const FirstWgrad
     for (int u = 0; u < 2; ++u) {
       const int p = tr0 + 32 * u;
       float fd[8], fy[8];
-      fw_unpack8(vd[u], fd);
-      fw_unpack8(vy[u], fy);
+      unpack8(vd[u], fd);
+      unpack8(vy[u], fy);
       uint32_t o[4];
 #pragma unroll
       for (int k = 0; k < 8; k += 2) {
-        const float g0 = fmaf(fy[k], ss[k], hh[k]) > 0.f ? fd[k] : 0.f;
-        const float g1 = fmaf(fy[k + 1], ss[k + 1], hh[k + 1]) > 0.f ? fd[k + 1] : 0.f;
-        o[k / 2] = pack2bf(fmaf(cA[k], g0, fmaf(cB[k], fy[k], cK[k])),
-                           fmaf(cA[k + 1], g1, fmaf(cB[k + 1], fy[k + 1], cK[k + 1])));
+        const float g0 = bn_relu_grad(fd[k], fy[k], ss[k], hh[k]);
+        const float g1 = bn_relu_grad(fd[k + 1], fy[k + 1], ss[k + 1], hh[k + 1]);
+        o[k / 2] = pack2bf(bn_bwd_apply(g0, fy[k], cA[k], cB[k], cK[k]),
+                           bn_bwd_apply(g1, fy[k + 1], cA[k + 1], cB[k + 1], cK[k + 1]));
       }
       *(uint4*)(buf + 2 * SUB + p * 128 + 16 * (tc ^ swz(p))) = make_uint4(o[0], o[1], o[2], o[3]);
     }
@@ -914,9 +904,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_first_bn_kernel(const FirstWgrad
       const int p = pj * 8 + rowl;
       const int g = cpos ^ swz(p);
       const int m = pbeg + ks * 64 + p;
-      const uint32_t q = fdiv2((uint32_t)m, a.fw_m, a.fw_s);
+      const uint32_t q = fdiv((uint32_t)m, a.fw_m, a.fw_s);
       const int w = m - (int)q * a.W;
-      const int h = (int)q - (int)fdiv2(q, a.fh_m, a.fh_s) * a.H;
+      const int h = (int)q - (int)fdiv(q, a.fh_m, a.fh_s) * a.H;
       const int tap = sub * 8 + g;
       const int dr = tap / 3 - 1, ds = tap % 3 - 1;
       const bool ok = (tap < 9) & inb(h + dr, a.H) & inb(w + ds, a.W);

@@ -10,32 +10,21 @@
 // head_bwd: dlogit = (sigmoid(x)-t)/M + dice_w * d(dice)/dx; da[p][c] = dlogit*w[c] (bf16);
 //   per-block partials of dW (64) and db.
 // 8 lanes per pixel (16 B each = 8 channels), so every access is a full 128-B line per pixel.
-#include "common.h"
+#include "bn_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
 
 #define HEAD_C 64
 #define HPX 4  // pixels in flight per 8-lane group in the streaming head kernels
 
-RDP_DEV void unpack8h(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
-
 RDP_DEV float dot8(const uint4& v, const float* w) {
   float f[8];
-  unpack8h(v, f);
+  unpack8(v, f);
   float s = 0.f;
 #pragma unroll
   for (int k = 0; k < 8; ++k) s = fmaf(f[k], w[k], s);
   return s;
 }
-
-RDP_DEV float bfround(float f) { return __uint_as_float(((uint32_t)f2bf(f)) << 16); }
 
 RDP_DEV float sum8lanes(float v) {  // reduce across the 8 lanes of a pixel group
   v += __shfl_xor(v, 1, 64);
@@ -45,17 +34,13 @@ RDP_DEV float sum8lanes(float v) {  // reduce across the 8 lanes of a pixel grou
 }
 
 // BN = true (training): `a` holds the last conv's PRE-BN output y and coef its BN coefficients
-// [mean | invstd | scale | shift] (64 each); the head applies a = bf16(relu(y*scale + shift)) itself,
+// (bn_dev.h layout, 64 each); the head applies a = bf16(relu(y*scale + shift)) itself,
 // so that activation is never written or re-read (up4.conv.double_conv.3 -> outc).
-RDP_DEV uint4 bn_relu8(const uint4& v, const float* ss, const float* hh) {
+RDP_DEV uint4 bn_relu8(const uint4& v, const float (&ss)[8], const float (&hh)[8]) {
   float f[8];
-  unpack8h(v, f);
-  uint4 o;
-  o.x = pack2bf(fmaxf(fmaf(f[0], ss[0], hh[0]), 0.f), fmaxf(fmaf(f[1], ss[1], hh[1]), 0.f));
-  o.y = pack2bf(fmaxf(fmaf(f[2], ss[2], hh[2]), 0.f), fmaxf(fmaf(f[3], ss[3], hh[3]), 0.f));
-  o.z = pack2bf(fmaxf(fmaf(f[4], ss[4], hh[4]), 0.f), fmaxf(fmaf(f[5], ss[5], hh[5]), 0.f));
-  o.w = pack2bf(fmaxf(fmaf(f[6], ss[6], hh[6]), 0.f), fmaxf(fmaf(f[7], ss[7], hh[7]), 0.f));
-  return o;
+  unpack8(v, f);
+  bn_relu_n(f, ss, hh);
+  return pack8(f);
 }
 
 // GRAD (training, BN-fused, BCE only -- d loss / d logit is then local, (sigmoid(x) - t) / M): the
@@ -75,11 +60,9 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const u16* __restrict__ a
   const int sub = lane & 7;
   float wl[8], ss[8], hh[8], mu[8], iv[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    wl[k] = w[sub * 8 + k];
-    if (BN) { ss[k] = coef[2 * HEAD_C + sub * 8 + k]; hh[k] = coef[3 * HEAD_C + sub * 8 + k]; }
-    if (GRAD) { mu[k] = coef[sub * 8 + k]; iv[k] = coef[HEAD_C + sub * 8 + k]; }
-  }
+  for (int k = 0; k < 8; ++k) wl[k] = w[sub * 8 + k];
+  if (BN) { bn_ld8(coef, BN_SCALE, HEAD_C, sub * 8, ss); bn_ld8(coef, BN_SHIFT, HEAD_C, sub * 8, hh); }
+  if (GRAD) { bn_ld8(coef, BN_MEAN, HEAD_C, sub * 8, mu); bn_ld8(coef, BN_INVSTD, HEAD_C, sub * 8, iv); }
   const float bias = b[0];
   const float gs = gscale / (float)M;
   float sb = 0.f, si = 0.f, sp = 0.f, st = 0.f;
@@ -113,14 +96,11 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const u16* __restrict__ a
         const float sgm = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
         const float dx = (sgm - tq[u]) * gs;
         float fy[8];
-        unpack8h(v[u], fy);
+        unpack8(v[u], fy);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          const float z = fmaf(fy[k], ss[k], hh[k]);
-          gw[k] = fmaf(dx, bfround(fmaxf(z, 0.f)), gw[k]);
-          const float g = z > 0.f ? bfround(dx * wl[k]) : 0.f;
-          sg[k] += g;
-          sgx[k] += g * (fy[k] - mu[k]) * iv[k];
+          gw[k] = fmaf(dx, bn_relu_bf(fy[k], ss[k], hh[k]), gw[k]);
+          bn_acc(bn_relu_grad(bfround(dx * wl[k]), fy[k], ss[k], hh[k]), fy[k], mu[k], iv[k], sg[k], sgx[k]);
         }
         if (sub == 0) gb += dx;
       }
@@ -240,14 +220,12 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const u16* __restrict__ a
   const int sub = lane & 7;
   float wl[8], mu[8], iv[8], ss[8], hh[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    wl[k] = w[sub * 8 + k];
-    if (BN) {
-      mu[k] = coef[sub * 8 + k];
-      iv[k] = coef[HEAD_C + sub * 8 + k];
-      ss[k] = coef[2 * HEAD_C + sub * 8 + k];
-      hh[k] = coef[3 * HEAD_C + sub * 8 + k];
-    }
+  for (int k = 0; k < 8; ++k) wl[k] = w[sub * 8 + k];
+  if (BN) {
+    bn_ld8(coef, BN_MEAN, HEAD_C, sub * 8, mu);
+    bn_ld8(coef, BN_INVSTD, HEAD_C, sub * 8, iv);
+    bn_ld8(coef, BN_SCALE, HEAD_C, sub * 8, ss);
+    bn_ld8(coef, BN_SHIFT, HEAD_C, sub * 8, hh);
   }
   const float invM = 1.f / (float)M;
   float I = 0.f, U = 0.f;
@@ -278,28 +256,23 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const u16* __restrict__ a
       float f[8];
       if (BN) {
         float fy[8];
-        unpack8h(vy, fy);
+        unpack8(vy, fy);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          const float z = fmaf(fy[k], ss[k], hh[k]);
-          f[k] = bfround(fmaxf(z, 0.f));  // the activation the forward head consumed
-          const float g = z > 0.f ? bfround(dx * wl[k]) : 0.f;
-          sg[k] += g;
-          sgx[k] += g * (fy[k] - mu[k]) * iv[k];
+          f[k] = bn_relu_bf(fy[k], ss[k], hh[k]);  // the activation the forward head consumed
+          bn_acc(bn_relu_grad(bfround(dx * wl[k]), fy[k], ss[k], hh[k]), fy[k], mu[k], iv[k], sg[k], sgx[k]);
         }
       } else {
-        unpack8h(vy, f);
+        unpack8(vy, f);
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) gw[k] = fmaf(dx, f[k], gw[k]);
       if (sub == 0) gb += dx;
       if (!BN) {
-        uint4 o;
-        o.x = pack2bf(dx * wl[0], dx * wl[1]);
-        o.y = pack2bf(dx * wl[2], dx * wl[3]);
-        o.z = pack2bf(dx * wl[4], dx * wl[5]);
-        o.w = pack2bf(dx * wl[6], dx * wl[7]);
-        *(uint4*)(da + (size_t)p * dapitch + sub * 8) = o;
+        float o[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = dx * wl[k];
+        *(uint4*)(da + (size_t)p * dapitch + sub * 8) = pack8(o);
       }
     }
   }
@@ -361,14 +334,9 @@ __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(const u16* __res
   const int c = (threadIdx.x & 7) * 8;
   float wl[8], ss[8], hh[8], A[8], B[8], K[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    wl[k] = w[c + k];
-    ss[k] = coef[2 * HEAD_C + c + k];
-    hh[k] = coef[3 * HEAD_C + c + k];
-    A[k] = coef2[c + k];
-    B[k] = coef2[HEAD_C + c + k];
-    K[k] = coef2[2 * HEAD_C + c + k];
-  }
+  for (int k = 0; k < 8; ++k) wl[k] = w[c + k];
+  bn_ld8(coef, BN_SCALE, HEAD_C, c, ss); bn_ld8(coef, BN_SHIFT, HEAD_C, c, hh);
+  bn_ld8(coef2, BN2_A, HEAD_C, c, A); bn_ld8(coef2, BN2_B, HEAD_C, c, B); bn_ld8(coef2, BN2_K, HEAD_C, c, K);
   const float invM = 1.f / (float)M;
   float I = 0.f, U = 0.f;
   if (dice_w != 0.f) { I = sums[1]; U = sums[2] + sums[3]; }
@@ -393,18 +361,14 @@ __global__ __launch_bounds__(256) void head_bn_bwd_apply_kernel(const u16* __res
       if (p < M) {
         const float dx = head_dlogit(x[u], t[u], invM, dice_w, I, den, dice_eps, gscale);
         float fy[8], o[8];
-        unpack8h(vy[u], fy);
+        unpack8(vy[u], fy);
+        // = bn_bwd_apply(bn_relu_grad(..)) of bn_dev.h, by hand (speed: profiles/pass_dev.md)
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const float g = fmaf(fy[k], ss[k], hh[k]) > 0.f ? bfround(dx * wl[k]) : 0.f;
           o[k] = fmaf(A[k], g, fmaf(B[k], fy[k], K[k]));
         }
-        uint4 v;
-        v.x = pack2bf(o[0], o[1]);
-        v.y = pack2bf(o[2], o[3]);
-        v.z = pack2bf(o[4], o[5]);
-        v.w = pack2bf(o[6], o[7]);
-        *(uint4*)(dy + (size_t)p * dypitch + c) = v;
+        *(uint4*)(dy + (size_t)p * dypitch + c) = pack8(o);
       }
     }
   }

@@ -46,7 +46,7 @@
 
 namespace {
 
-// unpack8h, pow2_classes, reduce_transpose, lane_logit, argmax_lowest: shared with the row-ring conv's fused
+// pow2_classes, reduce_transpose, lane_logit, argmax_lowest: shared with the row-ring conv's fused
 // K-class head, which must reproduce headk_mask_kernel's bits (head_multi_dev.h)
 using namespace rdp_headk;
 
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void headk_fwd_kernel(const u16* __restrict__ 
     for (int u = 0; u < HPX; ++u) {  // every lane runs the shuffles (zeros past M); only stores are guarded
       const long p = p0 + u * stride;
       float f[8];
-      unpack8h(v[u], f);
+      unpack8(v[u], f);
       const float x = lane_logit<K>(f, wl, sub) + bias;
       float mx = own ? x : -INFINITY;
 #pragma unroll
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256) void headk_bwd_kernel(const u16* __restrict__ 
         }
         const float inv = 1.f / se;
         float f[8];
-        unpack8h(vq[u], f);
+        unpack8(vq[u], f);
         [[maybe_unused]] float wt = 0.f, dot = 0.f, G[K];
         if constexpr (EXT) {
 #pragma unroll
@@ -391,7 +391,7 @@ __global__ __launch_bounds__(256) void headk_mask_kernel(const u16* __restrict__
   for (long p = blockIdx.x * 32l + (threadIdx.x >> 3); p < M; p += stride) {
     const uint4 v = *(const uint4*)(a + (size_t)p * apitch + sub * 8);
     float f[8];
-    unpack8h(v, f);
+    unpack8(v, f);
     const int idx = argmax_lowest<K>(lane_logit<K>(f, wl, sub) + bias, sub);
     if (sub == 0) mask[p] = idx == cls ? 1 : 0;
   }

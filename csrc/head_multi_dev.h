@@ -11,18 +11,9 @@
 // Layout both callers use: 8 lanes per pixel, lane `sub` (= lane & 7) holds the pixel's channels
 // 8 sub .. 8 sub + 7 (one 16-B read of 8 bf16) and the head weights wl[k][j] = w[k][8 sub + j].
 #pragma once
-#include "common.h"
+#include "vec_dev.h"
 
 namespace rdp_headk {
-
-RDP_DEV void unpack8h(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
 
 constexpr int pow2_classes(int K) { return K <= 2 ? 2 : K <= 4 ? 4 : 8; }
 

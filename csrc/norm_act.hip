@@ -8,7 +8,7 @@
 // (conv_igemm.hip); bn_finalize reduces them in fp64, updates running stats and emits the
 // per-channel affine (scale, shift) applied by bn_relu_apply. Backward is a two-pass
 // reduce (sum g, sum g*xhat) -> finalize (dgamma, dbeta, 3 apply coefficients) -> apply.
-#include "common.h"
+#include "bn_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
@@ -121,36 +121,46 @@ static const float* shrink_rows(const float* in, int T, int K, float* ws, int& r
   return ws;
 }
 
-// coef layout: [0:C) mean, [C:2C) invstd, [2C:3C) scale = gamma*invstd, [3C:4C) shift = beta - mean*scale
-// CPB channels per block, 1024 / CPB row groups. (16 channels per block -- four times the row groups --
-// measured neutral: the ~7 us per finalize is the kernel boundary, not the row walk.)
+// Both finalize kernels: channel c = blockIdx.x * CPB + tx of the block, s / q = the fp64 sums of the
+// T rows' two halves. True on the one thread (ty == 0, c < C) that holds them.
+template <int CPB>
+RDP_DEV bool fin_block_sums(const float* __restrict__ p, int T, int C, int& c, double& s, double& q) {
+  constexpr int RG = 64 * FIN_RG / CPB;
+  __shared__ double red[2][RG][CPB];
+  const int tx = threadIdx.x % CPB, ty = threadIdx.x / CPB;
+  c = blockIdx.x * CPB + tx;
+  s = 0.0;
+  q = 0.0;
+  if (c < C) fin_rows<RG>(p, T, C, c, ty, s, q);
+  red[0][ty][tx] = s;
+  red[1][ty][tx] = q;
+  __syncthreads();
+  if (ty != 0 || c >= C) return false;
+  s = 0.0;
+  q = 0.0;
+  for (int g = 0; g < RG; ++g) { s += red[0][g][tx]; q += red[1][g][tx]; }
+  return true;
+}
+
+// coef layout: bn_dev.h. CPB channels per block, 1024 / CPB row groups. (16 channels per block -- four
+// times the row groups -- measured neutral: the ~7 us per finalize is the kernel boundary, not the row walk.)
 template <int CPB>
 __global__ __launch_bounds__(64 * FIN_RG) void bn_finalize_kernel(const float* __restrict__ stats, int T, int C, double count,
                                    const float* __restrict__ gamma, const float* __restrict__ beta,
                                    float* __restrict__ rmean, float* __restrict__ rvar, long long* nbt,
                                    float momentum, float eps, float* __restrict__ coef) {
-  constexpr int RG = 64 * FIN_RG / CPB;
-  __shared__ double red[2][RG][CPB];
-  const int tx = threadIdx.x % CPB, ty = threadIdx.x / CPB;
-  const int c = blockIdx.x * CPB + tx;
-  double s = 0.0, q = 0.0;
-  if (c < C) fin_rows<RG>(stats, T, C, c, ty, s, q);
-  red[0][ty][tx] = s;
-  red[1][ty][tx] = q;
-  __syncthreads();
-  if (ty == 0 && c < C) {
-    s = 0.0;
-    q = 0.0;
-    for (int g = 0; g < RG; ++g) { s += red[0][g][tx]; q += red[1][g][tx]; }
+  int c;
+  double s, q;
+  if (fin_block_sums<CPB>(stats, T, C, c, s, q)) {
     const double mean = s / count;
     double var = q / count - mean * mean;
     if (var < 0.0) var = 0.0;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
     const float sc = gamma[c] * invstd;
-    coef[c] = (float)mean;
-    coef[C + c] = invstd;
-    coef[2 * C + c] = sc;
-    coef[3 * C + c] = beta[c] - (float)mean * sc;
+    coef[bn_off(BN_MEAN, C) + c] = (float)mean;
+    coef[bn_off(BN_INVSTD, C) + c] = invstd;
+    coef[bn_off(BN_SCALE, C) + c] = sc;
+    coef[bn_off(BN_SHIFT, C) + c] = beta[c] - (float)mean * sc;
     if (rmean) {
       const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
       rmean[c] = (1.f - momentum) * rmean[c] + momentum * (float)mean;
@@ -167,32 +177,10 @@ __global__ void bn_eval_coef_kernel(int C, const float* gamma, const float* beta
   if (c >= C) return;
   const float invstd = 1.0f / sqrtf(rvar[c] + eps);
   const float sc = gamma[c] * invstd;
-  coef[c] = rmean[c];
-  coef[C + c] = invstd;
-  coef[2 * C + c] = sc;
-  coef[3 * C + c] = beta[c] - rmean[c] * sc;
-}
-
-RDP_DEV void unpack8(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
-RDP_DEV uint4 pack8(const float* f) {
-  uint4 v;
-  v.x = pack2bf(f[0], f[1]);
-  v.y = pack2bf(f[2], f[3]);
-  v.z = pack2bf(f[4], f[5]);
-  v.w = pack2bf(f[6], f[7]);
-  return v;
-}
-
-RDP_DEV void ld8(const float* p, float* f) {
-  const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+  coef[bn_off(BN_MEAN, C) + c] = rmean[c];
+  coef[bn_off(BN_INVSTD, C) + c] = invstd;
+  coef[bn_off(BN_SCALE, C) + c] = sc;
+  coef[bn_off(BN_SHIFT, C) + c] = beta[c] - rmean[c] * sc;
 }
 
 // a = relu(y*scale + shift), 8 channels per thread
@@ -208,8 +196,8 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const u16* __restric
   const int g = threadIdx.x & (CG - 1), r = threadIdx.x / CG;
   const int c = g * 8;
   float ss[8], hh[8];
-  ld8(coef + 2 * C + c, ss);
-  ld8(coef + 3 * C + c, hh);
+  bn_ld8(coef, BN_SCALE, C, c, ss);
+  bn_ld8(coef, BN_SHIFT, C, c, hh);
   // chunk > 0: block b walks pixels [b * chunk, (b + 1) * chunk) contiguously (RPB * APX per step)
   const int stride = chunk ? RPB : gridDim.x * RPB;
   const int pbeg = chunk ? blockIdx.x * chunk : blockIdx.x * RPB;
@@ -227,11 +215,7 @@ __global__ __launch_bounds__(256) void bn_relu_apply_kernel(const u16* __restric
       if (p < pend) {
         float f[8];
         unpack8(v[u], f);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float z = fmaf(f[k], ss[k], hh[k]);
-          f[k] = relu ? fmaxf(z, 0.f) : z;
-        }
+        bn_relu_n(f, ss, hh, relu);
         *(uint4*)(out + (size_t)p * opitch + c) = pack8(f);
       }
     }
@@ -251,11 +235,11 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const u16* __re
   const int c = g * 8;
   float mean[8], inv[8], ss[8], hh[8];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    mean[k] = coef[c + k];
-    inv[k] = coef[C + c + k];
-    ss[k] = coef[2 * C + c + k];
-    hh[k] = coef[3 * C + c + k];
+  for (int k = 0; k < 8; ++k) {  // (scalar loads and the fold below by hand, speed: profiles/pass_dev.md)
+    mean[k] = coef[bn_off(BN_MEAN, C) + c + k];
+    inv[k] = coef[bn_off(BN_INVSTD, C) + c + k];
+    ss[k] = coef[bn_off(BN_SCALE, C) + c + k];
+    hh[k] = coef[bn_off(BN_SHIFT, C) + c + k];
   }
   float sg[8], sgx[8];
 #pragma unroll
@@ -265,12 +249,7 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_reduce_kernel(const u16* __re
       float fd[8], fy[8];
       unpack8(*(const uint4*)(da + (size_t)p * dapitch + c), fd);
       unpack8(*(const uint4*)(y + (size_t)p * ypitch + c), fy);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const float gg = (!relu || fmaf(fy[k], ss[k], hh[k]) > 0.f) ? fd[k] : 0.f;
-        sg[k] += gg;
-        sgx[k] += gg * (fy[k] - mean[k]) * inv[k];
-      }
+      bn_acc_n(fd, fy, mean, inv, ss, hh, sg, sgx, relu);
     }
   }
   const int R = rows;
@@ -297,27 +276,17 @@ __global__ __launch_bounds__(64 * FIN_RG) void bn_bwd_finalize_kernel(const floa
                                        const float* __restrict__ gamma, const float* __restrict__ coef,
                                        float* __restrict__ dgamma, float* __restrict__ dbeta,
                                        float* __restrict__ coef2) {
-  constexpr int RG = 64 * FIN_RG / CPB;
-  __shared__ double red[2][RG][CPB];
-  const int tx = threadIdx.x % CPB, ty = threadIdx.x / CPB;
-  const int c = blockIdx.x * CPB + tx;
-  double s = 0.0, q = 0.0;
-  if (c < C) fin_rows<RG>(partial, T, C, c, ty, s, q);
-  red[0][ty][tx] = s;
-  red[1][ty][tx] = q;
-  __syncthreads();
-  if (ty == 0 && c < C) {
-    s = 0.0;
-    q = 0.0;
-    for (int g = 0; g < RG; ++g) { s += red[0][g][tx]; q += red[1][g][tx]; }
+  int c;
+  double s, q;
+  if (fin_block_sums<CPB>(partial, T, C, c, s, q)) {
     if (dbeta) dbeta[c] = (float)s;
     if (dgamma) dgamma[c] = (float)q;
-    const double mean = coef[c], inv = coef[C + c], gm = gamma[c];
+    const double mean = coef[bn_off(BN_MEAN, C) + c], inv = coef[bn_off(BN_INVSTD, C) + c], gm = gamma[c];
     const double A = gm * inv;
     const double mg = s / count, mgx = q / count;
-    coef2[c] = (float)A;
-    coef2[C + c] = (float)(-A * inv * mgx);
-    coef2[2 * C + c] = (float)(-A * mg + A * inv * mgx * mean);
+    coef2[bn_off(BN2_A, C) + c] = (float)A;
+    coef2[bn_off(BN2_B, C) + c] = (float)(-A * inv * mgx);
+    coef2[bn_off(BN2_K, C) + c] = (float)(-A * mg + A * inv * mgx * mean);
   }
 }
 
@@ -331,8 +300,8 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const u16* __res
   const int g = threadIdx.x & (CG - 1), r = threadIdx.x / CG;
   const int c = g * 8;
   float ss[8], hh[8], A[8], B[8], K[8];
-  ld8(coef + 2 * C + c, ss); ld8(coef + 3 * C + c, hh);
-  ld8(coef2 + c, A); ld8(coef2 + C + c, B); ld8(coef2 + 2 * C + c, K);
+  bn_ld8(coef, BN_SCALE, C, c, ss); bn_ld8(coef, BN_SHIFT, C, c, hh);
+  bn_ld8(coef2, BN2_A, C, c, A); bn_ld8(coef2, BN2_B, C, c, B); bn_ld8(coef2, BN2_K, C, c, K);
   const int stride = chunk ? RPB : gridDim.x * RPB;  // (see bn_relu_apply_kernel)
   const int pbeg = chunk ? blockIdx.x * chunk : blockIdx.x * RPB;
   const int pend = chunk ? min(M, pbeg + chunk) : M;
@@ -354,17 +323,13 @@ __global__ __launch_bounds__(256) void bn_relu_bwd_apply_kernel(const u16* __res
         unpack8(vd[u], fd);
         unpack8(vy[u], fy);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float gg = (!relu || fmaf(fy[k], ss[k], hh[k]) > 0.f) ? fd[k] : 0.f;
-          o[k] = fmaf(A[k], gg, fmaf(B[k], fy[k], K[k]));
-        }
+        for (int k = 0; k < 8; ++k)
+          o[k] = bn_bwd_apply(bn_relu_grad(fd[k], fy[k], ss[k], hh[k], relu), fy[k], A[k], B[k], K[k]);
         *(uint4*)(dy + (size_t)p * dypitch + c) = pack8(o);
       }
     }
   }
 }
-
-static bool pow2_channels(int C) { return C >= 8 && C <= 2048 && (C & (C - 1)) == 0; }
 
 static int grid_px(long M, int C) {  // blocks for the pixel-walking elementwise kernels
   const long rpb = 256 / (C / 8);

@@ -10,7 +10,7 @@
 // wprep builds the derived bf16 layouts from the fp32 masters in one launch (segment table):
 //   kind 0: dgrad weights  Wt[cin][8-tap][cout] = W[cout][tap][cin]   (flip + transpose)
 //   kind 1: packed first layer  Wp[cout][16][8] (taps 0..8, channels 0..cin-1, zeros elsewhere)
-#include "common.h"
+#include "vec_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
 #include <stdlib.h>
@@ -33,9 +33,7 @@
     if constexpr (sizeof(G) == 4) {                                                                              \
       gg = ((const float4*)g)[i];                                                                                \
     } else {                                                                                                     \
-      const uint2 gb = ((const uint2*)g)[i];                                                                     \
-      gg = make_float4(__uint_as_float(gb.x << 16), __uint_as_float(gb.x & 0xffff0000u),                         \
-                       __uint_as_float(gb.y << 16), __uint_as_float(gb.y & 0xffff0000u));                        \
+      unpack4(((const uint2*)g)[i], &gg.x);                                                                      \
     }                                                                                                            \
     float* pa = &pp.x; float* ga = &gg.x; float* ma = &mm.x; float* va = &vv.x;                                  \
     _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                              \
@@ -94,9 +92,7 @@ __global__ __launch_bounds__(256) void grad_sqnorm_kernel(const G* __restrict__ 
     if constexpr (sizeof(G) == 4) {
       gg = ((const float4*)g)[i];
     } else {
-      const uint2 gb = ((const uint2*)g)[i];
-      gg = make_float4(__uint_as_float(gb.x << 16), __uint_as_float(gb.x & 0xffff0000u),
-                       __uint_as_float(gb.y << 16), __uint_as_float(gb.y & 0xffff0000u));
+      unpack4(((const uint2*)g)[i], &gg.x);
     }
     acc = fma((double)gg.x, (double)gg.x, acc);
     acc = fma((double)gg.y, (double)gg.y, acc);

@@ -10,26 +10,10 @@
 //     i1 = i0 + (i0 < in-1); the x2 output is placed at offset (oy, ox) inside the skip's H2 x W2
 //     (F.pad with [dx//2, dx-dx//2, dy//2, dy-dy//2]); the rest is zero. Backward is a
 //     deterministic gather (no atomics) that re-derives the forward's exact index/weight arithmetic.
-#include "common.h"
+#include "bn_dev.h"
+#include "pool_dev.h"
 #include "rdp_api.h"
 #include <algorithm>
-
-RDP_DEV void unpack8f(const uint4& v, float* f) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(w[k] << 16);
-    f[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u);
-  }
-}
-RDP_DEV uint4 pack8f(const float* f) {
-  uint4 v;
-  v.x = pack2bf(f[0], f[1]);
-  v.y = pack2bf(f[2], f[3]);
-  v.z = pack2bf(f[4], f[5]);
-  v.w = pack2bf(f[6], f[7]);
-  return v;
-}
 
 __global__ void maxpool2_fwd_kernel(const u16* __restrict__ x, int xpitch, u16* __restrict__ out, int opitch, int N,
                                     int H, int W, int C) {
@@ -44,20 +28,14 @@ __global__ void maxpool2_fwd_kernel(const u16* __restrict__ x, int xpitch, u16* 
     const long p00 = ((long)n * H + 2 * ho) * W + 2 * wo;
     const int c = g * 8;
     float v[4][8];
-    unpack8f(*(const uint4*)(x + p00 * xpitch + c), v[0]);
-    unpack8f(*(const uint4*)(x + (p00 + 1) * xpitch + c), v[1]);
-    unpack8f(*(const uint4*)(x + (p00 + W) * xpitch + c), v[2]);
-    unpack8f(*(const uint4*)(x + (p00 + W + 1) * xpitch + c), v[3]);
+    unpack8(*(const uint4*)(x + p00 * xpitch + c), v[0]);
+    unpack8(*(const uint4*)(x + (p00 + 1) * xpitch + c), v[1]);
+    unpack8(*(const uint4*)(x + (p00 + W) * xpitch + c), v[2]);
+    unpack8(*(const uint4*)(x + (p00 + W + 1) * xpitch + c), v[3]);
     float o[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float m = v[0][k];
-#pragma unroll
-      for (int q = 1; q < 4; ++q)
-        if (v[q][k] > m || isnan(v[q][k])) m = v[q][k];
-      o[k] = m;
-    }
-    *(uint4*)(out + po * opitch + c) = pack8f(o);
+    for (int k = 0; k < 8; ++k) o[k] = max4(v[0][k], v[1][k], v[2][k], v[3][k]);
+    *(uint4*)(out + po * opitch + c) = pack8(o);
   }
 }
 
@@ -80,12 +58,13 @@ __global__ void maxpool2_bwd_kernel(const u16* __restrict__ dp, int dppitch, con
     int idx[8];
     if (pooled) {
       const long p00 = ((long)n * H + 2 * hc) * W + 2 * wc;
-      unpack8f(*(const uint4*)(x + p00 * xpitch + c), v[0]);
-      unpack8f(*(const uint4*)(x + (p00 + 1) * xpitch + c), v[1]);
-      unpack8f(*(const uint4*)(x + (p00 + W) * xpitch + c), v[2]);
-      unpack8f(*(const uint4*)(x + (p00 + W + 1) * xpitch + c), v[3]);
+      unpack8(*(const uint4*)(x + p00 * xpitch + c), v[0]);
+      unpack8(*(const uint4*)(x + (p00 + 1) * xpitch + c), v[1]);
+      unpack8(*(const uint4*)(x + (p00 + W) * xpitch + c), v[2]);
+      unpack8(*(const uint4*)(x + (p00 + W + 1) * xpitch + c), v[3]);
       const long po = ((long)n * Ho + hc) * Wo + wc;
-      unpack8f(*(const uint4*)(dp + po * dppitch + c), d);
+      unpack8(*(const uint4*)(dp + po * dppitch + c), d);
+      // = the max4 rule (pool_dev.h) with its index, by hand (speed: profiles/pass_dev.md)
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float m = v[0][k];
@@ -102,14 +81,14 @@ __global__ void maxpool2_bwd_kernel(const u16* __restrict__ dp, int dppitch, con
       if (hh >= H || ww >= W) continue;
       const long p = ((long)n * H + hh) * W + ww;
       float s[8];
-      if (dskip) unpack8f(*(const uint4*)(dskip + p * dspitch + c), s);
+      if (dskip) unpack8(*(const uint4*)(dskip + p * dspitch + c), s);
       else {
 #pragma unroll
         for (int k = 0; k < 8; ++k) s[k] = 0.f;
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) o[q][k] = s[k] + ((pooled && idx[k] == q) ? d[k] : 0.f);
-      *(uint4*)(dx + p * dxpitch + c) = pack8f(o[q]);
+      *(uint4*)(dx + p * dxpitch + c) = pack8(o[q]);
     }
   }
 }
@@ -122,11 +101,6 @@ __global__ void maxpool2_bwd_kernel(const u16* __restrict__ dp, int dppitch, con
 // backward reduction (sum g, sum g*xhat over the ReLU mask) runs in the same pass on the values it
 // just produced instead of re-reading them. Each thread owns one 8-channel group for the launch
 // (coefficients in registers) and walks 2x2 windows with a grid stride; C is a power of two.
-RDP_DEV void ld8f(const float* p, float* f) {
-  const float4 a = *(const float4*)p, b = *(const float4*)(p + 4);
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-}
-
 __global__ __launch_bounds__(256) void bn_relu_apply_pool_kernel(const u16* __restrict__ y, int ypitch,
                                                                  u16* __restrict__ a, int apitch,
                                                                  u16* __restrict__ pool, int ppitch,
@@ -136,8 +110,8 @@ __global__ __launch_bounds__(256) void bn_relu_apply_pool_kernel(const u16* __re
   const int g = threadIdx.x & (CG - 1), r = threadIdx.x / CG;
   const int c = g * 8;
   float ss[8], hh[8];
-  ld8f(coef + 2 * C + c, ss);
-  ld8f(coef + 3 * C + c, hh);
+  bn_ld8(coef, BN_SCALE, C, c, ss);
+  bn_ld8(coef, BN_SHIFT, C, c, hh);
   const int Ho = H / 2, Wo = W / 2, Hc = (H + 1) / 2, Wc = (W + 1) / 2;
   const int nwin = N * Hc * Wc;
   for (int wi = blockIdx.x * RPB + r; wi < nwin; wi += gridDim.x * RPB) {
@@ -158,12 +132,13 @@ __global__ __launch_bounds__(256) void bn_relu_apply_pool_kernel(const u16* __re
     for (int q = 0; q < 4; ++q) {
       if (!ok[q]) continue;
       float f[8];
-      unpack8f(v[q], f);
+      unpack8(v[q], f);
+      // = bn_relu (bn_dev.h) and, below, max4 (pool_dev.h), by hand (speed: profiles/pass_dev.md)
 #pragma unroll
       for (int k = 0; k < 8; ++k) f[k] = fmaxf(fmaf(f[k], ss[k], hh[k]), 0.f);
-      const uint4 o = pack8f(f);
+      const uint4 o = pack8(f);
       if (a) *(uint4*)(a + px[q] * apitch + c) = o;  // a == nullptr: pool only (the caller writes a elsewhere)
-      unpack8f(o, av[q]);  // the pool sees exactly the stored (bf16) activation
+      unpack8(o, av[q]);  // the pool sees exactly the stored (bf16) activation
     }
     if (hc < Ho && wc < Wo) {
       float o[8];
@@ -175,7 +150,7 @@ __global__ __launch_bounds__(256) void bn_relu_apply_pool_kernel(const u16* __re
           if (av[q][k] > m || isnan(av[q][k])) m = av[q][k];
         o[k] = m;
       }
-      *(uint4*)(pool + (((long)n * Ho + hc) * Wo + wc) * ppitch + c) = pack8f(o);
+      *(uint4*)(pool + (((long)n * Ho + hc) * Wo + wc) * ppitch + c) = pack8(o);
     }
   }
 }
@@ -193,10 +168,11 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_bn_reduce_kernel(
   const int g = threadIdx.x & (CG - 1), r = threadIdx.x / CG;
   const int c = g * 8;
   float mean[8], inv[8], ss[8], hh[8];
-  ld8f(coef + c, mean);
-  ld8f(coef + C + c, inv);
-  ld8f(coef + 2 * C + c, ss);
-  ld8f(coef + 3 * C + c, hh);
+  bn_ld8(coef, BN_MEAN, C, c, mean);
+  bn_ld8(coef, BN_INVSTD, C, c, inv);
+  bn_ld8(coef, BN_SCALE, C, c, ss);
+  bn_ld8(coef, BN_SHIFT, C, c, hh);
+  // below = bn_relu / max4 with its index / bn_acc_n (bn_dev.h, pool_dev.h), by hand (speed: profiles/pass_dev.md)
   float sg[8], sgx[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { sg[k] = 0.f; sgx[k] = 0.f; }
@@ -229,12 +205,12 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_bn_reduce_kernel(
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         float f[8];
-        unpack8f(vy[q], f);
+        unpack8(vy[q], f);
 #pragma unroll
         for (int k = 0; k < 8; ++k) f[k] = fmaxf(fmaf(f[k], ss[k], hh[k]), 0.f);
-        unpack8f(pack8f(f), v[q]);
+        unpack8(pack8(f), v[q]);
       }
-      unpack8f(vd, d);
+      unpack8(vd, d);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float m = v[0][k];
@@ -249,13 +225,13 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_bn_reduce_kernel(
     for (int q = 0; q < 4; ++q) {
       if (!ok[q]) continue;
       float sk[8], o[8], fy[8];
-      unpack8f(vs[q], sk);
+      unpack8(vs[q], sk);
 #pragma unroll
       for (int k = 0; k < 8; ++k) o[k] = sk[k] + ((pooled && idx[k] == q) ? d[k] : 0.f);
-      const uint4 ov = pack8f(o);
+      const uint4 ov = pack8(o);
       *(uint4*)(dx + px[q] * dxpitch + c) = ov;
-      unpack8f(ov, o);  // reduce the stored (bf16) gradient, as the standalone reduce would
-      unpack8f(vy[q], fy);
+      unpack8(ov, o);  // reduce the stored (bf16) gradient, as the standalone reduce would
+      unpack8(vy[q], fy);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float gg = fmaf(fy[k], ss[k], hh[k]) > 0.f ? o[k] : 0.f;
@@ -283,13 +259,6 @@ struct UpGeom {
   float rh, rw;
 };
 
-RDP_DEV void up_src(int u, int in, float r, int& i0, int& i1, float& l1) {
-  const float s = r * (float)u;
-  i0 = (int)s;
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-}
-
 // Row-blocked bilinear x2 (align_corners=True). One work item = one output (fwd) / input-gradient
 // (bwd) image row segment of 256 (pixel, 8-channel group) pairs: the row's source rows and weights
 // are block-uniform (scalar), channel groups are a power of two, so the per-thread indexing is shifts
@@ -297,11 +266,6 @@ RDP_DEV void up_src(int u, int in, float r, int& i0, int& i1, float& l1) {
 // coef != nullptr: x is the producing layer's PRE-BN output; its training BN + ReLU (coef =
 // [mean|invstd|scale|shift]) is applied to each tap and rounded to bf16 exactly as bn_relu_apply would
 // store it, so the post-activation tensor of the layer below every Up block is never materialised.
-RDP_DEV void bn_relu8(float* v, const float* sc, const float* sh) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = bf2f(f2bf(fmaxf(fmaf(v[k], sc[k], sh[k]), 0.f)));
-}
-
 // R = 1 (too few rows for bands, e.g. batch-1 serving): one output row per work item, 4 taps per output.
 __global__ __launch_bounds__(256) void upsample2_fwd_taps_kernel(const u16* __restrict__ x, int xpitch,
                                                                  u16* __restrict__ out, int opitch, UpGeom g, int lcg,
@@ -326,21 +290,21 @@ __global__ __launch_bounds__(256) void upsample2_fwd_taps_kernel(const u16* __re
       up_src(ux, g.win, g.rw, x0, x1, lx);
       const long base = (long)n * g.hin;
       float a[8], b[8], cc[8], d[8];
-      unpack8f(*(const uint4*)(x + ((base + y0) * g.win + x0) * xpitch + c), a);
-      unpack8f(*(const uint4*)(x + ((base + y0) * g.win + x1) * xpitch + c), b);
-      unpack8f(*(const uint4*)(x + ((base + y1) * g.win + x0) * xpitch + c), cc);
-      unpack8f(*(const uint4*)(x + ((base + y1) * g.win + x1) * xpitch + c), d);
+      unpack8(*(const uint4*)(x + ((base + y0) * g.win + x0) * xpitch + c), a);
+      unpack8(*(const uint4*)(x + ((base + y0) * g.win + x1) * xpitch + c), b);
+      unpack8(*(const uint4*)(x + ((base + y1) * g.win + x0) * xpitch + c), cc);
+      unpack8(*(const uint4*)(x + ((base + y1) * g.win + x1) * xpitch + c), d);
       if (coef) {
         float sc[8], sh[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { sc[k] = coef[2 * g.C + c + k]; sh[k] = coef[3 * g.C + c + k]; }
-        bn_relu8(a, sc, sh); bn_relu8(b, sc, sh); bn_relu8(cc, sc, sh); bn_relu8(d, sc, sh);
+        for (int k = 0; k < 8; ++k) { sc[k] = coef[bn_off(BN_SCALE, g.C) + c + k]; sh[k] = coef[bn_off(BN_SHIFT, g.C) + c + k]; }
+        bn_relu_bf_n(a, sc, sh); bn_relu_bf_n(b, sc, sh); bn_relu_bf_n(cc, sc, sh); bn_relu_bf_n(d, sc, sh);
       }
       const float hy = 1.f - ly, hx = 1.f - lx;
 #pragma unroll
       for (int k = 0; k < 8; ++k) o[k] = hy * (hx * a[k] + lx * b[k]) + ly * (hx * cc[k] + lx * d[k]);
     }
-    *(uint4*)(out + ((long)row * g.Wout + X) * opitch + c) = pack8f(o);
+    *(uint4*)(out + ((long)row * g.Wout + X) * opitch + c) = pack8(o);
   }
 }
 
@@ -352,13 +316,13 @@ __global__ __launch_bounds__(256) void upsample2_fwd_taps_kernel(const u16* __re
 RDP_DEV void up_hrow(const u16* __restrict__ x, long rowbase, int x0, int x1, int xpitch, int c, float hx,
                      float lx, const float* __restrict__ coef, int C, float* h) {
   float a[8], b[8];
-  unpack8f(*(const uint4*)(x + (rowbase + x0) * xpitch + c), a);
-  unpack8f(*(const uint4*)(x + (rowbase + x1) * xpitch + c), b);
+  unpack8(*(const uint4*)(x + (rowbase + x0) * xpitch + c), a);
+  unpack8(*(const uint4*)(x + (rowbase + x1) * xpitch + c), b);
   if (coef) {
     float sc[8], sh[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { sc[k] = coef[2 * C + c + k]; sh[k] = coef[3 * C + c + k]; }
-    bn_relu8(a, sc, sh); bn_relu8(b, sc, sh);
+    for (int k = 0; k < 8; ++k) { sc[k] = coef[bn_off(BN_SCALE, C) + c + k]; sh[k] = coef[bn_off(BN_SHIFT, C) + c + k]; }
+    bn_relu_bf_n(a, sc, sh); bn_relu_bf_n(b, sc, sh);
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k) h[k] = hx * a[k] + lx * b[k];
@@ -418,7 +382,7 @@ __global__ __launch_bounds__(256) void upsample2_fwd_kernel(const u16* __restric
 #pragma unroll
         for (int k = 0; k < 8; ++k) o[k] = hy * h0[k] + ly * h1[k];
       }
-      *(uint4*)(out + (((long)n * g.Hout + Y) * g.Wout + X) * opitch + c) = pack8f(o);
+      *(uint4*)(out + (((long)n * g.Hout + Y) * g.Wout + X) * opitch + c) = pack8(o);
     }
   }
 }
@@ -450,7 +414,7 @@ RDP_DEV void up_hsum(const u16* __restrict__ dout, long ro, const int* xo, const
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     float d[8];
-    unpack8f(v[b], d);
+    unpack8(v[b], d);
 #pragma unroll
     for (int k = 0; k < 8; ++k) h[k] = fmaf(wx[b], d[k], h[k]);
   }
@@ -466,16 +430,17 @@ __global__ __launch_bounds__(256) void upsample2_bwd_kernel(const u16* __restric
   const int CG = 1 << lcg;
   const int uh = 2 * g.hin, uw = 2 * g.win;
   const int c = (threadIdx.x & (CG - 1)) * 8;
+  // BNR: below = bn_ld8 / bn_acc_n (bn_dev.h), by hand (speed: profiles/pass_dev.md)
   float mean[8], inv[8], ss[8], hh[8], sg[8], sgx[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     sg[k] = 0.f;
     sgx[k] = 0.f;
     if (BNR) {
-      mean[k] = coef[c + k];
-      inv[k] = coef[g.C + c + k];
-      ss[k] = coef[2 * g.C + c + k];
-      hh[k] = coef[3 * g.C + c + k];
+      mean[k] = coef[bn_off(BN_MEAN, g.C) + c + k];
+      inv[k] = coef[bn_off(BN_INVSTD, g.C) + c + k];
+      ss[k] = coef[bn_off(BN_SCALE, g.C) + c + k];
+      hh[k] = coef[bn_off(BN_SHIFT, g.C) + c + k];
     }
   }
   const int nband = (g.hin + R - 1) / R;
@@ -524,12 +489,12 @@ __global__ __launch_bounds__(256) void upsample2_bwd_kernel(const u16* __restric
       }
       const int row = n * g.hin + i;
       const long p = (long)row * g.win + j;
-      const uint4 o = pack8f(acc);
+      const uint4 o = pack8(acc);
       *(uint4*)(dx + p * xpitch + c) = o;
       if (BNR) {
         float fg[8], fy[8];
-        unpack8f(o, fg);
-        unpack8f(*(const uint4*)(y + p * ypitch + c), fy);
+        unpack8(o, fg);
+        unpack8(*(const uint4*)(y + p * ypitch + c), fy);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const float gg = fmaf(fy[k], ss[k], hh[k]) > 0.f ? fg[k] : 0.f;
@@ -589,10 +554,10 @@ __global__ void upT_shuffle_kernel(const u16* __restrict__ yT, int ypitch, const
       const long src = ((long)n * g.h + (hy >> 1)) * g.w + (wx >> 1);
       const int j = ((hy & 1) * 2 + (wx & 1)) * g.C + c;
       float f[8];
-      unpack8f(*(const uint4*)(yT + src * ypitch + j), f);
+      unpack8(*(const uint4*)(yT + src * ypitch + j), f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) f[k] += bias[c + k];
-      v = pack8f(f);
+      v = pack8(f);
     }
     *(uint4*)(u + pix * upitch + c) = v;
   }
@@ -630,7 +595,7 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const u16* __restrict_
   if (r < RPB)
     for (long p = blockIdx.x * (long)RPB + r; p < M; p += (long)gridDim.x * RPB) {
       float f[8];
-      unpack8f(*(const uint4*)(x + p * pitch + g * 8), f);
+      unpack8(*(const uint4*)(x + p * pitch + g * 8), f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) acc[k] += f[k];
     }
@@ -700,10 +665,9 @@ int rdp_maxpool2_bwd(const void* dp, int dppitch, const void* x, int xpitch, con
                      dxpitch, N, H, W, C);
   return 0;
 }
-static bool pow2c(int C) { return C >= 8 && C <= 2048 && (C & (C - 1)) == 0; }
 int rdp_bn_relu_apply_pool(const void* y, int ypitch, void* a, int apitch, void* pool, int ppitch, const float* coef,
                            int N, int H, int W, int C, hipStream_t s) {
-  if (!pow2c(C) || ypitch % 8 || apitch % 8 || ppitch % 8) return -1;
+  if (!pow2_channels(C) || ypitch % 8 || apitch % 8 || ppitch % 8) return -1;
   const long rpb = 256 / (C / 8), nwin = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
   // <= 16384 blocks (64/CU): 256^2 x 64 at bs 64 239 -> 219 us, 128^2 x 128 121 -> 116 us vs a 4096 cap
   const int grid = (int)std::max<long>(1, std::min<long>((nwin + rpb - 1) / rpb, 16384));
@@ -714,7 +678,7 @@ int rdp_bn_relu_apply_pool(const void* y, int ypitch, void* a, int apitch, void*
 int rdp_maxpool2_bwd_bn_reduce(const void* dp, int dppitch, const void* x, int xpitch, const void* dskip, int dspitch,
                                void* dx, int dxpitch, const void* y, int ypitch, const float* coef, int N, int H, int W,
                                int C, float* partial, int max_blocks, hipStream_t s) {
-  if (!pow2c(C) || dppitch % 8 || xpitch % 8 || dspitch % 8 || dxpitch % 8 || ypitch % 8) return -1;
+  if (!pow2_channels(C) || dppitch % 8 || xpitch % 8 || dspitch % 8 || dxpitch % 8 || ypitch % 8) return -1;
   const long rpb = 256 / (C / 8), nwin = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
   // ~4 windows per thread row: enough bytes in flight, few partial rows for the finalize
   const int grid = (int)std::max<long>(1, std::min<long>((nwin + 4 * rpb - 1) / (4 * rpb), max_blocks));
@@ -731,7 +695,7 @@ static int ilog2(int v) {
 }
 int rdp_upsample2_fwd(const void* x, int xpitch, void* out, int opitch, int N, int hin, int win, int Hout, int Wout,
                       int oy, int ox, int C, const float* coef, hipStream_t s) {
-  if (!pow2c(C) || xpitch % 8 || opitch % 8) return -1;
+  if (!pow2_channels(C) || xpitch % 8 || opitch % 8) return -1;
   UpGeom g{N, hin, win, Hout, Wout, oy, ox, C, ac_scale(hin, 2 * hin), ac_scale(win, 2 * win)};
   const int lcg = ilog2(C / 8), nchunk = (int)(((long)Wout * (C / 8) + 255) / 256);
   // band height 8 (128^2 -> 256^2 x 64, bs 64: 196 us with 4 taps per output -> 132 us; 16 rows 139 us),
@@ -751,7 +715,7 @@ int rdp_upsample2_fwd(const void* x, int xpitch, void* out, int opitch, int N, i
 int rdp_upsample2_bwd(const void* dout, int dpitch, void* dx, int xpitch, int N, int hin, int win, int Hout, int Wout,
                       int oy, int ox, int C, const void* y, int ypitch, const float* coef, float* partial,
                       int max_blocks, hipStream_t s) {
-  if (!pow2c(C) || dpitch % 8 || xpitch % 8 || (y && ypitch % 8)) return -1;
+  if (!pow2_channels(C) || dpitch % 8 || xpitch % 8 || (y && ypitch % 8)) return -1;
   UpGeom g{N, hin, win, Hout, Wout, oy, ox, C, ac_scale(hin, 2 * hin), ac_scale(win, 2 * win)};
   const int lcg = ilog2(C / 8), nchunk = (int)(((long)win * (C / 8) + 255) / 256);
   // band height 4 (256^2 -> 128^2 x 64 + BN reduce, bs 64: 198 us unbanded -> 165 us; 2 rows 171, 8 rows
