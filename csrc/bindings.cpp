@@ -500,124 +500,214 @@ float* ws_ptr(const c10::optional<torch::Tensor>& ws, int K) {
   return ws->data_ptr<float>();
 }
 
-// The plan of a dense conv of this shape, as a dict (kernel: the RdpConvKernel value, -1 = unsupported)
+// The plan of a dense conv of this shape, as a dict (kernel: the RdpConvKernel value, -1 = unsupported). chunks: the
+// image slices conv_fwd / conv_dgrad run a batch past the 2 GiB reach as; the plan is then that of one slice, and
+// the fused forms (bn, bnin) exist only at chunks == 1 (bn is not offered, bnin is unsupported)
 py::dict conv_plan(int N, int H, int W, int C1, int C2, int Cout, int taps, int packed, int kernel, bool stats,
-                   bool eval, int split, long ws_elems, bool pool, bool up, bool bn, bool wfrag) {
+                   bool eval, int split, long ws_elems, bool pool, bool up, bool bn, bool wfrag, bool bnin) {
+  const int Cy1 = split > 0 ? split : Cout;
+  const int nc = chunk_images((long)H * W * std::max({C1, C2, Cy1, Cout - Cy1}) * 2, N);
+  const int chunks = N > 0 ? (N + nc - 1) / nc : 1;
   RdpConvQuery q;
-  q.N = N; q.H = H; q.W = W; q.C1 = C1; q.C2 = C2; q.Cout = Cout; q.taps = taps; q.packed = packed; q.kernel = kernel;
-  q.stats = stats; q.eval = eval; q.split = split; q.ws_elems = ws_elems; q.pool = pool; q.up = up; q.bn = bn;
-  q.wfrag = wfrag;
+  q.N = std::min(N, nc); q.H = H; q.W = W; q.C1 = C1; q.C2 = C2; q.Cout = Cout; q.taps = taps; q.packed = packed;
+  q.kernel = bnin && chunks > 1 ? RDP_CONV_UNSUPPORTED : kernel;
+  q.stats = stats; q.eval = eval; q.split = split; q.ws_elems = ws_elems; q.pool = pool; q.up = up;
+  q.bn = bn && chunks == 1; q.bnin = bnin; q.wfrag = wfrag;
   const RdpConvPlan p = rdp_conv_plan_dense(q);
   py::dict d;
-  d["kernel"] = p.kernel; d["name"] = rdp_conv_kernel_name(p.kernel);
+  d["kernel"] = p.kernel; d["name"] = rdp_conv_kernel_name(p.kernel); d["chunks"] = chunks;
+  d["ring_form"] = p.kernel == RDP_CONV_RING ? p.ring_form : -1;
   d["bm"] = p.BM; d["bn"] = p.BN; d["waves"] = p.waves; d["ksplit"] = p.ksplit; d["rowband_mode"] = p.rowband_mode;
   d["launches"] = p.launches; d["grid"] = p.grid; d["reduce_grid"] = p.rgrid; d["stats_rows"] = p.stats_rows;
   d["ws_elems"] = p.ws_elems; d["pool_fused"] = p.pool_fused; d["up_fused"] = p.up_fused; d["bn_rows"] = p.bn_rows;
   return d;
 }
 
-// y = conv(cat(x1, x2), w); returns #M-tiles (stats rows)
+// What conv_fwd and conv_dgrad have validated, for conv_run. The tensors are views (an undefined Act: not given) that
+// conv_run binds slice by slice; the blocks carry everything else a launch takes: c the weights, the stats slab and
+// the eval epilogue, fuse the upsample's placement, bn the owner layer's coefficients and row slab (dgrad), in the
+// producer's BN + ReLU (forward: x1 is its pre-BN output, a_out also receives the activation).
+struct ConvCall {
+  const char* what = "conv";
+  Act x1, x2, y1, y2, pool, up, bn_y, a_out;
+  RdpConv c;
+  RdpConvFuse fuse;
+  RdpConvBnBwd bn;
+  RdpConvBnIn in;
+  int taps = 9, packed = 0, kernel = RDP_CONV_AUTO;
+  long stats_rows = 0, bn_rows = 0;  // what the stats slab / bn.bnpart hold
+  float* ws = nullptr;
+  long ws_elems = 0;
+  const void* wfrag = nullptr;  // (eval) the fragment-major copy of the weights, for the row-band kernel
+  long wfrag_bytes = 0;
+};
+struct ConvRows {
+  int stats = 0, bn = 0;  // what the launches reported (the stats-slab rows) / rows written to bn.bnpart
+};
+
+// The one bind / chunk / launch body. Batch chunks: the conv kernels address each tensor through ONE buffer
+// descriptor with 32-bit offsets (< 2 GiB), so a batch whose largest tensor passes that (256^2 x 64 ch bf16 at
+// N >= 256) runs as consecutive launches over image slices (convs never cross images); BN partial rows of the
+// slices are appended, fused pool / upsample outputs sliced alike. A chunked batch is offered no BN-backward
+// operand (0 rows: the caller's separate pass) and cannot apply a BN to its input.
+ConvRows conv_run(const ConvCall& k) {
+  const Act &a1 = k.x1, &o1 = k.y1;
+  const int Cout = o1.C + k.y2.C, taps = k.taps, packed = k.packed, kernel = k.kernel;
+  const int nc = chunk_images({a1, k.x2, o1, k.y2, k.bn_y, k.a_out}, a1.N);
+  TORCH_CHECK(!k.in.iscale || nc >= a1.N, k.what, ": in_coef needs a batch that runs as one launch (tensors < 2 GiB)");
+  float* const wsp = k.ws;
+  const long wsn = k.ws_elems, wfn = k.wfrag_bytes;
+  const void* const wfp = k.wfrag;
+  const bool want_fused = k.pool.ptr || k.up.ptr;
+  ConvRows rows;
+  for (int n0 = 0; n0 < a1.N; n0 += nc) {
+    const int nn = std::min(nc, a1.N - n0);
+    if (k.c.stats)
+      TORCH_CHECK(rows.stats + rdp_conv_stats_rows((long)nn * a1.H * a1.W, Cout, kernel) <= k.stats_rows,
+                  "stats slab too small");
+    // every launch argument is a value here (the blocks are captured by copy): RDP_PLAN may keep the launch for
+    // replay (plan mode)
+    RdpConv c = k.c;
+    conv_bind(c, kX1, a1, n0, nn);
+    conv_bind(c, kX2, k.x2, n0, nn);
+    conv_bind(c, kY1, o1, n0, nn);
+    conv_bind(c, kY2, k.y2, n0, nn);
+    if (c.stats) c.stats += (long)rows.stats * 2 * Cout;
+    c.Cout = Cout;
+    RdpConvFuse fuse = k.fuse;
+    if (k.pool.ptr) { fuse.pool = k.pool.image(n0); fuse.ppitch = k.pool.pitch; }
+    if (k.up.ptr) { fuse.up = k.up.image(n0); fuse.upitch = k.up.pitch; fuse.uH = k.up.H; fuse.uW = k.up.W; }
+    RdpConvBnBwd bn;
+    if (k.bn_y.ptr && nc >= a1.N) { bn = k.bn; bn.bny = k.bn_y.ptr; bn.bnypitch = k.bn_y.pitch; }
+    RdpConvBnIn in = k.in;
+    if (k.a_out.ptr) { in.aout = k.a_out.ptr; in.abytes = k.a_out.bytes; in.apitch = k.a_out.pitch; }
+    if (bn.bny)  // the rows the launch below will write
+      TORCH_CHECK(rdp_conv_plan(c, taps, packed, kernel, wsp && wsn > 0, wsn, fuse, want_fused, bn, in, wfp ? wfn : 0)
+                      .bn_rows <= k.bn_rows, k.what, ": partial too small");
+    // the fused pool / upsample flag and the BN-backward row count: heap cells owned by the launch. They are named
+    // inside the closure so that a recorded launch owns the cells it writes on every replay
+    auto pooled = std::make_shared<int>(0);
+    auto bnrows = std::make_shared<int>(0);
+    const int r = RDP_PLAN(rdp_conv_igemm(c, taps, packed, kernel, wsp, wsn, wfp, wfn, fuse,
+                                          want_fused ? pooled.get() : nullptr, bn, bnrows.get(), in, st));
+    TORCH_CHECK(r >= 0, k.what, ": no kernel for this conv (C1=", a1.C, ", C2=", c.C2, ", Cout=", Cout, ", kernel=",
+                rdp_conv_kernel_name(kernel), " (", kernel, ")", in.iscale ? ", BN on the input" : "", ")");
+    void* const py1 = c.y1;
+    const int oH = o1.H, oW = o1.W, oC = o1.C, op1 = o1.pitch;
+    if (k.pool.ptr && !*pooled)
+      TORCH_CHECK(RDP_PLAN(rdp_maxpool2_fwd(py1, op1, fuse.pool, fuse.ppitch, nn, oH, oW, oC, st)) == 0,
+                  "conv_fwd: maxpool");
+    if (k.up.ptr && !*pooled)
+      TORCH_CHECK(RDP_PLAN(rdp_upsample2_fwd(py1, op1, fuse.up, fuse.upitch, nn, oH, oW, fuse.uH, fuse.uW, fuse.uoy,
+                                             fuse.uox, oC, nullptr, st)) == 0,
+                  "conv_fwd: upsample");
+    rows.stats += r;
+    rows.bn += *bnrows;
+  }
+  return rows;
+}
+
+// the sources, destinations, weights and split-K workspace both conv bindings take
+void conv_operands(ConvCall& k, const torch::Tensor& x1, const torch::Tensor& w, const torch::Tensor& y1,
+                   const c10::optional<torch::Tensor>& y2, const c10::optional<torch::Tensor>& ws) {
+  k.x1 = act(x1, "x1");
+  k.y1 = act(y1, "y1");
+  if (y2) k.y2 = act(*y2, "y2");
+  TORCH_CHECK(k.y1.N == k.x1.N && k.y1.H == k.x1.H && k.y1.W == k.x1.W, k.what, ": y spatial mismatch");
+  conv_weights(k.c, w);
+  TORCH_CHECK(w.size(0) == k.y1.C + k.y2.C, k.what, ": w rows != Cout");
+  if (ws) { check_f32(*ws, "ws"); k.ws = ws->data_ptr<float>(); k.ws_elems = ws->numel(); }
+}
+
+// y = conv(cat(x1, x2), w); returns #M-tiles (stats rows). in_coef (training, the row ring's 64 -> 64 form only:
+// anything else is an error): x1 is the producer layer's PRE-BN output and the conv applies that layer's BN + ReLU
+// (in_coef: its [mean|invstd|scale|shift]) to the rows it stages, so the activation need not exist; a_out: it is
+// also written there, bitwise what bn_relu_apply writes, for a plain weight-gradient pass.
 int conv_fwd(torch::Tensor x1, c10::optional<torch::Tensor> x2, torch::Tensor w, int taps, int packed,
              torch::Tensor y1, c10::optional<torch::Tensor> y2, c10::optional<torch::Tensor> stats, int bm_pref,
              c10::optional<torch::Tensor> affine, int relu, c10::optional<torch::Tensor> ws,
              c10::optional<torch::Tensor> pool, c10::optional<torch::Tensor> up, int up_oy, int up_ox,
-             c10::optional<torch::Tensor> wfrag) {
-  Act a1 = act(x1, "x1"), a2;
+             c10::optional<torch::Tensor> wfrag, c10::optional<torch::Tensor> in_coef,
+             c10::optional<torch::Tensor> a_out) {
+  ConvCall k;
+  k.what = "conv_fwd";
+  conv_operands(k, x1, w, y1, y2, ws);
+  const Act &a1 = k.x1, &o1 = k.y1;
   if (x2) {
-    a2 = act(*x2, "x2");
-    TORCH_CHECK(a2.N == a1.N && a2.H == a1.H && a2.W == a1.W, "x2 spatial mismatch");
+    k.x2 = act(*x2, "x2");
+    TORCH_CHECK(k.x2.N == a1.N && k.x2.H == a1.H && k.x2.W == a1.W, "x2 spatial mismatch");
   }
-  check_w(w);
-  Act o1 = act(y1, "y1"), o2;
-  int Cout = o1.C;
-  if (y2) { o2 = act(*y2, "y2"); Cout += o2.C; }
-  TORCH_CHECK(o1.N == a1.N && o1.H == a1.H && o1.W == a1.W, "y spatial mismatch");
-  TORCH_CHECK(w.size(0) == Cout, "w rows != Cout");
-  float* sp = nullptr;
+  k.taps = taps; k.packed = packed; k.kernel = bm_pref; k.c.erelu = relu;
+  const int Cout = o1.C + k.y2.C;
   if (stats) {
     check_f32(*stats, "stats");
-    const long M = (long)a1.N * a1.H * a1.W;
-    const long rows = rdp_conv_stats_rows(M, Cout, bm_pref);
+    const long rows = rdp_conv_stats_rows((long)a1.N * a1.H * a1.W, Cout, bm_pref);
     TORCH_CHECK(stats->numel() >= rows * 2 * Cout, "stats slab too small");
-    sp = stats->data_ptr<float>();
+    k.c.stats = stats->data_ptr<float>();
+    k.stats_rows = stats->numel() / (2l * Cout);
   }
-  const float* esc = nullptr;
-  const float* esh = nullptr;
   if (affine) {  // BN coefficient block (bn_dev.h layout, BN_ROWS * Cout floats)
     check_f32(*affine, "affine");
     TORCH_CHECK(affine->numel() >= (long)BN_ROWS * Cout, "affine must hold 4*Cout floats");
-    esc = affine->data_ptr<float>() + bn_off(BN_SCALE, Cout);
-    esh = affine->data_ptr<float>() + bn_off(BN_SHIFT, Cout);
+    k.c.escale = affine->data_ptr<float>() + bn_off(BN_SCALE, Cout);
+    k.c.eshift = affine->data_ptr<float>() + bn_off(BN_SHIFT, Cout);
   }
-  if (ws) check_f32(*ws, "ws");
   // pool (eval): MaxPool2d(2) of y1 -> pool [N][H/2][W/2][Cout]; fused into the split-K reduce when
   // that path runs, else a maxpool2_fwd launch after the conv
-  Act po;
   if (pool) {
-    po = act(*pool, "pool");
+    const Act& po = k.pool = act(*pool, "pool");
     TORCH_CHECK(!y2 && !stats && po.N == o1.N && po.H == o1.H / 2 && po.W == o1.W / 2 && po.C == o1.C,
                 "pool: eval conv with one destination, [N][H/2][W/2][Cout]");
   }
   // up (eval): bilinear x2 upsample of y1 into up at (up_oy, up_ox); fused into the split-K reduce
   // when that path runs, else an upsample2_fwd launch after the conv
-  Act uo;
   if (up) {
-    uo = act(*up, "up");
+    const Act& uo = k.up = act(*up, "up");
     TORCH_CHECK(!pool && !y2 && !stats && uo.N == o1.N && uo.C == o1.C && up_oy >= 0 && up_ox >= 0 &&
                 2 * o1.H + up_oy <= uo.H && 2 * o1.W + up_ox <= uo.W, "up: eval conv, [N][>=2H][>=2W][Cout]");
+    k.fuse.uoy = up_oy; k.fuse.uox = up_ox;
   }
-  // Batch chunks: the conv kernels address each tensor through ONE buffer descriptor with 32-bit
-  // offsets (< 2 GiB), so a batch whose largest tensor passes that (256^2 x 64 ch bf16 at N >= 256)
-  // runs as consecutive launches over image slices (convs never cross images); BN partial rows of
-  // the slices are appended, fused pool / upsample outputs sliced alike.
-  const int nc = chunk_images({a1, a2, o1, o2}, a1.N);
-  const long avail_rows = stats ? stats->numel() / (2l * Cout) : 0;
-  int rows = 0;
-  for (int n0 = 0; n0 < a1.N; n0 += nc) {
-    const int nn = std::min(nc, a1.N - n0);
-    if (sp) TORCH_CHECK(rows + rdp_conv_stats_rows((long)nn * a1.H * a1.W, Cout, bm_pref) <= avail_rows, "stats slab too small");
-    // every launch argument is a value here (the blocks are captured by copy): RDP_PLAN may keep the launch for
-    // replay (plan mode)
-    RdpConv c;
-    conv_bind(c, kX1, a1, n0, nn);
-    conv_bind(c, kX2, a2, n0, nn);
-    conv_bind(c, kY1, o1, n0, nn);
-    conv_bind(c, kY2, o2, n0, nn);
-    conv_weights(c, w);
-    c.stats = sp ? sp + (long)rows * 2 * Cout : nullptr;
-    c.Cout = Cout;
-    c.escale = esc; c.eshift = esh; c.erelu = relu;
-    RdpConvFuse fuse;
-    if (pool) { fuse.pool = po.image(n0); fuse.ppitch = po.pitch; }
-    if (up) {
-      fuse.up = uo.image(n0); fuse.upitch = uo.pitch; fuse.uH = uo.H; fuse.uW = uo.W;
-      fuse.uoy = up_oy; fuse.uox = up_ox;
-    }
-    float* const wsp = ws ? ws->data_ptr<float>() : nullptr;
-    const long wsn = ws ? (long)ws->numel() : 0L;
-    const bool want_fused = pool || up;
-    // the fused pool / upsample result flag: a heap cell owned by the launch (kept alive in a plan)
-    auto pooled = std::make_shared<int>(0);
-    // wfrag (eval): the fragment-major copy of w, for the row-band kernel where the dispatcher picks it
-    const void* const wfp = wfrag ? wfrag->data_ptr() : nullptr;
-    const long wfn = wfrag ? (long)wfrag->numel() * 2 : 0L;
-    // `pooled` is named inside the closure so that a recorded launch owns the cell it writes on every replay
-    const int r = RDP_PLAN(rdp_conv_igemm(c, taps, packed, bm_pref, wsp, wsn, wfp, wfn, fuse,
-                                          want_fused ? pooled.get() : nullptr, RdpConvBnBwd{}, nullptr, st));
-    TORCH_CHECK(r >= 0, "conv_fwd: no kernel for this conv (C1=", a1.C, ", C2=", c.C2, ", Cout=", Cout, ", kernel=",
-                rdp_conv_kernel_name(bm_pref), " (", bm_pref, "))");
-    void* const py1 = c.y1;
-    const int oH = o1.H, oW = o1.W, oC = o1.C, op1 = o1.pitch;
-    if (pool && !*pooled)
-      TORCH_CHECK(RDP_PLAN(rdp_maxpool2_fwd(py1, op1, fuse.pool, fuse.ppitch, nn, oH, oW, oC, st)) == 0,
-                  "conv_fwd: maxpool");
-    if (up && !*pooled)
-      TORCH_CHECK(RDP_PLAN(rdp_upsample2_fwd(py1, op1, fuse.up, fuse.upitch, nn, oH, oW, fuse.uH, fuse.uW, fuse.uoy,
-                                             fuse.uox, oC, nullptr, st)) == 0,
-                  "conv_fwd: upsample");
-    rows += r;
+  if (wfrag) { k.wfrag = wfrag->data_ptr(); k.wfrag_bytes = (long)wfrag->numel() * 2; }
+  if (in_coef) {
+    check_f32(*in_coef, "in_coef");
+    TORCH_CHECK(in_coef->numel() >= (long)BN_ROWS * a1.C, "in_coef: [4 C] f32");
+    k.in.iscale = in_coef->data_ptr<float>() + bn_off(BN_SCALE, a1.C);
+    k.in.ishift = in_coef->data_ptr<float>() + bn_off(BN_SHIFT, a1.C);
   }
-  return rows;
+  if (a_out && a_out->defined()) {
+    const Act& q = k.a_out = act(*a_out, "a_out");
+    TORCH_CHECK(in_coef && q.N == a1.N && q.H == a1.H && q.W == a1.W && q.C == a1.C, "a_out: with in_coef, x1's shape");
+  }
+  return conv_run(k).stats;
+}
+
+// The input gradient dx1 | dx2 = conv(dy, w), w the dgrad weights [Cin][taps * Cout], split over the concat's two
+// sources. bn_y / bn_coef / bn_partial (together, one destination): dx1 is the activation gradient of one BN + ReLU
+// layer (bn_y: its pre-BN output, bn_coef: its [mean|invstd|scale|shift]), and where the kernel that runs can --
+// the row ring's epilogue, the split-K reduce -- it also writes that layer's BN-backward partial rows to
+// bn_partial. Returns their count for bn_bwd_finalize; 0: none written, the caller runs bn_relu_bwd_reduce. The
+// dgrad always runs.
+int conv_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx1, c10::optional<torch::Tensor> dx2,
+               c10::optional<torch::Tensor> ws, c10::optional<torch::Tensor> bn_y, c10::optional<torch::Tensor> bn_coef,
+               c10::optional<torch::Tensor> bn_partial, int kernel) {
+  ConvCall k;
+  k.what = "conv_dgrad";
+  conv_operands(k, dy, w, dx1, dx2, ws);
+  const Act &a = k.x1, &o = k.y1;
+  TORCH_CHECK(w.size(1) % a.C == 0, "conv_dgrad: w must be [Cin][taps * Cout]");
+  k.taps = (int)(w.size(1) / a.C); k.kernel = kernel;
+  if (bn_y || bn_coef || bn_partial) {
+    TORCH_CHECK(bn_y && bn_coef && bn_partial && !dx2, "conv_dgrad: bn_y, bn_coef, bn_partial go together, with one dx");
+    const Act& b = k.bn_y = act(*bn_y, "bn_y");
+    TORCH_CHECK(b.N == a.N && b.H == a.H && b.W == a.W && b.C == o.C, "conv_dgrad: bn_y shape mismatch");
+    check_f32(*bn_coef, "bn_coef");
+    check_f32(*bn_partial, "bn_partial");
+    TORCH_CHECK(bn_coef->numel() >= (long)BN_ROWS * o.C, "bn_coef must hold 4*C floats");
+    k.bn.bncoef = bn_coef->data_ptr<float>();
+    k.bn.bnpart = bn_partial->data_ptr<float>();
+    k.bn_rows = bn_partial->numel() / (2l * o.C);
+  }
+  return conv_run(k).bn;
 }
 
 
@@ -739,105 +829,6 @@ void bn_relu_apply(torch::Tensor y, torch::Tensor out, torch::Tensor coef, int r
   TORCH_CHECK(coef.numel() >= (long)BN_ROWS * a.C, "coef");
   TORCH_CHECK(RDP_PLAN(rdp_bn_relu_apply(a.ptr, a.pitch, o.ptr, o.pitch, coef.data_ptr<float>(), a.N * a.H * a.W, a.C, relu,
                                 st)) == 0, "bn_relu_apply");
-}
-
-// 3x3 dgrad (row-ring kernel) whose epilogue also writes the BN-backward partial rows of the layer that
-// owns dx (y_bn: its pre-BN output, coef: its [mean|invstd|scale|shift]; ReLU). Returns the partial
-// rows for bn_bwd_finalize, or -1 if the ring kernel does not apply (caller falls back to
-// conv_fwd + bn_relu_bwd_reduce; nothing was launched).
-int conv_dgrad_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, torch::Tensor y_bn, torch::Tensor coef,
-                     torch::Tensor partial) {
-  Act a = act(dy, "dy"), o = act(dx, "dx"), b = act(y_bn, "y_bn");
-  check_w(w);
-  TORCH_CHECK(o.N == a.N && o.H == a.H && o.W == a.W && b.N == a.N && b.H == a.H && b.W == a.W && b.C == o.C,
-              "conv_dgrad_bnred: shape mismatch");
-  TORCH_CHECK(w.size(0) == o.C, "w rows != Cout");
-  check_f32(coef, "coef");
-  check_f32(partial, "partial");
-  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * o.C, "coef must hold 4*C floats");
-  // ring grid <= 256 blocks x 4 pixel groups (64 couts) or 2 (128): <= 1024 rows of 2*C
-  TORCH_CHECK(partial.numel() >= 1024l * 2 * o.C, "partial too small");
-  // batches past the 2 GiB buffer-offset reach: the caller's chunked conv_fwd + bn_relu_bwd_reduce
-  if (chunk_images({a, o, b}, a.N) < a.N) return -1;
-  RdpConv c;
-  conv_bind(c, kX1, a, 0, a.N);
-  conv_bind(c, kY1, o, 0, a.N);
-  conv_weights(c, w);
-  c.Cout = o.C;
-  c.stats = partial.data_ptr<float>();
-  RdpRingFuse f;
-  f.bn_y = b.ptr; f.bn_ypitch = b.pitch; f.bn_coef = coef.data_ptr<float>();
-  return RDP_PLAN(rdp_conv_ring_ex(c, 256, f, st));
-}
-
-// 3x3 dgrad into one BN + ReLU layer's activation gradient (dx, one destination) through the implicit-GEMM
-// dispatch: where it runs split-K (small M x long K: the reference batch's deep layers), the split-K
-// reduce also writes that layer's BN-backward partial rows (y_bn: its pre-BN output, coef: its
-// [mean|invstd|scale|shift]) and this returns their count; 0 when the conv ran on another path (the
-// caller runs bn_relu_bwd_reduce); -1 when nothing was launched (batches past the 2 GiB reach: the
-// caller's chunked conv_fwd).
-int conv_dgrad_splitk_bnred(torch::Tensor dy, torch::Tensor w, torch::Tensor dx, torch::Tensor y_bn,
-                            torch::Tensor coef, torch::Tensor partial, c10::optional<torch::Tensor> ws) {
-  Act a = act(dy, "dy"), o = act(dx, "dx"), b = act(y_bn, "y_bn");
-  check_w(w);
-  TORCH_CHECK(o.N == a.N && o.H == a.H && o.W == a.W && b.N == a.N && b.H == a.H && b.W == a.W && b.C == o.C,
-              "conv_dgrad_splitk_bnred: shape mismatch");
-  TORCH_CHECK(w.size(0) == o.C && w.size(1) >= 9l * a.C, "conv_dgrad_splitk_bnred: w must be [Cout][9 * Cin]");
-  check_f32(coef, "coef");
-  check_f32(partial, "partial");
-  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * o.C, "coef must hold 4*C floats");
-  TORCH_CHECK(partial.numel() >= 512l * 2 * o.C, "partial too small");  // the split-K reduce: <= 512 rows
-  if (ws) check_f32(*ws, "ws");
-  if (chunk_images({a, o, b}, a.N) < a.N) return -1;
-  RdpConv c;
-  conv_bind(c, kX1, a, 0, a.N);
-  conv_bind(c, kY1, o, 0, a.N);
-  conv_weights(c, w);
-  c.Cout = o.C;
-  RdpConvBnBwd bn;
-  bn.bny = b.ptr; bn.bnypitch = b.pitch; bn.bncoef = coef.data_ptr<float>(); bn.bnpart = partial.data_ptr<float>();
-  float* const wsp = ws ? ws->data_ptr<float>() : nullptr;
-  const long wsn = ws ? (long)ws->numel() : 0L;
-  // the row-count cell: owned by the launch; `rows` is named inside the closure so that a recorded launch keeps
-  // the cell it writes on every replay alive
-  auto rows = std::make_shared<int>(0);
-  const int r = RDP_PLAN(rdp_conv_igemm(c, 9, 0, RDP_CONV_AUTO, wsp, wsn, nullptr, 0, RdpConvFuse{}, nullptr, bn, rows.get(), st));
-  TORCH_CHECK(r >= 0, "conv_dgrad_splitk_bnred: unsupported shape (Cin=", a.C, ", Cout=", o.C, ")");
-  return *rows;
-}
-
-// Training forward of a 3x3 64 -> 64 conv whose input is the producer layer's PRE-BN output x_pre: the
-// row-ring kernel applies the producer's BN + ReLU (in_coef: its [mean|invstd|scale|shift]) to the
-// staged rows itself, so the activation is never written (conv_ring.hip BNIN). Writes y and this
-// conv's BN statistic rows; returns the rows, or -1 when the ring kernel does not apply (nothing
-// launched: the caller runs bn_relu_apply + conv_fwd). a_out (optional): the activation is also
-// written there (bitwise what bn_relu_apply writes), for a plain weight-gradient pass.
-int conv_fwd_bnin(torch::Tensor x_pre, torch::Tensor w, torch::Tensor y, torch::Tensor stats, torch::Tensor in_coef,
-                  c10::optional<torch::Tensor> a_out) {
-  Act a = act(x_pre, "x_pre"), o = act(y, "y");
-  RdpRingFuse f;
-  if (a_out && a_out->defined()) {
-    Act q = act(*a_out, "a_out");
-    TORCH_CHECK(q.N == a.N && q.H == a.H && q.W == a.W && q.C == a.C, "conv_fwd_bnin: a_out shape");
-    f.aout = q.ptr; f.abytes = q.bytes; f.apitch = q.pitch;
-  }
-  check_w(w);
-  TORCH_CHECK(o.N == a.N && o.H == a.H && o.W == a.W && w.size(0) == o.C, "conv_fwd_bnin: shape mismatch");
-  check_f32(stats, "stats");
-  check_f32(in_coef, "in_coef");
-  TORCH_CHECK(in_coef.numel() >= (long)BN_ROWS * a.C, "in_coef: [4 C] f32");
-  // (the ring grid writes <= 256 blocks x 4 pixel-group rows of 2 * C)
-  if (a.C != 64 || o.C != 64 || a.W % 64 || a.H % 2 || stats.numel() < 1024l * 2 * o.C) return -1;
-  if (chunk_images({a, o}, a.N) < a.N) return -1;
-  RdpConv c;
-  conv_bind(c, kX1, a, 0, a.N);
-  conv_bind(c, kY1, o, 0, a.N);
-  conv_weights(c, w);
-  c.Cout = o.C;
-  c.stats = stats.data_ptr<float>();
-  f.iscale = in_coef.data_ptr<float>() + bn_off(BN_SCALE, a.C);
-  f.ishift = in_coef.data_ptr<float>() + bn_off(BN_SHIFT, a.C);
-  return RDP_PLAN(rdp_conv_ring_ex(c, 256, f, st));
 }
 
 int bn_relu_bwd_reduce(torch::Tensor da, torch::Tensor y, torch::Tensor coef, int relu, torch::Tensor partial) {
@@ -1146,24 +1137,38 @@ void head_bn_bwd_apply(torch::Tensor y, torch::Tensor w, torch::Tensor logits, t
               "head_bn_bwd_apply: pitches must be multiples of 8");
 }
 
+// The body of conv_head_mask / conv_headk_mask: the eval conv (64 -> 64, BN fold + ReLU) whose output only the fused
+// serving head h reads, on the row ring; false (nothing launched) where that kernel does not apply
+bool conv_ring_head(const Act& a, const torch::Tensor& w, const torch::Tensor& coef, RdpRingHead h,
+                    const torch::Tensor& mask) {
+  check_w(w);
+  check_f32(coef, "coef");
+  const int Co = (int)w.size(0);
+  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * Co, "coef size");
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kUInt8 && mask.is_contiguous() &&
+              mask.numel() >= (long)a.N * a.H * a.W, "mask: u8 [N*H*W]");
+  RdpConv c;
+  conv_bind(c, kX1, a, 0, a.N);
+  conv_weights(c, w);
+  c.Cy1 = 64; c.ypitch1 = 64; c.Cout = Co;
+  c.escale = coef.data_ptr<float>() + bn_off(BN_SCALE, Co); c.eshift = coef.data_ptr<float>() + bn_off(BN_SHIFT, Co);
+  c.erelu = 1;
+  h.mask = mask.data_ptr();
+  return RDP_PLAN(rdp_conv_ring_head(c, h, st)) == 0;
+}
+
 // eval conv (64 -> 64, BN fold + ReLU) + serving 1x1 head + (logit > thr) in one kernel (row ring);
 // returns false (nothing launched) where that kernel does not apply
 bool conv_head_mask(torch::Tensor x, torch::Tensor w, torch::Tensor coef, torch::Tensor hw, torch::Tensor hb,
                     double thr, torch::Tensor mask) {
   Act a = act(x, "x");
   check_w(w);
-  check_f32(coef, "coef");
   check_f32(hw, "head_w");
   check_f32(hb, "head_b");
-  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * w.size(0) && hw.numel() == w.size(0) && hb.numel() >= 1, "coef / head sizes");
-  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kUInt8 && mask.is_contiguous() &&
-              mask.numel() >= (long)a.N * a.H * a.W, "mask: u8 [N*H*W]");
-  const int Co = (int)w.size(0);
-  const int r = RDP_PLAN(rdp_conv_ring_head(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, w.size(1), Co, a.N, a.H,
-                                   a.W, coef.data_ptr<float>() + bn_off(BN_SCALE, Co), coef.data_ptr<float>() + bn_off(BN_SHIFT, Co),
-                                   hw.data_ptr<float>(), hb.data_ptr<float>(), (float)thr, mask.data_ptr(),
-                                   st));
-  return r == 0;
+  TORCH_CHECK(hw.numel() == w.size(0) && hb.numel() >= 1, "coef / head sizes");
+  RdpRingHead h;
+  h.hw = hw.data_ptr<float>(); h.hb = hb.data_ptr<float>(); h.thr = (float)thr;
+  return conv_ring_head(a, w, coef, h, mask);
 }
 
 // Row-band eval conv called directly (csrc/conv_rowband.hip), with OHWI weights (wfrag = 0) or their
@@ -1343,20 +1348,13 @@ void headk_mask(torch::Tensor a, torch::Tensor w, torch::Tensor b, int cls, torc
 bool conv_headk_mask(torch::Tensor x, torch::Tensor w, torch::Tensor coef, torch::Tensor hw, torch::Tensor hb, int cls,
                      torch::Tensor mask) {
   Act a = act(x, "x");
-  check_w(w);
-  check_f32(coef, "coef");
-  const int K = headk_classes(hw, hb, "conv_headk_mask");
-  TORCH_CHECK(coef.numel() >= (long)BN_ROWS * w.size(0), "coef size");
-  TORCH_CHECK(cls >= 0 && cls < K, "conv_headk_mask: class ", cls, " outside 0..", K - 1);
+  RdpRingHead h;
+  h.K = headk_classes(hw, hb, "conv_headk_mask");
+  TORCH_CHECK(cls >= 0 && cls < h.K, "conv_headk_mask: class ", cls, " outside 0..", h.K - 1);
   const long M = (long)a.N * a.H * a.W;
   TORCH_CHECK(M > 0 && M < (1L << 31), "conv_headk_mask: pixel count");
-  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kUInt8 && mask.is_contiguous() && mask.numel() >= M,
-              "mask: u8 [N*H*W]");
-  const int Co = (int)w.size(0);
-  const int r = RDP_PLAN(rdp_conv_ring_headk(a.ptr, a.bytes, a.C, a.pitch, w.data_ptr(), w.numel() * 2, w.size(1), Co, a.N,
-                                             a.H, a.W, coef.data_ptr<float>() + bn_off(BN_SCALE, Co), coef.data_ptr<float>() + bn_off(BN_SHIFT, Co),
-                                             hw.data_ptr<float>(), hb.data_ptr<float>(), K, cls, mask.data_ptr(), st));
-  return r == 0;
+  h.hw = hw.data_ptr<float>(); h.hb = hb.data_ptr<float>(); h.cls = cls;
+  return conv_ring_head(a, w, coef, h, mask);
 }
 
 // ---- validation metrics (csrc/seg_metrics.hip) ----
@@ -2111,7 +2109,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_fwd", on_device(&conv_fwd), py::arg("x1"), py::arg("x2"), py::arg("w"), py::arg("taps"), py::arg("packed"),
         py::arg("y1"), py::arg("y2"), py::arg("stats"), py::arg("bm_pref"), py::arg("affine"), py::arg("relu"),
         py::arg("ws") = py::none(), py::arg("pool") = py::none(), py::arg("up") = py::none(),
-        py::arg("up_oy") = 0, py::arg("up_ox") = 0, py::arg("wfrag") = py::none());
+        py::arg("up_oy") = 0, py::arg("up_ox") = 0, py::arg("wfrag") = py::none(), py::arg("in_coef") = py::none(),
+        py::arg("a_out") = py::none());
+  m.def("conv_dgrad", on_device(&conv_dgrad), py::arg("dy"), py::arg("w"), py::arg("dx1"), py::arg("dx2") = py::none(),
+        py::arg("ws") = py::none(), py::arg("bn_y") = py::none(), py::arg("bn_coef") = py::none(),
+        py::arg("bn_partial") = py::none(), py::arg("kernel") = (int)RDP_CONV_AUTO);
   m.def("conv_ws_elems", &rdp_conv_ws_elems);
   m.def("conv_stats_rows", &rdp_conv_stats_rows);
   // the kernels conv_fwd's bm_pref may name (csrc/conv_plan.h RdpConvKernel), as plain ints
@@ -2120,13 +2122,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_plan", &conv_plan, py::arg("n"), py::arg("h"), py::arg("w"), py::arg("c1"), py::arg("c2"), py::arg("cout"),
         py::arg("taps") = 9, py::arg("packed") = 0, py::arg("kernel") = 0, py::arg("stats") = false,
         py::arg("eval") = false, py::arg("split") = 0, py::arg("ws_elems") = 0, py::arg("pool") = false,
-        py::arg("up") = false, py::arg("bn") = false, py::arg("wfrag") = false,
-        "host only, launches nothing: what conv_fwd would run for a dense conv of this shape (rdp_conv_plan)");
+        py::arg("up") = false, py::arg("bn") = false, py::arg("wfrag") = false, py::arg("bnin") = false,
+        "host only, launches nothing: what conv_fwd / conv_dgrad would run for a dense conv of this shape "
+        "(rdp_conv_plan)");
+  // the row ring's forms (csrc/conv_plan.h RdpRingForm): conv_plan's ring_form
+  m.attr("RING_PLAIN") = (int)RDP_RING_PLAIN; m.attr("RING_POOL") = (int)RDP_RING_POOL;
+  m.attr("RING_BNRED") = (int)RDP_RING_BNRED; m.attr("RING_BNIN") = (int)RDP_RING_BNIN;
   m.def("conv_wgrad", on_device(&conv_wgrad), py::arg("x1"), py::arg("x2"), py::arg("dy"), py::arg("taps"),
         py::arg("packed"), py::arg("cin_real"), py::arg("slab"), py::arg("out"), py::arg("accumulate"),
         py::arg("splits"), py::arg("variant"));
-  m.def("conv_fwd_bnin", on_device(&conv_fwd_bnin), py::arg("x_pre"), py::arg("w"), py::arg("y"), py::arg("stats"),
-        py::arg("in_coef"), py::arg("a_out") = py::none());
   m.def("wgrad_first_bn", on_device(&wgrad_first_bn));
   m.def("wgrad_slab_elems", &rdp_conv_wgrad_slab_elems);
   m.def("wgrad_halo_slab_elems", &rdp_conv_wgrad_halo_slab_elems);
@@ -2144,9 +2148,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_eval_coef", on_device(&bn_eval_coef));
   m.def("bn_relu_apply", on_device(&bn_relu_apply));
   m.def("bn_relu_bwd_reduce", on_device(&bn_relu_bwd_reduce));
-  m.def("conv_dgrad_bnred", on_device(&conv_dgrad_bnred));
-  m.def("conv_dgrad_splitk_bnred", on_device(&conv_dgrad_splitk_bnred), py::arg("dy"), py::arg("w"), py::arg("dx"),
-        py::arg("y_bn"), py::arg("coef"), py::arg("partial"), py::arg("ws") = py::none());
   m.def("bn_bwd_finalize", on_device(&bn_bwd_finalize));
   m.def("bn_relu_bwd_apply", on_device(&bn_relu_bwd_apply));
   m.def("maxpool2_fwd", on_device(&maxpool2_fwd));

@@ -1041,12 +1041,12 @@ static ConvArgs conv_args(const RdpConv& c, int taps, int packed, float* ws, con
 
 extern "C" int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int kernel, float* ws, long ws_elems,
                               const void* wfrag, long wfrag_bytes, const RdpConvFuse& fuse, int* pooled,
-                              const RdpConvBnBwd& bn, int* bnrows, hipStream_t s) {
+                              const RdpConvBnBwd& bn, int* bnrows, const RdpConvBnIn& in, hipStream_t s) {
   if (pooled) *pooled = 0;
   if (bnrows) *bnrows = 0;
   const bool has_ws = ws != nullptr && ws_elems > 0;
-  const RdpConvPlan p =
-      rdp_conv_plan(c, taps, packed, kernel, has_ws, ws_elems, fuse, pooled != nullptr, bn, wfrag ? wfrag_bytes : 0);
+  const RdpConvPlan p = rdp_conv_plan(c, taps, packed, kernel, has_ws, ws_elems, fuse, pooled != nullptr, bn, in,
+                                      wfrag ? wfrag_bytes : 0);
   switch (p.kernel) {
     case RDP_CONV_UNSUPPORTED: return -1;
     case RDP_CONV_FIRST: return rdp_conv_first(c, s);
@@ -1059,9 +1059,9 @@ extern "C" int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int kernel
       return r < 0 ? -1 : 0;
     }
     case RDP_CONV_RING: {
-      if (!p.pool_fused) return rdp_conv_ring(c, 256, s);
-      const int r = rdp_conv_ring_pool(c, fuse.pool, fuse.ppitch, s);
-      if (r == 0) *pooled = 1;
+      const int r = rdp_conv_ring(c, p.ring_form, fuse, bn, in, s);
+      if (r >= 0 && p.pool_fused) *pooled = 1;
+      if (r >= 0 && p.bn_rows && bnrows) *bnrows = r;
       return r;
     }
     case RDP_CONV_RING2:

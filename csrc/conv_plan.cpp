@@ -30,6 +30,11 @@ bool pp_split_enabled() {  // RDP_PP_SPLIT=0: the 128 x 128 split-K kernel inste
   return on != 0;
 }
 
+bool splitk_bnred_on() {  // RDP_SPLITK_BNRED=0: the split-K reduce leaves the BN-backward rows to a separate pass
+  static const int on = env_int("RDP_SPLITK_BNRED", 1);
+  return on != 0;
+}
+
 // the row-ring grid: blocks of pairs_per_block row pairs
 void ring_grid(RdpRingGeo& g, int N, int H, int W, int max_blocks) {
   g.WS = W / 64;
@@ -185,7 +190,8 @@ RdpRowbandGeo rdp_rowband_geo(const RdpConv& c, bool pool, long pbytes, int ppit
 }
 
 // ---- row ring --------------------------------------------------------------------------------------------------
-RdpRingGeo rdp_ring_geo(const RdpConv& c, const RdpRingFuse& f, RdpRingForm form, int ppitch, int max_blocks) {
+RdpRingGeo rdp_ring_geo(const RdpConv& c, RdpRingForm form, int ppitch, int max_blocks, const RdpConvBnBwd& bn,
+                        const RdpConvBnIn& in) {
   RdpRingGeo g;
   if (c.C1 != 64 || c.W % 64 || c.H % 2 || c.ldw < 576) return g;
   if (c.xbytes1 >= kMaxBytes || c.wbytes >= kMaxBytes) return g;
@@ -193,9 +199,11 @@ RdpRingGeo rdp_ring_geo(const RdpConv& c, const RdpRingFuse& f, RdpRingForm form
     if (c.Cout != 64 || !c.escale || !c.eshift) return g;
     if (form == RDP_RING_POOL && (ppitch % 4 || c.ybytes1 >= kMaxBytes || c.y2 || c.Cy1 != 64)) return g;
   } else {
-    if (f.aout && (!f.iscale || f.abytes >= kMaxBytes || f.apitch % 8)) return g;
-    if (f.bn_y && (!c.stats || c.escale || c.y2 || f.bn_ypitch % 4 || c.Cout != 64)) return g;
-    if (f.iscale && (!f.ishift || f.bn_y || c.escale || c.y2 || c.Cout != 64)) return g;
+    const bool unfusable = c.escale || c.y2 || c.Cout != 64;  // what neither fused training form takes
+    const bool bn_ok = bn.bny && bn.bncoef && bn.bnpart && bn.bnypitch % 4 == 0 && !c.stats;
+    if (form == RDP_RING_BNRED && (!bn_ok || unfusable)) return g;
+    if (form == RDP_RING_BNIN && (!in.iscale || !in.ishift || unfusable)) return g;
+    if (form == RDP_RING_BNIN && in.aout && (in.abytes >= kMaxBytes || in.apitch % 8)) return g;
     if ((c.Cout != 64 && c.Cout != 128) || c.Cy1 % 32) return g;
     if (c.y2 == nullptr && c.Cy1 != c.Cout) return g;
     if (c.ybytes1 >= kMaxBytes || c.ybytes2 >= kMaxBytes) return g;
@@ -270,8 +278,8 @@ RdpConvFuseOk rdp_conv_fuse_ok(const RdpConv& c, const RdpConvFuse& fuse, bool w
           c.escale != nullptr && c.eshift != nullptr && c.Cout % RDP_UP_CG == 0 && fuse.upitch % 4 == 0 &&
           (long)(RDP_UP_TY / 2 + 2) * c.W * RDP_UP_CG * 2 <= 65536 && fuse.uH >= 2 * c.H && fuse.uW >= 2 * c.W &&
           (long)c.H * c.W <= 256;
-  ok.bn = bn.bnpart && bn.bny && bn.bncoef && !c.stats && !c.escale && c.y2 == nullptr && c.Cy1 == c.Cout &&
-          bn.bnypitch % 4 == 0 && fuse.pool == nullptr && fuse.up == nullptr;
+  ok.bn = splitk_bnred_on() && bn.bnpart && bn.bny && bn.bncoef && !c.stats && !c.escale && c.y2 == nullptr &&
+          c.Cy1 == c.Cout && bn.bnypitch % 4 == 0 && fuse.pool == nullptr && fuse.up == nullptr;
   return ok;
 }
 
@@ -584,7 +592,8 @@ extern "C" long rdp_conv_wgrad_halo_slab_elems(int N, int H, int W, int Cin, int
 
 // ---- the plan --------------------------------------------------------------------------------------------------
 RdpConvPlan rdp_conv_plan(const RdpConv& c, int taps, int packed, int kernel, bool has_ws, long ws_elems,
-                          const RdpConvFuse& fuse, bool want_fused, const RdpConvBnBwd& bn, long wfrag_bytes) {
+                          const RdpConvFuse& fuse, bool want_fused, const RdpConvBnBwd& bn, const RdpConvBnIn& in,
+                          long wfrag_bytes) {
   RdpConvPlan p;
   const RdpConvPlan none;
   bool known = false;
@@ -593,6 +602,28 @@ RdpConvPlan rdp_conv_plan(const RdpConv& c, int taps, int packed, int kernel, bo
   const bool autok = kernel == RDP_CONV_AUTO;
   const int Cin = c.C1 + c.C2;
   const bool wpool = fuse.pool != nullptr && want_fused, wup = fuse.up != nullptr && want_fused;
+
+  // The row ring's fused training forms, before everything else. Neither has a grid threshold: the plain ring is
+  // auto only from 256 row pairs (below), but a fused form also saves its layer a whole pass over the tensor, so
+  // it runs at any size the kernel takes.
+  const bool ring_ok = (autok || kernel == RDP_CONV_RING) && taps == 9 && !packed && c.C2 == 0 && c.x2 == nullptr;
+  auto ring_fused = [&](RdpRingForm form) {
+    const RdpRingGeo g = ring_ok ? rdp_ring_geo(c, form, 0, 256, bn, in) : RdpRingGeo{};
+    if (g.fits) {
+      p.kernel = RDP_CONV_RING;
+      p.ring_form = form;
+      p.grid = g.grid;
+      p.stats_rows = g.rows;
+      if (form == RDP_RING_BNRED) p.bn_rows = g.rows;
+    }
+    return g.fits;
+  };
+  const bool bn_offered = bn.bny && bn.bncoef && bn.bnpart;
+  // the producer's BN + ReLU applied to the input: nothing but the ring can read a pre-BN tensor
+  if (in.iscale) return !bn_offered && !wpool && !wup && ring_fused(RDP_RING_BNIN) ? p : none;
+  // the owner's BN-backward rows from the ring epilogue; where it does not fit, the decision below is the one
+  // without the block, and only a split-K reduce can still write the rows (rdp_conv_fuse_ok)
+  if (bn_offered && ring_fused(RDP_RING_BNRED)) return p;
 
   // first layer (3-channel input, packed K): auto for it (IGEMM4_256 runs the packed implicit GEMM, the tests'
   // second opinion)
@@ -640,11 +671,12 @@ RdpConvPlan rdp_conv_plan(const RdpConv& c, int taps, int packed, int kernel, bo
     if (taps == 9 && !packed && c.C2 == 0 && c.x2 == nullptr) {
       RdpRingGeo g;
       if (wpool && !c.stats && !c.y2 && c.escale)  // eval: MaxPool2d fused into the ring epilogue
-        g = rdp_ring_geo(c, RdpRingFuse{}, RDP_RING_POOL, fuse.ppitch, 256);
+        g = rdp_ring_geo(c, RDP_RING_POOL, fuse.ppitch, 256);
       const bool pools = g.fits;
-      if (!pools) g = rdp_ring_geo(c, RdpRingFuse{}, RDP_RING_PLAIN, 0, 256);
+      if (!pools) g = rdp_ring_geo(c, RDP_RING_PLAIN, 0, 256);
       if (g.fits) {
         p.kernel = RDP_CONV_RING;
+        p.ring_form = pools ? RDP_RING_POOL : RDP_RING_PLAIN;
         p.pool_fused = pools;
         p.grid = g.grid;
         p.stats_rows = g.rows;
@@ -777,12 +809,13 @@ RdpConvPlan rdp_conv_plan_dense(const RdpConvQuery& q) {
   static char mark;
   static float fmark;
   const int Cin = q.C1 + q.C2, Cy1 = q.split > 0 ? q.split : q.Cout;
+  auto bytes = [&](int C) { return (long)q.N * q.H * q.W * C * 2; };
   RdpConv c;
-  c.x1 = &mark; c.C1 = q.C1; c.pitch1 = q.C1;
-  if (q.C2) { c.x2 = &mark; c.C2 = q.C2; c.pitch2 = q.C2; }
+  c.x1 = &mark; c.C1 = q.C1; c.pitch1 = q.C1; c.xbytes1 = bytes(q.C1);
+  if (q.C2) { c.x2 = &mark; c.C2 = q.C2; c.pitch2 = q.C2; c.xbytes2 = bytes(q.C2); }
   c.w = &mark; c.ldw = q.packed ? 128 : q.taps * Cin; c.wbytes = (long)q.Cout * c.ldw * 2;
-  c.y1 = &mark; c.Cy1 = Cy1; c.ypitch1 = Cy1;
-  if (q.split > 0) { c.y2 = &mark; c.ypitch2 = q.Cout - Cy1; }
+  c.y1 = &mark; c.Cy1 = Cy1; c.ypitch1 = Cy1; c.ybytes1 = bytes(Cy1);
+  if (q.split > 0) { c.y2 = &mark; c.ypitch2 = q.Cout - Cy1; c.ybytes2 = bytes(q.Cout - Cy1); }
   c.N = q.N; c.H = q.H; c.W = q.W; c.Cout = q.Cout;
   if (q.stats) c.stats = &fmark;
   if (q.eval) { c.escale = &fmark; c.eshift = &fmark; c.erelu = 1; }
@@ -791,7 +824,9 @@ RdpConvPlan rdp_conv_plan_dense(const RdpConvQuery& q) {
   if (q.up) { fuse.up = &mark; fuse.upitch = q.Cout; fuse.uH = 2 * q.H; fuse.uW = 2 * q.W; }
   RdpConvBnBwd bn;
   if (q.bn) { bn.bny = &mark; bn.bnypitch = q.Cout; bn.bncoef = &fmark; bn.bnpart = &fmark; }
-  return rdp_conv_plan(c, q.taps, q.packed, q.kernel, q.ws_elems > 0, q.ws_elems, fuse, q.pool || q.up, bn,
+  RdpConvBnIn in;
+  if (q.bnin) { in.iscale = in.ishift = &fmark; in.aout = &mark; in.apitch = q.C1; in.abytes = bytes(q.C1); }
+  return rdp_conv_plan(c, q.taps, q.packed, q.kernel, q.ws_elems > 0, q.ws_elems, fuse, q.pool || q.up, bn, in,
                        q.wfrag ? (long)q.Cout * 9 * Cin * 2 : 0);
 }
 

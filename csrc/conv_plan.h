@@ -44,27 +44,34 @@ struct RdpConvFuse {
   int upitch = 0, uH = 0, uW = 0, uoy = 0, uox = 0;
 };
 // rdp_conv_igemm, training dgrad into one BN + ReLU layer's activation gradient, optional: that layer's pre-BN
-// output bny, its coefficients bncoef [mean|invstd|scale|shift], and bnpart, which receives its BN-backward partial
-// rows from the split-K reduce when that path runs
+// output bny, its coefficients bncoef [mean|invstd|scale|shift] (ReLU applied), and bnpart, which receives its
+// BN-backward partial rows where the kernel that runs can write them: the row ring's epilogue (RDP_RING_BNRED) or
+// the split-K reduce. A block counts as offered when all three pointers are set.
 struct RdpConvBnBwd {
   const void* bny = nullptr;
   int bnypitch = 0;
   const float* bncoef = nullptr;
   float* bnpart = nullptr;
 };
-// rdp_conv_ring_ex, optional and exclusive: bn_y / bn_coef = the dgrad form (the BN-backward partial rows of the
-// layer that owns the output go to stats; bn_y: its pre-BN activations, bn_coef: its [mean|invstd|scale|shift],
-// ReLU applied); iscale / ishift = BN + ReLU of the producer layer applied to the staged input rows, which aout
-// (optional) also receives as an activation tensor
-struct RdpRingFuse {
-  const void* bn_y = nullptr;
-  int bn_ypitch = 0;
-  const float* bn_coef = nullptr;
+// rdp_conv_igemm, training forward, optional (iscale set: offered): x1 is the producer layer's pre-BN output and the
+// conv applies that layer's BN + ReLU (iscale / ishift per input channel) to the rows it stages; aout (optional)
+// also receives the formed activation as a tensor. Only the row ring (RDP_RING_BNIN) can read such an input.
+struct RdpConvBnIn {
   const float* iscale = nullptr;
   const float* ishift = nullptr;
   void* aout = nullptr;
   long abytes = 0;
   int apitch = 0;
+};
+// rdp_conv_ring_head: the serving 1x1 head fused into the eval ring conv, which then writes only the u8 mask.
+// K = 1: mask = (logit > thr), hw [64], hb [1]; 2 <= K <= 8: mask = (arg-max class == cls), hw [K][64], hb [K]
+struct RdpRingHead {
+  const float* hw = nullptr;
+  const float* hb = nullptr;
+  int K = 1;
+  float thr = 0.f;
+  int cls = 0;
+  void* mask = nullptr;
 };
 
 // ---- the kernels -------------------------------------------------------------------------------------------------
@@ -86,7 +93,7 @@ enum RdpConvKernel : int {
   RDP_CONV_PP256 = 4,
   RDP_CONV_PP128 = 5,
   // conv_ring.hip: 64 -> 64 / 128 channels, 3x3, one source, W % 64 == 0, even H; the eval MaxPool2d fused where
-  // asked for; auto from 256 row pairs
+  // asked for; auto from 256 row pairs, and at any size in its fused training forms (RdpConvBnBwd, RdpConvBnIn)
   RDP_CONV_RING = 6,
   // the ping-pong kernel with K split over work items (rdp_pp_split) + the shared reduce, 256 x 128 / 256 x 256:
   // auto (128) for small M x long K
@@ -153,11 +160,10 @@ struct RdpRingGeo {
   bool fits = false;
   int WS = 0, nrows = 0, npairs = 0, pairs_per_block = 0, grid = 0, rows = 0;
 };
-inline RdpRingForm rdp_ring_form(const RdpRingFuse& f) {
-  return f.bn_y ? RDP_RING_BNRED : f.iscale ? RDP_RING_BNIN : RDP_RING_PLAIN;
-}
-// ppitch: the pool's pixel pitch (POOL); max_blocks caps the grid (<= 0: 256)
-RdpRingGeo rdp_ring_geo(const RdpConv& c, const RdpRingFuse& f, RdpRingForm form, int ppitch, int max_blocks);
+// ppitch: the pool's pixel pitch (POOL); max_blocks caps the grid (<= 0: 256); bn: the BNRED form's operand (its
+// rows go to bn.bnpart, c.stats stays null); in: the BNIN form's
+RdpRingGeo rdp_ring_geo(const RdpConv& c, RdpRingForm form, int ppitch, int max_blocks,
+                        const RdpConvBnBwd& bn = RdpConvBnBwd{}, const RdpConvBnIn& in = RdpConvBnIn{});
 // conv_ring2_kernel: c = the two 64-channel sources; the launch computes output channels co0 .. co0 + 63 of a
 // cout_total-channel conv
 RdpRingGeo rdp_ring2_geo(const RdpConv& c, int max_blocks, int cout_total, int co0);
@@ -182,6 +188,7 @@ struct RdpGemmShape {
   int N = 0, uH = 0;  // the fused upsample's grid: images x rows of its output map
 };
 // what the split-K reduce may fuse (each needs the split to happen): the eval pool / upsample, the BN-backward rows
+// (RDP_SPLITK_BNRED=0 takes the rows out, A/B: the caller's separate pass then; the ring form is not affected)
 struct RdpConvFuseOk {
   bool pool = false, up = false, bn = false;
 };
@@ -214,19 +221,24 @@ struct RdpConvPlan {
   int kernel = RDP_CONV_UNSUPPORTED;  // the kernel that runs (never AUTO)
   int BM = 0, BN = 0, waves = 0, ksplit = 1;  // implicit GEMM / ping-pong: tile, waves per block, K split
   int rowband_mode = 0;                       // ROWBAND: the wfrag mode
+  int ring_form = RDP_RING_PLAIN;             // RING: the RdpRingForm that runs (PLAIN, POOL, BNRED or BNIN)
   int launches = 1;   // conv launches (RING2X2: 2), each of grid blocks
   int grid = 0;
   int rgrid = 0;      // blocks of the split-K reduce launch (0: none)
   int stats_rows = 0; // what rdp_conv_igemm returns: the rows of the stats slab the conv writes when it has one
   long ws_elems = 0;  // fp32 workspace elements the launch uses
   bool pool_fused = false, up_fused = false;  // fuse's pool / upsample is written by the conv
-  int bn_rows = 0;    // rows written to bn.bnpart
+  int bn_rows = 0;    // rows written to bn.bnpart (0: none, the caller runs the separate reduce pass)
 };
 // The dispatcher's decision, launching nothing. kernel: an RdpConvKernel (anything else: unsupported); has_ws /
 // ws_elems: the split-K workspace offered; want_fused: the caller can take a fused pool / upsample (passes the
 // result cell); wfrag_bytes: extent of the fragment-major weight copy (0: none given).
+// bn offered (kernel AUTO or RING): the ring in its BNRED form wherever rdp_ring_geo fits it, else the decision
+// without the block, the split-K reduce writing the rows where rdp_conv_fuse_ok allows, else bn_rows = 0.
+// in offered: the ring in its BNIN form wherever rdp_ring_geo fits it, else unsupported.
 RdpConvPlan rdp_conv_plan(const RdpConv& c, int taps, int packed, int kernel, bool has_ws, long ws_elems,
-                          const RdpConvFuse& fuse, bool want_fused, const RdpConvBnBwd& bn, long wfrag_bytes);
+                          const RdpConvFuse& fuse, bool want_fused, const RdpConvBnBwd& bn, const RdpConvBnIn& in,
+                          long wfrag_bytes);
 // the part of an offered workspace a split may use: slab bytes < 2 GiB (buffer offsets)
 inline long rdp_conv_ws_limit(bool has_ws, long ws_elems) {
   return has_ws && ws_elems > 0 ? (ws_elems < (1L << 29) ? ws_elems : (1L << 29)) : 0;
@@ -240,11 +252,12 @@ RdpConv rdp_ring2_sources(const RdpConv& c);
 
 // A conv described by its shape alone, for callers without tensors (sizing, the conv_plan binding, the CPU test):
 // rdp_conv_plan on a dense block of that shape. split > 0: two destinations, split | Cout - split channels;
-// stats / eval: the training / eval form; pool, up (to [2H][2W]), bn, wfrag: those operands are offered;
-// ws_elems > 0: a workspace of that size is.
+// stats / eval: the training / eval form; pool, up (to [2H][2W]), bn, bnin, wfrag: those operands are offered;
+// ws_elems > 0: a workspace of that size is. The extents are those of dense tensors, so a shape whose tensors reach
+// 2 GiB plans as unsupported: callers that run such a batch as image slices ask about one slice.
 struct RdpConvQuery {
   int N = 0, H = 0, W = 0, C1 = 0, C2 = 0, Cout = 0, taps = 9, packed = 0, kernel = RDP_CONV_AUTO, split = 0;
-  bool stats = false, eval = false, pool = false, up = false, bn = false, wfrag = false;
+  bool stats = false, eval = false, pool = false, up = false, bn = false, bnin = false, wfrag = false;
   long ws_elems = 0;
 };
 RdpConvPlan rdp_conv_plan_dense(const RdpConvQuery& q);

@@ -615,8 +615,10 @@ __global__ __launch_bounds__(512, 2) void conv_ring_kernel(const RingArgs a) {
   }
 }
 
-// The one RdpConv -> RingArgs fill, for every form of the kernel (the head and pool forms add their own fields)
-static RingArgs ring_args(const RdpConv& c, const RdpRingFuse& f, const RdpRingGeo& g) {
+// The one RdpConv -> RingArgs fill, for every form of the kernel (the head and pool forms add their own fields).
+// BNRED: the epilogue's partial rows are the owner layer's, so they go to bn.bnpart
+static RingArgs ring_args(const RdpConv& c, const RdpRingGeo& g, const RdpConvBnBwd& bn = RdpConvBnBwd{},
+                          const RdpConvBnIn& in = RdpConvBnIn{}) {
   RingArgs a = {};
   a.x = (const u16*)c.x1; a.xbytes = (uint32_t)c.xbytes1; a.pitch = c.pitch1;
   a.w = (const u16*)c.w; a.wbytes = (uint32_t)c.wbytes; a.ldw = c.ldw;
@@ -624,10 +626,10 @@ static RingArgs ring_args(const RdpConv& c, const RdpRingFuse& f, const RdpRingG
   a.y2 = (u16*)(c.y2 ? c.y2 : c.y1); a.ybytes2 = c.y2 ? (uint32_t)c.ybytes2 : 0u;
   a.ypitch2 = c.y2 ? c.ypitch2 : c.ypitch1;
   a.Cy1 = c.Cy1;
-  a.stats = c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
-  a.bny = (const u16*)f.bn_y; a.bnypitch = f.bn_ypitch; a.bncoef = f.bn_coef;
-  a.iscale = f.iscale; a.ishift = f.ishift;
-  a.aout = (u16*)f.aout; a.abytes = (uint32_t)f.abytes; a.apitch = f.apitch;
+  a.stats = bn.bny ? bn.bnpart : c.stats; a.escale = c.escale; a.eshift = c.eshift; a.erelu = c.erelu;
+  a.bny = (const u16*)bn.bny; a.bnypitch = bn.bnypitch; a.bncoef = bn.bncoef;
+  a.iscale = in.iscale; a.ishift = in.ishift;
+  a.aout = (u16*)in.aout; a.abytes = (uint32_t)in.abytes; a.apitch = in.apitch;
   a.H = c.H; a.W = c.W; a.WS = g.WS;
   a.nrows = g.nrows; a.npairs = g.npairs; a.pairs_per_block = g.pairs_per_block;
   const FastDiv fh = make_fastdiv((uint32_t)c.H), fs = make_fastdiv((uint32_t)g.WS);
@@ -635,51 +637,22 @@ static RingArgs ring_args(const RdpConv& c, const RdpRingFuse& f, const RdpRingG
   return a;
 }
 
-// the eval conv (64 -> 64, BN folded + ReLU) whose output only the fused serving heads consume
-static RdpConv ring_head_conv(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw, int Cout,
-                              int N, int H, int W, const float* escale, const float* eshift) {
-  RdpConv c;
-  c.x1 = x; c.xbytes1 = xbytes; c.C1 = C; c.pitch1 = pitch;
-  c.w = w; c.wbytes = wbytes; c.ldw = ldw;
-  c.Cy1 = 64; c.ypitch1 = 64;
-  c.N = N; c.H = H; c.W = W; c.Cout = Cout;
-  c.escale = escale; c.eshift = eshift; c.erelu = 1;
-  return c;
-}
-
-extern "C" int rdp_conv_ring(const RdpConv& c, int max_blocks, hipStream_t s) {
-  return rdp_conv_ring_ex(c, max_blocks, RdpRingFuse{}, s);
-}
-
-extern "C" int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
-                                  int Cout, int N, int H, int W, const float* escale, const float* eshift,
-                                  const float* hw, const float* hb, float hthr, void* mask, hipStream_t s) {
-  const RdpConv c = ring_head_conv(x, xbytes, C, pitch, w, wbytes, ldw, Cout, N, H, W, escale, eshift);
-  const RdpRingGeo g = rdp_ring_geo(c, RdpRingFuse{}, RDP_RING_HEAD, 0, 256);
-  if (!g.fits || !hw || !hb || !mask) return -1;
-  RingArgs a = ring_args(c, RdpRingFuse{}, g);
-  a.hw = hw; a.hb = hb; a.hthr = hthr; a.hmask = (uint8_t*)mask;
-  hipLaunchKernelGGL((conv_ring_kernel<64, false, true>), dim3(g.grid), dim3(512), 0, s, a);
-  return 0;
-}
-
 template <int K>
 static void launch_ring_headk(int grid, hipStream_t s, const RingArgs& a) {
   hipLaunchKernelGGL((conv_ring_kernel<64, false, false, false, false, K>), dim3(grid), dim3(512), 0, s, a);
 }
 
-extern "C" int rdp_conv_ring_headk(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw,
-                                   int Cout, int N, int H, int W, const float* escale, const float* eshift,
-                                   const float* hw, const float* hb, int K, int cls, void* mask, hipStream_t s) {
-  const RdpConv c = ring_head_conv(x, xbytes, C, pitch, w, wbytes, ldw, Cout, N, H, W, escale, eshift);
-  const RdpRingGeo g = rdp_ring_geo(c, RdpRingFuse{}, RDP_RING_HEAD, 0, 256);
-  if (!g.fits || !hw || !hb || !mask) return -1;
-  // (a channel-sliced view of a wider tensor, pitch != 64, keeps the separate launches)
-  if (pitch != 64 || K < 2 || K > 8 || cls < 0 || cls >= K || N <= 0 || H <= 0 || (long)N * H * W >= (1l << 31))
+extern "C" int rdp_conv_ring_head(const RdpConv& c, const RdpRingHead& h, hipStream_t s) {
+  const RdpRingGeo g = rdp_ring_geo(c, RDP_RING_HEAD, 0, 256);
+  if (!g.fits || !h.hw || !h.hb || !h.mask) return -1;
+  // K classes: a channel-sliced view of a wider tensor, pitch != 64, keeps the separate launches
+  if (h.K != 1 && (c.pitch1 != 64 || h.K < 2 || h.K > 8 || h.cls < 0 || h.cls >= h.K || c.N <= 0 || c.H <= 0 ||
+                   (long)c.N * c.H * c.W >= (1l << 31)))
     return -1;
-  RingArgs a = ring_args(c, RdpRingFuse{}, g);
-  a.hw = hw; a.hb = hb; a.hmask = (uint8_t*)mask; a.hcls = cls;
-  switch (K) {
+  RingArgs a = ring_args(c, g);
+  a.hw = h.hw; a.hb = h.hb; a.hthr = h.thr; a.hmask = (uint8_t*)h.mask; a.hcls = h.cls;
+  switch (h.K) {
+    case 1: hipLaunchKernelGGL((conv_ring_kernel<64, false, true>), dim3(g.grid), dim3(512), 0, s, a); break;
     case 2: launch_ring_headk<2>(g.grid, s, a); break;
     case 3: launch_ring_headk<3>(g.grid, s, a); break;
     case 4: launch_ring_headk<4>(g.grid, s, a); break;
@@ -691,23 +664,18 @@ extern "C" int rdp_conv_ring_headk(const void* x, long xbytes, int C, int pitch,
   return 0;
 }
 
-extern "C" int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipStream_t s) {
-  const RdpRingGeo g = rdp_ring_geo(c, RdpRingFuse{}, RDP_RING_POOL, ppitch, 256);
-  if (!g.fits || !pool) return -1;
-  RingArgs a = ring_args(c, RdpRingFuse{}, g);
-  a.pool = (u16*)pool; a.ppitch = ppitch;
-  hipLaunchKernelGGL((conv_ring_kernel<64, false, false, true>), dim3(g.grid), dim3(512), 0, s, a);
-  return 0;
-}
-
-extern "C" int rdp_conv_ring_ex(const RdpConv& c, int max_blocks, const RdpRingFuse& f, hipStream_t s) {
-  const RdpRingForm form = rdp_ring_form(f);
-  const RdpRingGeo g = rdp_ring_geo(c, f, form, 0, max_blocks);
-  if (!g.fits) return -1;
-  const RingArgs a = ring_args(c, f, g);
-  if (c.Cout == 128) hipLaunchKernelGGL((conv_ring_kernel<128>), dim3(g.grid), dim3(512), 0, s, a);
-  else if (form == RDP_RING_BNRED) hipLaunchKernelGGL((conv_ring_kernel<64, true>), dim3(g.grid), dim3(512), 0, s, a);
-  else if (form == RDP_RING_BNIN)
+extern "C" int rdp_conv_ring(const RdpConv& c, int form, const RdpConvFuse& fuse, const RdpConvBnBwd& bn,
+                             const RdpConvBnIn& in, hipStream_t s) {
+  const bool bnred = form == RDP_RING_BNRED, bnin = form == RDP_RING_BNIN, pool = form == RDP_RING_POOL;
+  if (!bnred && !bnin && !pool && form != RDP_RING_PLAIN) return -1;
+  const RdpRingGeo g = rdp_ring_geo(c, (RdpRingForm)form, pool ? fuse.ppitch : 0, 256, bn, in);
+  if (!g.fits || (pool && !fuse.pool)) return -1;
+  RingArgs a = ring_args(c, g, bnred ? bn : RdpConvBnBwd{}, bnin ? in : RdpConvBnIn{});
+  if (pool) { a.pool = (u16*)fuse.pool; a.ppitch = fuse.ppitch; }
+  if (pool) hipLaunchKernelGGL((conv_ring_kernel<64, false, false, true>), dim3(g.grid), dim3(512), 0, s, a);
+  else if (c.Cout == 128) hipLaunchKernelGGL((conv_ring_kernel<128>), dim3(g.grid), dim3(512), 0, s, a);
+  else if (bnred) hipLaunchKernelGGL((conv_ring_kernel<64, true>), dim3(g.grid), dim3(512), 0, s, a);
+  else if (bnin)
     hipLaunchKernelGGL((conv_ring_kernel<64, false, false, false, true>), dim3(g.grid), dim3(512), 0, s, a);
   else hipLaunchKernelGGL((conv_ring_kernel<64>), dim3(g.grid), dim3(512), 0, s, a);
   return g.rows;

@@ -6,7 +6,8 @@
 
 #include "rdp_host_api.h"
 
-// The conv family's operand blocks (RdpConv, RdpConvFuse, RdpConvBnBwd, RdpRingFuse, RdpWgrad, RdpWgradBn, RdpUpT), the
+// The conv family's operand blocks (RdpConv, RdpConvFuse, RdpConvBnBwd, RdpConvBnIn, RdpRingHead, RdpWgrad, RdpWgradBn,
+// RdpUpT), the
 // kernel names and the plans
 #include "conv_plan.h"
 
@@ -46,32 +47,26 @@ int rdp_conv_upT_dgrad(const RdpConv& c, const RdpUpT& t, hipStream_t s);
 // force. ws: the split-K fp32 slab of ws_elems elements (rdp_conv_ws_elems), or nullptr. wfrag / wfrag_bytes: the
 // fragment-major copy of the weights for the row-band kernel, or nullptr. *pooled = 1 if fuse's pool / upsample was
 // written, else 0 (the caller launches the pool / upsample; nullptr: no fusion). *bnrows = the rows written to
-// bn.bnpart, else 0 (the caller runs bn_relu_bwd_reduce).
+// bn.bnpart by the ring epilogue or the split-K reduce, else 0 (the caller runs bn_relu_bwd_reduce). in: x1 is
+// the producer's pre-BN output (only the ring's BNIN form runs it: anything else is unsupported).
 int rdp_conv_igemm(const RdpConv& c, int taps, int packed, int kernel, float* ws, long ws_elems, const void* wfrag,
                    long wfrag_bytes, const RdpConvFuse& fuse, int* pooled, const RdpConvBnBwd& bn, int* bnrows,
-                   hipStream_t s);
+                   const RdpConvBnIn& in, hipStream_t s);
 
 // ---- csrc/conv_ring.hip ---------------------------------------------------------------------------------------
 // The ring kernel (3x3, one 64-channel source, 64 or 128 outputs -- split at a multiple of 32 into two
-// destinations --, W % 64 == 0, even H: rdp_ring_geo); max_blocks caps the grid (<= 0: 256). Returns the stats
-// rows it writes, or -1 when not applicable.
-int rdp_conv_ring(const RdpConv& c, int max_blocks, hipStream_t s);
-int rdp_conv_ring_ex(const RdpConv& c, int max_blocks, const RdpRingFuse& f, hipStream_t s);
-// Eval conv (64 -> 64, BN folded + ReLU) fused with the serving 1x1 head: writes only the u8 mask
-// (logit > thr) of the 64-channel output. Returns 0, or -1 when the ring kernel does not apply.
-int rdp_conv_ring_head(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw, int Cout,
-                       int N, int H, int W, const float* escale, const float* eshift, const float* hw,
-                       const float* hb, float hthr, void* mask, hipStream_t s);
-// The same conv fused with the K-class serving head (hw [K*64], hb [K], 2 <= K <= 8): writes only the u8 mask
-// (arg-max class == cls, ties to the lowest class), bit for bit the mask rdp_headk_mask writes from the stored
-// output. Returns 0, or -1 (nothing launched) where the ring kernel does not apply, the input is a strided view
-// (pitch != 64) or K / cls are out of range.
-int rdp_conv_ring_headk(const void* x, long xbytes, int C, int pitch, const void* w, long wbytes, int ldw, int Cout,
-                        int N, int H, int W, const float* escale, const float* eshift, const float* hw,
-                        const float* hb, int K, int cls, void* mask, hipStream_t s);
-// Eval conv (64 -> 64, BN folded + ReLU) that also writes MaxPool2d(2) of its output into pool
-// [N][H/2][W/2][64] (pixel pitch ppitch). Returns 0, or -1 when the ring kernel does not apply.
-int rdp_conv_ring_pool(const RdpConv& c, void* pool, int ppitch, hipStream_t s);
+// destinations --, W % 64 == 0, even H: rdp_ring_geo) in the RdpRingForm the plan names: PLAIN, POOL (eval, 64 ->
+// 64: also MaxPool2d(2) of the output into fuse.pool), BNRED (the owner layer's BN-backward partial rows into
+// bn.bnpart) or BNIN (in: the producer's BN + ReLU applied to the staged input). Returns the partial rows it
+// writes, or -1 (nothing launched) when the form does not apply.
+int rdp_conv_ring(const RdpConv& c, int form, const RdpConvFuse& fuse, const RdpConvBnBwd& bn, const RdpConvBnIn& in,
+                  hipStream_t s);
+// Eval conv (64 -> 64, BN folded + ReLU; c has no destination) fused with the serving 1x1 head: writes only the u8
+// mask of the 64-channel output. h.K = 1: logit > h.thr; 2 <= h.K <= 8: arg-max class == h.cls (ties to the lowest
+// class), bit for bit the mask rdp_headk_mask writes from the stored output. Returns 0, or -1 (nothing launched)
+// where the ring kernel does not apply and, for K classes, where the input is a strided view (pitch != 64) or K /
+// cls are out of range.
+int rdp_conv_ring_head(const RdpConv& c, const RdpRingHead& h, hipStream_t s);
 // Two-source row ring (see conv_ring2_kernel): x1 / x2 = the two 64-channel sources (for one
 // 128-channel tensor: its two halves), 64 outputs into y1, 3x3, W % 64 == 0, even H. cout_total / co0: the
 // launch computes output channels co0 .. co0 + 63 of a cout_total-channel conv (w, y1, escale / eshift

@@ -421,7 +421,7 @@ class _Ablated:
     ``bn_relu_apply``, ``conv_wgrad``), and ``wgsum`` / ``wgred`` drop the weight-gradient slab
     reductions inside ``conv_wgrad`` (csrc/conv_wgrad.hip). The step time without a kernel class bounds
     what fusing or speeding it up can gain (profiles/step_ablation.md)."""
-    RET = {"bn_relu_bwd_reduce": 1, "conv_wgrad": 1, "wgrad_first_bn": 0, "conv_dgrad_bnred": 0}
+    RET = {"bn_relu_bwd_reduce": 1, "conv_wgrad": 1, "wgrad_first_bn": 0}
 
     def __init__(self, C, names):
         self._C, self._names = C, frozenset(names)
@@ -639,8 +639,8 @@ class UNetExecutor:
             pairs = [self.down_layers[0]] + ([self.up_layers[-1]] if self.up_layers else [])
             for la, lb in pairs:
                 n, h, w, c = la.y.shape
-                if (lb.x1 is la.a and lb.x2 is None and c == 64 and lb.spec.cout == 64 and lb.spec.taps == 9
-                        and not lb.spec.packed and w % 64 == 0 and h % 2 == 0 and n * h * w * c * 2 < (1 << 31)):
+                plan = C.conv_plan(n, h, w, c, 0, lb.spec.cout, lb.spec.taps, int(lb.spec.packed), stats=True, bnin=True)
+                if lb.x1 is la.a and lb.x2 is None and plan["kernel"] == C.CONV_RING and plan["chunks"] == 1:
                     lb.bnin = la
                     la.consumer_bnin = True
         # ... and the forward also stores that activation (one extra write) so the weight gradient runs the
@@ -710,8 +710,6 @@ class UNetExecutor:
         dev, bf = self.dev, torch.bfloat16
         # RDP_WGRAD_OVERLAP=0 serialises the wgrads on the main stream (clean per-kernel profiles)
         self.overlap_wgrad = dev.type == "cuda" and os.environ.get("RDP_WGRAD_OVERLAP", "1") != "0"
-        # BN-backward partial rows from the split-K dgrad reduce (RDP_SPLITK_BNRED=0: the separate pass, A/B)
-        self.splitk_bnred = os.environ.get("RDP_SPLITK_BNRED", "1") != "0"
         # a stream whose kernels overlap the main stream's (concurrent_stream: not on its hardware queue)
         self.side = concurrent_stream(dev, [torch.cuda.current_stream(dev)]) if self.overlap_wgrad else None
         # split-K grid target of the generic / packed weight-gradient kernels. Fewer splits = less fp32
@@ -845,8 +843,8 @@ class UNetExecutor:
                        pool, None, 0, 0, wf)
             return pool is not None
         if L.bnin is not None:  # the producer's BN + ReLU applied by this conv (row-ring BNIN)
-            rows = C.conv_fwd_bnin(L.bnin.y, w, L.y, self.stats, L.bnin.coef, L.bnin.a)
-            assert rows > 0, "conv_fwd_bnin: ring kernel not applicable"
+            rows = C.conv_fwd(L.bnin.y, None, w, sp.taps, 0, L.y, None, self.stats, C.CONV_AUTO, None, 0, self.kws,
+                              in_coef=L.bnin.coef, a_out=L.bnin.a)
         else:
             rows = C.conv_fwd(L.x1, L.x2, w, sp.taps, int(sp.packed), L.y, None, self.stats, C.CONV_AUTO, None, 0,
                               self.kws)
@@ -1231,27 +1229,16 @@ class UNetExecutor:
         else:
             self._on_wgrad_stream(lambda slab: C.conv_wgrad(L.x1, L.x2, L.dy, sp.taps, int(sp.packed), sp.cin_real,
                                                             slab, gw, 0, L.splits, C.WGRAD_AUTO))
-        # dgrad into the da of a BN layer: where the row-ring kernel runs it (64 -> 64 channels), its
-        # epilogue also produces that layer's BN-backward partial sums (no bn_relu_bwd_reduce pass)
+        # dgrad into the da of a BN layer: where the row ring runs it (64 -> 64 channels) or the conv splits K (the
+        # reference batch's deep layers), the epilogue / the split-K reduce also writes that layer's BN-backward
+        # partial rows (0 rows: _bn_bwd runs the bn_relu_bwd_reduce pass)
         owner = L.dx1_owner
-        fusable = owner is not None and L.dx2 is None and sp.taps == 9 and not owner.bwd_rows
-        done = False
-        if fusable:
-            rows = C.conv_dgrad_bnred(L.dy, self.m.dgrad_weight(sp), L.dx1, owner.y, owner.coef, self.bn_partial)
-            if rows > 0:
-                owner.bwd_rows = rows
-                done = True
-        if fusable and not done and self.splitk_bnred:
-            # where the dgrad runs split-K (the reference batch's deep layers), the split-K reduce writes the
-            # owner's BN-backward partial rows too: no bn_relu_bwd_reduce pass (0 rows: another path ran)
-            rows = C.conv_dgrad_splitk_bnred(L.dy, self.m.dgrad_weight(sp), L.dx1, owner.y, owner.coef,
-                                             self.bn_partial, self.kws)
-            if rows >= 0:
-                owner.bwd_rows = rows
-                done = True
-        if L.dx1 is not None and not done:
-            C.conv_fwd(L.dy, None, self.m.dgrad_weight(sp), sp.taps, 0, L.dx1, L.dx2, None, C.CONV_AUTO, None, 0,
-                       self.kws)
+        if L.dx1 is not None:
+            if owner is not None and L.dx2 is None and sp.taps == 9 and not owner.bwd_rows:
+                owner.bwd_rows = C.conv_dgrad(L.dy, self.m.dgrad_weight(sp), L.dx1, None, self.kws, owner.y, owner.coef,
+                                              self.bn_partial)
+            else:
+                C.conv_dgrad(L.dy, self.m.dgrad_weight(sp), L.dx1, L.dx2, self.kws)
         if hooks is not None:  # the weight gradient is final once its stream's work so far has run
             hooks(sp, wstream)
 

@@ -80,8 +80,9 @@ def main():
             if a.wgrad:  # v = C.WGRAD_AUTO / GENERIC / HALO
                 C.conv_wgrad(x1, x2, dy, 9, 0, 0, slab, out, 0, splits, v)
             elif v in (9, 10):  # 10: BN-on-input forward that also stores the activation
-                if C.conv_fwd_bnin(x1, w, y, stats, coef, a_st if v == 10 else None) <= 0:
-                    raise RuntimeError("bnin n/a")
+                # (raises where the plan has no kernel for a pre-BN input: the variant is then skipped)
+                C.conv_fwd(x1, None, w, 9, 0, y, None, stats, C.CONV_AUTO, None, 0, None, in_coef=coef,
+                           a_out=a_st if v == 10 else None)
             else:
                 # v = the conv kernel to force (C.CONV_*)
                 C.conv_fwd(x1, x2, w, 9, 0, y, None, stats, v, None, 0, ws)

@@ -411,7 +411,7 @@ class BnRed:
     W: int
     Cdy: int
     Cdx: int
-    splitk: bool   # conv_dgrad_splitk_bnred (else the ring's conv_dgrad_bnred)
+    splitk: bool   # what the plan must answer: a split-K conv whose reduce writes the rows (else the BNRED ring)
     seed: int = 0
 
 

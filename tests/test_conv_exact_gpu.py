@@ -204,13 +204,15 @@ def test_conv_dgrad_bnred_exact(C, b):
     wt = L.dgrad_weight(w).to(DEV)
     out = torch.full((b.N, b.H, b.W, b.Cdx), L.SENTINEL, dtype=L.BF16, device=DEV)
     part = torch.full((1024 * 2 * b.Cdx,), NAN, device=DEV)
-    if b.splitk:
-        ws = _ws(C, (b.N, b.H, b.W, b.Cdy, 0, b.Cdx), 9, "AUTO")
-        T = C.conv_dgrad_splitk_bnred(dy.to(DEV), wt, out, y.to(DEV), coef.to(DEV), part, ws)
-    else:
-        T = C.conv_dgrad_bnred(dy.to(DEV), wt, out, y.to(DEV), coef.to(DEV), part)
+    ws = _ws(C, (b.N, b.H, b.W, b.Cdy, 0, b.Cdx), 9, "AUTO") if b.splitk else None
+    T = C.conv_dgrad(dy.to(DEV), wt, out, None, ws, y.to(DEV), coef.to(DEV), part)
     torch.cuda.synchronize()
-    assert 0 < T <= 1024
+    plan = C.conv_plan(b.N, b.H, b.W, b.Cdy, 0, b.Cdx, ws_elems=ws.numel() if b.splitk else 0, bn=True)
+    assert 0 < T <= 1024 and T == plan["bn_rows"], (T, plan)
+    if b.splitk:
+        assert plan["ksplit"] > 1, plan
+    else:
+        assert (plan["name"], plan["ring_form"]) == ("RING", C.RING_BNRED), plan
     assert torch.equal(out.cpu(), L.expected_bf16(dx))
     got = _stats_sums(part, T, b.Cdx)
     assert (got[0] == sums[0]).all()

@@ -22,7 +22,7 @@ import lattice as L
 from robotic_discovery_platform_amd.models.unet import unet_conv_specs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KNOBS = ("RDP_ROWBAND", "RDP_ROWBAND_X_MAXPIX", "RDP_ROWBAND_R2", "RDP_PP_SPLIT")
+KNOBS = ("RDP_ROWBAND", "RDP_ROWBAND_X_MAXPIX", "RDP_ROWBAND_R2", "RDP_PP_SPLIT", "RDP_SPLITK_BNRED")
 KERNELS = ("AUTO", "HALO", "IGEMM8_128", "IGEMM8_256", "PP256", "PP128", "RING", "PPSK128", "PPSK256", "FIRST", "RING2",
            "RING2X2", "ROWBAND", "IGEMM4_128", "IGEMM4_256")
 INT_KEYS = ("code", "bm", "bn", "waves", "ksplit", "mode", "launches", "grid", "rgrid", "rows", "ws", "pool", "up",
@@ -44,8 +44,9 @@ def driver(tmp_path_factory):
     return exe
 
 
-def _run(exe, lines):
+def _run(exe, lines, **knobs):
     env = {k: v for k, v in os.environ.items() if k not in KNOBS}
+    env.update(knobs)
     env.update(ASAN_OPTIONS="detect_leaks=1:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1")
     r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -58,9 +59,9 @@ def _run(exe, lines):
 
 
 def _plan(n, h, w, c1, c2, cout, kernel="AUTO", taps=9, packed=0, stats=0, ev=0, split=0, ws=0, pool=0, up=0, bn=0,
-          wfrag=0):
+          wfrag=0, bnin=0):
     return (f"plan {n} {h} {w} {c1} {c2} {cout} {taps} {int(packed)} {kernel} {int(stats)} {int(ev)} {split} {ws} "
-            f"{int(pool)} {int(up)} {int(bn)} {int(wfrag)}")
+            f"{int(pool)} {int(up)} {int(bn)} {int(wfrag)} {int(bnin)}")
 
 
 # ---------------------------------------------------------------------------------------------
@@ -91,11 +92,14 @@ def _fwd_queries(n, size, ev, ws):
     return q
 
 
-def _dgrad_queries(n, size, ws):
+def _dgrad_queries(n, size, ws, owned_only=False):
+    """owned_only: the BN-backward operand as the executor offers it, only where dx is the activation gradient of a
+    BN layer -- the second conv of a block, whose input is the first conv's activation (the other input gradients
+    go to a pool or to the concat's halves)."""
     q = []
-    for _, s, c1, c2, cout, packed, _, _ in _unet_layers(size):
+    for i, (_, s, c1, c2, cout, packed, _, _) in enumerate(_unet_layers(size)):
         if not packed:  # dy (cout channels) -> d(input), split over the concat's two sources
-            q.append(_plan(n, s, s, cout, 0, c1 + c2, split=c1 if c2 else 0, ws=ws, bn=1))
+            q.append(_plan(n, s, s, cout, 0, c1 + c2, split=c1 if c2 else 0, ws=ws, bn=i % 2 == 1 or not owned_only))
     return q
 
 
@@ -136,6 +140,32 @@ def test_unet_auto_dispatch_is_pinned(driver, mode, n):
     assert got == PINNED[(mode, n)], [(a, g, e) for a, g, e in zip(names, got, PINNED[(mode, n)]) if g != e]
 
 
+# Where the BN layer that owns each input gradient gets its BN-backward partial rows, from kernel traces of the last
+# commit that chose the dgrad binding in Python (one 256^2 training step at batch 64 and at batch 4, bilinear decoder;
+# profiles/conv_fused_dispatch.md section 2): "ring" = the dgrad is conv_ring_kernel<64, true, ...>, the BNRED
+# instantiation, and bn_bwd_finalize follows it; "splitk" = the dgrad's conv_splitk_reduce_kernel is followed by
+# bn_bwd_finalize directly; "pass" = a bn_relu_bwd_reduce / maxpool2_bwd_bn_reduce / upsample2_bwd kernel runs in
+# between (also every input gradient no BN layer owns). Same order as PINNED[("dgrad", n)].
+BN_ROWS_FROM = {
+    64: ["ring"] + ["pass"] * 15 + ["ring"],
+    4: ["ring", "pass", "pass", "pass", "pass", "pass", "splitk", "pass", "splitk", "pass", "splitk",
+        "pass", "pass", "pass", "pass", "pass", "ring"],
+}
+
+
+@pytest.mark.parametrize("n", sorted(BN_ROWS_FROM))
+def test_unet_dgrad_bn_rows_are_pinned(driver, n):
+    ws = _unet_ws(driver, n, 256, True)
+    got = []
+    for p in _run(driver, _dgrad_queries(n, 256, ws, owned_only=True)):
+        ring = (p["kernel"], p["form"]) == ("RING", "BNRED")
+        assert ring == (p["kernel"] == "RING" and p["bnrows"] > 0), p
+        assert p["bnrows"] == 0 or ring or p["ksplit"] > 1, p
+        got.append("ring" if ring else "splitk" if p["bnrows"] else "pass")
+    names = [l[0] for l in _unet_layers(256)][1:]
+    assert got == BN_ROWS_FROM[n], [(a, g, e) for a, g, e in zip(names, got, BN_ROWS_FROM[n]) if g != e]
+
+
 # ---------------------------------------------------------------------------------------------
 # the sweep: bound, workspace, forced kernels
 # ---------------------------------------------------------------------------------------------
@@ -163,7 +193,7 @@ def _sweep_shapes():
 
 def test_sweep_bound_workspace_forced(driver):
     maps, chans = _sweep_shapes()
-    forms = (dict(stats=1), dict(ev=1, pool=1, wfrag=1), dict(ev=1, up=1), dict(bn=1))
+    forms = (dict(stats=1), dict(ev=1, pool=1, wfrag=1), dict(ev=1, up=1), dict(bn=1), dict(stats=1, bnin=1))
     lines, req = [], []
     for n in (1, 2, 3, 4, 64):
         for h, w in maps:
@@ -192,6 +222,50 @@ def test_sweep_bound_workspace_forced(driver):
     assert not bad_forced, bad_forced[:5]
     assert not bad_ws, bad_ws[:5]
     assert not bad_bound, (len(bad_bound), bad_bound[:5])
+
+
+def _ring_fits(c1, c2, cout, split, h, w):
+    """The old chain's condition for the ring's fused forms: 64 -> 64, one source, one destination, whole 64-pixel
+    row segments, an even number of rows (dense 3x3 weights; none of the sweep's tensors reaches 2 GiB here)."""
+    return c1 == 64 and c2 == 0 and cout == 64 and not split and w % 64 == 0 and h % 2 == 0
+
+
+def test_fused_forms_follow_the_old_chain(driver):
+    """The chain of three bindings the plan replaced, transcribed. Input gradients: the BNRED ring wherever it fit, at
+    any grid size; else the automatic choice, whose split-K reduce wrote the rows where the conv split K; else the
+    plain conv. Forward on a pre-BN input: the BNIN ring or nothing."""
+    maps, chans = _sweep_shapes()
+    shapes = [(n, h, w) + c for n in (1, 2, 3, 4, 64) for h, w in maps for c in chans
+              if not c[3] and n * h * w * max(c[0], c[1], c[2]) * 2 < (1 << 31)]
+    q = {}
+    for key, kw in (("bn", dict(bn=1)), ("plain", {}), ("ring", dict(kernel="RING")), ("bnin", dict(stats=1, bnin=1)),
+                    ("bn_noknob", dict(bn=1))):
+        lines = [_plan(n, h, w, c1, c2, cout, split=split, ws=-1, **{k: v for k, v in kw.items()})
+                 for n, h, w, c1, c2, cout, _, split in shapes if not (split and "stats" in kw)]
+        knobs = dict(RDP_SPLITK_BNRED="0") if key == "bn_noknob" else {}
+        q[key] = iter(_run(driver, lines, **knobs))
+    same = ("kernel", "grid", "ksplit", "rgrid", "ws", "launches")
+    n_ring = n_splitk = 0
+    for n, h, w, c1, c2, cout, _, split in shapes:
+        bn, plain, forced, off = next(q["bn"]), next(q["plain"]), next(q["ring"]), next(q["bn_noknob"])
+        fits = _ring_fits(c1, c2, cout, split, h, w)
+        where = (n, h, w, c1, c2, cout, split)
+        if fits:
+            assert (bn["kernel"], bn["form"]) == ("RING", "BNRED"), (where, bn)
+            assert bn["bnrows"] == bn["rows"] == forced["rows"] > 0 and bn["grid"] == forced["grid"], (where, bn, forced)
+            assert off == bn, (where, off)  # the knob does not touch the ring form
+            n_ring += 1
+        else:
+            assert bn["form"] != "BNRED" and all(bn[k] == plain[k] for k in same), (where, bn, plain)
+            assert bn["bnrows"] in (0, bn["rows"]) and (bn["bnrows"] == 0 or bn["ksplit"] > 1), (where, bn)
+            assert off["bnrows"] == 0 and all(off[k] == plain[k] for k in same), (where, off)
+            n_splitk += bn["bnrows"] > 0
+        if not split:
+            bnin = next(q["bnin"])
+            assert (bnin["kernel"], bnin["form"]) == (("RING", "BNIN") if fits else ("UNSUPPORTED", "-")), (where, bnin)
+            if fits:
+                assert bnin["rows"] == forced["rows"] and bnin["grid"] == forced["grid"], (where, bnin, forced)
+    assert n_ring > 20 and n_splitk > 20, (n_ring, n_splitk)
 
 
 def test_unknown_kernel_is_unsupported(driver):

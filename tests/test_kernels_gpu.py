@@ -352,10 +352,11 @@ def test_bn_relu_train_fwd_bwd(C):
     assert relerr(dg, bn.weight.grad) < 1e-3 and relerr(db, bn.bias.grad) < 1e-3
 
 
-@pytest.mark.parametrize("N,H,W,Cout", [(2, 64, 64, 64), (1, 32, 128, 64), (2, 16, 64, 128)])
+@pytest.mark.parametrize("N,H,W,Cout", [(2, 64, 64, 64), (1, 32, 128, 64), (2, 16, 64, 128), (1, 2, 64, 64)])
 def test_conv_dgrad_bnred(C, N, H, W, Cout):
     """Row-ring dgrad with the next BN's backward reduction in its epilogue: dx identical to the
-    unfused dgrad; the partial sums match torch fp32 sum(g), sum(g * xhat) of the bf16 dx."""
+    unfused dgrad; the partial sums match torch fp32 sum(g), sum(g * xhat) of the bf16 dx. The form has no grid
+    threshold: (1, 2, 64) is one row pair, one block, far below the 256 pairs from which the plain ring is auto."""
     torch.manual_seed(17)
     dev = "cuda"
     dy = bf(torch.randn(N, H, W, 64, device=dev))
@@ -370,11 +371,16 @@ def test_conv_dgrad_bnred(C, N, H, W, Cout):
     coef = torch.cat([mean, inv, scale, shift]).contiguous()
     dx = torch.empty(N, H, W, Cout, dtype=torch.bfloat16, device=dev)
     part = torch.zeros(1024 * 2 * Cout, device=dev)
-    rows = C.conv_dgrad_bnred(dy, wk, dx, y, coef, part)
-    if Cout != 64:  # only the 64-output ring kernel has the fused variant: -1, nothing launched
-        assert rows == -1
+    rows = C.conv_dgrad(dy, wk, dx, None, None, y, coef, part)
+    plan = C.conv_plan(N, H, W, 64, 0, Cout, bn=True)
+    assert rows == plan["bn_rows"], (rows, plan)
+    if Cout != 64:  # only the 64-output ring kernel has the fused variant: the plain dgrad ran, no rows
+        dx_ref = torch.empty_like(dx)
+        C.conv_fwd(dy, None, wk, 9, 0, dx_ref, None, None, C.CONV_AUTO, None, 0)
+        torch.cuda.synchronize()
+        assert rows == 0 and torch.equal(dx, dx_ref)
         return
-    assert rows > 0
+    assert rows > 0 and (plan["name"], plan["ring_form"]) == ("RING", C.RING_BNRED), plan
     dx_ref = torch.empty_like(dx)
     C.conv_fwd(dy, None, wk, 9, 0, dx_ref, None, None, C.CONV_RING, None, 0)  # same ring kernel, no fusion
     torch.cuda.synchronize()
@@ -385,6 +391,27 @@ def test_conv_dgrad_bnred(C, N, H, W, Cout):
     p = part[: rows * 2 * Cout].view(rows, 2, Cout).sum(0)
     assert relerr(p[0], g.sum((0, 1, 2))) < 1e-3
     assert relerr(p[1], (g * (y.float() - mean) * inv).sum((0, 1, 2))) < 1e-3
+
+
+def test_conv_dgrad_without_fused_rows(C):
+    """Where neither the ring nor a split-K reduce can write the owner's rows (8 x 8, no workspace), conv_dgrad
+    still runs the dgrad -- bitwise conv_fwd's -- returns 0 and leaves the partial slab alone."""
+    torch.manual_seed(18)
+    dev = "cuda"
+    dy = bf(torch.randn(1, 8, 8, 64, device=dev))
+    wk = bf(torch.randn(64, 576, device=dev) * 0.05)
+    y = bf(torch.randn(1, 8, 8, 64, device=dev))
+    coef = torch.cat([torch.zeros(64), torch.ones(64), torch.ones(64), torch.zeros(64)]).to(dev)
+    dx = torch.full((1, 8, 8, 64), float("nan"), dtype=torch.bfloat16, device=dev)
+    part = torch.full((1024 * 2 * 64,), float("nan"), device=dev)
+    rows = C.conv_dgrad(dy, wk, dx, None, None, y, coef, part)
+    plan = C.conv_plan(1, 8, 8, 64, 0, 64, bn=True)
+    assert rows == 0 == plan["bn_rows"] and plan["name"] != "RING", (rows, plan)
+    dx_ref = torch.empty_like(dx)
+    C.conv_fwd(dy, None, wk, 9, 0, dx_ref, None, None, C.CONV_AUTO, None, 0)
+    torch.cuda.synchronize()
+    assert torch.equal(dx, dx_ref)
+    assert torch.isnan(part).all()
 
 
 @pytest.mark.parametrize("N,H,W", [(2, 64, 64), (1, 32, 128), (3, 16, 64)])
@@ -407,16 +434,18 @@ def test_conv_bnin_fwd_and_wgrad(C, N, H, W):
     rows_cap = max(1024, C.conv_stats_rows(N * H * W, 64, C.CONV_AUTO))
     st_ref, st = (torch.zeros(rows_cap * 2 * 64, device=dev) for _ in range(2))
     rows_ref = C.conv_fwd(a, None, wk, 9, 0, y_ref, None, st_ref, C.CONV_RING, None, 0)  # ring kernel on a
-    rows = C.conv_fwd_bnin(y_pre, wk, y_out, st, coef)
+    rows = C.conv_fwd(y_pre, None, wk, 9, 0, y_out, None, st, C.CONV_AUTO, None, 0, in_coef=coef)
     torch.cuda.synchronize()
     assert rows == rows_ref > 0
+    plan = C.conv_plan(N, H, W, 64, 0, 64, stats=True, bnin=True)
+    assert (plan["name"], plan["ring_form"], plan["stats_rows"], plan["chunks"]) == ("RING", C.RING_BNIN, rows, 1), plan
     assert torch.equal(y_out, y_ref) and torch.equal(st[: rows * 128], st_ref[: rows * 128])
     assert relerr(nchw(y_out), F.conv2d(nchw(a).float(), w.float(), padding=1)) < 1e-2
     # with a_out: the same outputs, and the formed activation written bitwise as bn_relu_apply writes it
     a_out = torch.full_like(y_pre, 3.0)
     y_out.zero_()
     st.zero_()
-    assert C.conv_fwd_bnin(y_pre, wk, y_out, st, coef, a_out) == rows
+    assert C.conv_fwd(y_pre, None, wk, 9, 0, y_out, None, st, C.CONV_AUTO, None, 0, in_coef=coef, a_out=a_out) == rows
     torch.cuda.synchronize()
     assert torch.equal(y_out, y_ref) and torch.equal(st[: rows * 128], st_ref[: rows * 128])
     assert torch.equal(a_out, a)
@@ -428,7 +457,10 @@ def test_conv_bnin_not_applicable(C):
     coef = torch.ones(256, device=dev)
     y = torch.empty_like(y_pre)
     wk = bf(torch.randn(64, 576, device=dev))
-    assert C.conv_fwd_bnin(y_pre, wk, y, torch.zeros(1024 * 128, device=dev), coef) == -1
+    assert C.conv_plan(1, 16, 48, 64, 0, 64, stats=True, bnin=True)["name"] == "UNSUPPORTED"
+    st = torch.zeros(C.conv_stats_rows(16 * 48, 64, C.CONV_AUTO) * 128, device=dev)
+    with pytest.raises(RuntimeError, match="no kernel for this conv"):  # nothing else can read a pre-BN input
+        C.conv_fwd(y_pre, None, wk, 9, 0, y, None, st, C.CONV_AUTO, None, 0, in_coef=coef)
 
 
 def test_maxpool_fwd_bwd_with_skip(C):
@@ -1255,7 +1287,7 @@ def test_bn_relu_pool_fusions(C, N, H, W, Ch):
 @pytest.mark.parametrize("N,H,Cdy,Cdx", [(4, 32, 512, 256), (4, 16, 512, 512), (2, 8, 128, 64)])
 def test_dgrad_splitk_bnred_matches_separate_reduce(C, N, H, Cdy, Cdx):
     """Split-K dgrad whose reduce also writes the owner BN layer's backward partial rows
-    (conv_dgrad_splitk_bnred, csrc/conv_igemm.hip conv_splitk_reduce_kernel): dx bitwise the plain dgrad,
+    (conv_dgrad, csrc/conv_igemm.hip conv_splitk_reduce_kernel): dx bitwise the plain dgrad,
     the row sums equal bn_relu_bwd_reduce's and the fp32 sums of the same g."""
     torch.manual_seed(12)
     dev = "cuda"
@@ -1271,8 +1303,9 @@ def test_dgrad_splitk_bnred_matches_separate_reduce(C, N, H, Cdy, Cdx):
     ws = torch.zeros(n_ws, device=dev)
     dx = torch.empty(N, H, H, Cdx, dtype=torch.bfloat16, device=dev)
     part = torch.zeros(1024 * 2 * Cdx, device=dev)
-    T = C.conv_dgrad_splitk_bnred(dy, w, dx, y, coef, part, ws)
-    assert T > 0
+    T = C.conv_dgrad(dy, w, dx, None, ws, y, coef, part)
+    plan = C.conv_plan(N, H, H, Cdy, 0, Cdx, ws_elems=n_ws, bn=True)
+    assert T > 0 and T == plan["bn_rows"] and plan["ksplit"] > 1, (T, plan)
     dx_ref = torch.empty_like(dx)
     C.conv_fwd(dy, None, w, 9, 0, dx_ref, None, None, C.CONV_AUTO, None, 0, ws)
     assert torch.equal(dx, dx_ref)
@@ -1364,7 +1397,7 @@ def test_head_bn_fused(C, dice_w):
 
 def test_conv_batch_chunks_subprocess():
     """Batches past the kernels' 2 GiB buffer-offset reach run as image slices (conv_fwd appends the BN
-    partial rows, conv_wgrad accumulates, conv_dgrad_bnred defers to the chunked fallback). The bound
+    partial rows, conv_wgrad accumulates, conv_dgrad runs the slices without the BN-backward rows). The bound
     is lowered with RDP_CONV_CHUNK_BYTES (read once per process) in a child process so the chunked
     path runs on small tensors; results must match the unchunked launches of this process."""
     import os
@@ -1389,7 +1422,12 @@ dy = bf(torch.randn(N, H, W, 128, device=dev))
 slab = torch.zeros(C.wgrad_slab_elems(N, H, W, 128, 128, 9, 0, 64), device=dev)
 out = torch.zeros(128 * 9 * 128, device=dev)
 C.conv_wgrad(x1, x2, dy, 9, 0, 0, slab, out, 0, 64, 0)
-torch.save({"y": y.cpu(), "s": st[: r * 256].view(r, 2, 128).sum(0).cpu(), "g": out.cpu()}, sys.argv[2])
+dx = torch.empty(N, H, W, 64, dtype=torch.bfloat16, device=dev)
+part = torch.zeros(1024 * 2 * 64, device=dev)
+coef = torch.cat([torch.zeros(64), torch.ones(128), torch.zeros(64)]).to(dev)
+bn_rows = C.conv_dgrad(x1, w[:64, :576].contiguous(), dx, None, None, x2, coef, part)
+torch.save({"y": y.cpu(), "s": st[: r * 256].view(r, 2, 128).sum(0).cpu(), "g": out.cpu(), "dx": dx.cpu(),
+            "bn_rows": bn_rows}, sys.argv[2])
 '''
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = []
@@ -1402,6 +1440,8 @@ torch.save({"y": y.cpu(), "s": st[: r * 256].view(r, 2, 128).sum(0).cpu(), "g": 
     assert torch.equal(outs[0]["y"], outs[1]["y"])
     assert torch.allclose(outs[0]["s"], outs[1]["s"], rtol=1e-4, atol=1e-2)
     assert relerr(outs[1]["g"], outs[0]["g"]) < 1e-5
+    # (the slices are below the ring's auto threshold: another kernel, the same dx to bf16 rounding)
+    assert outs[0]["bn_rows"] > 0 and outs[1]["bn_rows"] == 0 and relerr(outs[1]["dx"], outs[0]["dx"]) < 1e-2
 
 
 
